@@ -14,7 +14,10 @@ from the UMI strings to the consensus strings, with per-stage seconds, per-kerne
 milliseconds (HIP events on the launch stream) and a roofline entry for the two dominant
 kernels.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--read-len L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--read-len L] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the timed paths computed (see dump_align / dump_consensus) so that two builds run with
+the same arguments, hence on the same seeded inputs, can be compared output for output.
 
 For N > 1: one rank per GPU under torch.distributed.run -- either started by the caller (RANK / WORLD_SIZE in
 the environment) or, when `python bench.py --gpus N` is run bare, by bench.py itself as a child process; --gpus
@@ -51,6 +54,14 @@ VALU64_PEAK_TLOPS = 256 * 4 * 16 * 2.4e9 / 1e12   # 39.3 T lane-ops/s, fp64
 # the kernel runs it as such: 3 add + 2 min + 2 for the match score = 7
 ALIGN_OPS_PER_CELL = 10
 MSA_OPS_PER_CELL = 7
+# --dump-outputs: every .npy file of one run together stays within DUMP_BYTES; the DP's per-read outputs take up to
+# DUMP_ALIGN_BYTES of it (the default 10^6 reads whole), the pipeline pass's consensus reads the rest.  Samples of larger
+# outputs are drawn with DUMP_SEED alone, so two builds run with the same arguments dump the same rows.
+DUMP_BYTES = 64 * 10**6
+DUMP_ALIGN_BYTES = 40 * 10**6
+DUMP_HEADER_BYTES = 1024          # allowance per file for the .npy header (np.save writes 128 bytes for a 1-D array)
+DUMP_CONSENSUS = 1000             # consensus reads of the pipeline pass dumped at most
+DUMP_SEED = 0
 
 
 def source_sha(names):
@@ -86,6 +97,62 @@ def pmc_record(kernel, sources):
                                            "compare with this line's kernel_ms before reading traffic against it"},
                 "workload": d.get("workload"), "derived": d.get("derived")}
     return {"traffic": None, "traffic_source": None}
+
+
+def save_dump(dump_dir, arrays):
+    """Writes every array of {name: array} as dump_dir/<name>.npy; returns the bytes written."""
+    import numpy as np
+    written = 0
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs writes float32 / float64 only, %s is %s" % (name, a.dtype))
+        path = os.path.join(dump_dir, name + ".npy")
+        np.save(path, a)
+        written += os.path.getsize(path)
+    return written
+
+
+def dump_align(dump_dir, outs):
+    """The DP's outputs as adaptor_align hands them to its caller (per read: score, start, end, start and width of the
+    UMI section), as float64.  Beyond DUMP_ALIGN_BYTES a fixed seeded sample of the reads, their indices in
+    align_read_index."""
+    import numpy as np
+    arrays = {"align_" + k: v.astype(np.float64) for k, v in outs.items()}
+    n, row = len(outs["scores"]), 8 * len(outs)
+    if n * row > DUMP_ALIGN_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ALIGN_BYTES // (row + 8), replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["align_read_index"] = idx.astype(np.float64)
+    return save_dump(dump_dir, arrays)
+
+
+def dump_consensus(dump_dir, r, budget):
+    """What the pipeline pass `r` (pipeline.run_resident) hands to its caller, for a fixed seeded sample of at most
+    DUMP_CONSENSUS of its consensus reads, cut short to fit `budget` bytes of data: their indices, bases and Phred
+    characters (float32 character codes, concatenated, with offsets) and the 1-based read ids of the group each was
+    built from (with offsets)."""
+    import numpy as np
+    cons, phred, goff, gflat = r["cons"], r["phred"], r["goff"], r["gflat"]
+    pick = np.random.default_rng(DUMP_SEED).permutation(len(cons))[:DUMP_CONSENSUS]
+    # per consensus read: bases + qualities (4 B per character each), members, its index and two offsets (8 B each)
+    cost = np.cumsum(8 * cons.widths()[pick] + 8 * np.diff(goff)[pick] + 24)
+    pick = np.sort(pick[:np.searchsorted(cost, budget - 16, side="right")])
+
+    def cat(vals, off, dtype):
+        parts = [vals[off[j]:off[j + 1]] for j in pick]
+        return np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype)
+
+    def offsets(off):
+        return np.concatenate([[0], np.cumsum(np.diff(off)[pick])]).astype(np.float64)
+
+    return save_dump(dump_dir, {
+        "pipeline_consensus_index": pick.astype(np.float64),
+        "pipeline_consensus_offsets": offsets(cons.off),
+        "pipeline_consensus_bases": cat(cons.chars, cons.off, np.float32),
+        "pipeline_consensus_quals": cat(phred.chars, phred.off, np.float32),
+        "pipeline_group_offsets": offsets(goff),
+        "pipeline_group_members": cat(gflat, goff, np.float64),
+    })
 
 
 def cpu_baseline(seq_strings, qual_strings, cores):
@@ -374,9 +441,16 @@ def main():
     ap.add_argument("--giant-virtual-ranks", type=int, default=0,
                     help="on ONE GPU: rehearse the giant pre-group leg at the size of an N = V run (see giant_group_leg)")
     ap.add_argument("--no-giant", action="store_true", help="skip the giant pre-group leg of N > 1 runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write rank 0's outputs of the last timed DP step and of the timed pipeline pass "
+                         "as DIR/<name>.npy (float32 / float64, at most 64 MB in all; fixed seeded samples of larger outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
 
     import numpy as np
     import torch
@@ -469,6 +543,10 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = reduce([elapsed], dist.ReduceOp.MAX)[0]
     all_cells = reduce([float(cells)], dist.ReduceOp.SUM)[0]
+    dumped = 0
+    if rank == 0 and args.dump_outputs:   # (every step rewrites the same buffers: they hold the last one's results)
+        dumped = dump_align(args.dump_outputs, {k: t.cpu().numpy() for k, t in (
+            ("scores", scores), ("starts", starts), ("ends", ends), ("section_starts", sso), ("section_widths", swo))})
 
     out = None
     if rank == 0:
@@ -665,6 +743,8 @@ def main():
             if len(runs) == 1:   # (only the first pass's wall time is reported: its strings go back before the timed pass)
                 runs[0] = {"wall": r["wall"]}
                 del r
+        if rank == 0 and args.dump_outputs:
+            dump_consensus(args.dump_outputs, runs[-1], DUMP_BYTES - dumped - 6 * DUMP_HEADER_BYTES)
         # the same pass with the centre-star alignment (spec v1, round 1's algorithm) for comparison, on every rank
         calls.set_msa_spec(1)
         try:

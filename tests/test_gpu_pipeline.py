@@ -407,3 +407,44 @@ print("rccl ok")
         env.pop(k, None)
     res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0 and "rccl ok" in res.stdout, res.stderr[-2000:]
+
+
+def test_bench_dumps_what_its_timed_steps_computed(tmp_path, enc):
+    """bench.py --dump-outputs: two runs with the same arguments dump identical arrays (float32 / float64, within 64 MB), and
+    the DP's are what sarlacc_adaptor_align on host buffers returns for the same seeded reads."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    from sarlacc_amd import calls, devsynth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, read_len = 3000, 600
+    base = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        base.pop(k, None)
+    dumps = []
+    for rep in range(2):
+        d = tmp_path / ("run%d" % rep)
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--reads", str(n), "--read-len", str(read_len), "--molecules", "400", "--copies", "6",
+                              "--no-cpu", "--no-host-pointer", "--no-quality-align", "--dump-outputs", str(d)],
+                             env=base, capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = json.loads([x for x in res.stdout.splitlines() if x.startswith("{")][0])
+        assert out["steps"] == 3 and out["warmup"] == 1
+        files = sorted(os.listdir(d))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10**6
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    got = dumps[0]
+    assert sorted(got) == sorted(dumps[1]) and {"align_scores", "pipeline_consensus_bases"} <= set(got)
+    for k, v in got.items():
+        assert v.dtype in (np.float32, np.float64) and np.array_equal(v, dumps[1][k]), k
+    assert got["pipeline_consensus_index"].size > 0 and got["pipeline_group_members"].size > 0
+
+    seq, qual, off, _ = devsynth.make_reads(n, read_len, A1, A2, seed=1000, device=torch.device("cuda", 0))
+    seqs, quals = devsynth.to_host_strings(seq, qual, off, n)
+    want = calls.adaptor_align(seqs, quals, enc, 5, 1, A1, [9], [21])
+    assert np.array_equal(got["align_scores"].view(np.int64), want[0].view(np.int64))
+    for name, w in (("starts", want[1]), ("ends", want[2]), ("section_starts", want[3][0]), ("section_widths", want[4][0])):
+        assert np.array_equal(got["align_" + name], w), name

@@ -296,3 +296,78 @@ def test_quality_class_encodings():
     for bad in ("", "sanger", "x", None, 3):
         with pytest.raises(ValueError, match="should be one of"):
             encoding_for_qual_type(bad)
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    """bench.py --steps sets the number of timed steps: none at all is an argument error, before any device is asked for."""
+    import subprocess
+    import sys
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True, timeout=120)
+        assert res.returncode != 0 and "--steps must be at least 1" in res.stderr
+        assert not [x for x in res.stdout.splitlines() if x.startswith("{")]
+
+
+def test_bench_output_dump_sampling_and_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 files only, whole outputs while they fit, beyond that the same seeded
+    sample on every call, within the byte budget."""
+    import bench
+    from sarlacc_amd.strset import StringSet
+    rng = np.random.default_rng(5)
+    n = 3000
+    outs = {"scores": rng.random(n), "starts": rng.integers(1, 500, n, dtype=np.int32), "ends": rng.integers(1, 500, n, dtype=np.int32),
+            "section_starts": rng.integers(1, 500, n, dtype=np.int32), "section_widths": rng.integers(0, 20, n, dtype=np.int32)}
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    whole = tmp_path / "whole"
+    whole.mkdir()
+    bench.dump_align(str(whole), outs)
+    got = load(whole)
+    assert sorted(got) == sorted("align_" + k for k in outs)
+    for k, v in outs.items():
+        assert got["align_" + k].dtype == np.float64 and np.array_equal(got["align_" + k], v)
+
+    monkeypatch.setattr(bench, "DUMP_ALIGN_BYTES", 8000)
+    sampled = []
+    for rep in range(2):
+        d = tmp_path / ("sampled%d" % rep)
+        d.mkdir()
+        written = bench.dump_align(str(d), outs)
+        assert written <= 8000 + 6 * bench.DUMP_HEADER_BYTES
+        sampled.append(load(d))
+    idx = sampled[0]["align_read_index"].astype(np.int64)
+    assert idx.size == 8000 // 48 and (np.diff(idx) > 0).all()
+    for k, v in outs.items():
+        assert np.array_equal(sampled[0]["align_" + k], v[idx]) and np.array_equal(sampled[1]["align_" + k], sampled[0]["align_" + k])
+
+    # consensus reads of a pipeline pass: groups of 2..6 reads, consensus of 50..150 characters
+    ng = 2500
+    sizes = rng.integers(2, 7, ng)
+    goff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    gflat = rng.permutation(int(goff[-1])).astype(np.int32) + 1
+    widths = rng.integers(50, 151, ng)
+    coff = np.concatenate([[0], np.cumsum(widths)]).astype(np.int64)
+    cons = StringSet(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, int(coff[-1]))], coff)
+    phred = StringSet(rng.integers(33, 75, int(coff[-1])).astype(np.uint8), coff.copy())
+    r = {"cons": cons, "phred": phred, "goff": goff, "gflat": gflat}
+    for budget in (10**8, 300_000):
+        dumps = []
+        for rep in range(2):
+            d = tmp_path / ("cons%d_%d" % (budget, rep))
+            d.mkdir()
+            written = bench.dump_consensus(str(d), r, budget)
+            assert written <= budget + 6 * bench.DUMP_HEADER_BYTES
+            dumps.append(load(d))
+        got = dumps[0]
+        for k in got:
+            assert got[k].dtype in (np.float32, np.float64) and np.array_equal(got[k], dumps[1][k]), k
+        pick = got["pipeline_consensus_index"].astype(np.int64)
+        assert 0 < pick.size <= bench.DUMP_CONSENSUS and (np.diff(pick) > 0).all()
+        assert pick.size == bench.DUMP_CONSENSUS or budget < 10**8
+        co, go = got["pipeline_consensus_offsets"].astype(np.int64), got["pipeline_group_offsets"].astype(np.int64)
+        for i, j in enumerate(pick):
+            assert got["pipeline_consensus_bases"][co[i]:co[i + 1]].astype(np.uint8).tobytes() == cons[j].encode()
+            assert got["pipeline_consensus_quals"][co[i]:co[i + 1]].astype(np.uint8).tobytes() == phred[j].encode()
+            assert np.array_equal(got["pipeline_group_members"][go[i]:go[i + 1]], gflat[goff[j]:goff[j + 1]])
