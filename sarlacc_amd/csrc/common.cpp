@@ -124,11 +124,17 @@ int Context::stage_end(const char* name, hipStream_t s) {
     return 0;
 }
 
-void Context::release() {
-    for (auto& kv : ws)
-        if (kv.second.ptr) (void)hipFree(kv.second.ptr);
-    ws.clear();
+int64_t Context::release_matching(const std::function<bool(const std::string&)>& match) {
+    int64_t freed = 0;
+    for (auto it = ws.begin(); it != ws.end();) {
+        if (!match(it->first)) { ++it; continue; }
+        if (it->second.ptr) { (void)hipFree(it->second.ptr); freed += static_cast<int64_t>(it->second.cap); }
+        it = ws.erase(it);
+    }
+    return freed;
 }
+
+void Context::release() { release_matching([](const std::string&) { return true; }); }
 
 int check_encoding(const double* errors, const char* names, int n) {
     if (n <= 0 || !errors || !names) return fail("encoding vector must be non-empty and named");
@@ -179,29 +185,6 @@ void sarlacc_release_workspace(void) {
     sarlacc::ctx().release();
     (void)sarlacc_host_release();   // the idle page-locked result blocks as well
     (void)sarlacc_dev_pool_release();   // ... and the idle device blocks of sarlacc_dev_malloc
-}
-
-int64_t sarlacc_release_umi_workspace(void) {
-    // every buffer umi.hip asks for carries one of these prefixes (encode_and_rank / pair_edges: "u1.", "u2."; the uploads of
-    // the entry points: "g1.", "g2.", "g.", "ps", "lv", "lev"; adjacency "adj."; clustering "cl.")
-    static const char* const prefixes[] = {"u1.", "u2.", "g1.", "g2.", "g.", "ps.", "ps", "lv.", "lv", "lev.", "lev", "adj.", "cl."};
-    sarlacc::Context& c = sarlacc::ctx();
-    int64_t freed = 0;
-    for (auto it = c.ws.begin(); it != c.ws.end();) {
-        bool mine = false;
-        for (const char* pf : prefixes) {
-            const size_t n = std::strlen(pf);
-            const bool whole = pf[n - 1] != '.';   // names without a dot must match entirely
-            if (whole ? it->first == pf : it->first.compare(0, n, pf) == 0) { mine = true; break; }
-        }
-        if (mine) {
-            if (it->second.ptr) { (void)hipFree(it->second.ptr); freed += static_cast<int64_t>(it->second.cap); }
-            it = c.ws.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    return freed;
 }
 
 int64_t sarlacc_workspace_report(char* buf, int64_t cap) {

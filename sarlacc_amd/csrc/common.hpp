@@ -98,6 +98,8 @@ struct Context {
 
     // Returns a cached device buffer of at least `bytes` (grown geometrically).
     int buffer(const char* name, size_t bytes, void** out);
+    // Frees the cached buffers whose name `match` accepts; returns the bytes given back.
+    int64_t release_matching(const std::function<bool(const std::string&)>& match);
     void release();
 };
 
@@ -106,18 +108,18 @@ Context& ctx();
 int ensure_device();
 
 template <typename T>
-int upload(const char* name, const T* host, size_t count, T** dev, hipStream_t s) {
+int upload(const std::string& name, const T* host, size_t count, T** dev, hipStream_t s) {
     void* p = nullptr;
-    SL_TRY(ctx().buffer(name, (count ? count : 1) * sizeof(T), &p));
+    SL_TRY(ctx().buffer(name.c_str(), (count ? count : 1) * sizeof(T), &p));
     if (count) SL_HIP(hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, s));
     *dev = static_cast<T*>(p);
     return 0;
 }
 
 template <typename T>
-int scratch(const char* name, size_t count, T** dev) {
+int scratch(const std::string& name, size_t count, T** dev) {
     void* p = nullptr;
-    SL_TRY(ctx().buffer(name, (count ? count : 1) * sizeof(T), &p));
+    SL_TRY(ctx().buffer(name.c_str(), (count ? count : 1) * sizeof(T), &p));
     *dev = static_cast<T*>(p);
     return 0;
 }

@@ -17,8 +17,7 @@
 //
 // Streaming byte work, HBM-bound: ~2 reads + 1 write of the text.
 #include "common.hpp"
-
-#include <rocprim/rocprim.hpp>
+#include "devprim.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
@@ -227,16 +226,6 @@ __global__ void __launch_bounds__(128) k_fq_copy(const uint8_t* text, const FqRe
     }
 }
 
-template <typename T>
-static int exclusive_scan_i64(const char* tag, const T* d_in, int64_t* d_out, size_t n, hipStream_t s) {
-    size_t tmp = 0;
-    SL_HIP(rocprim::exclusive_scan(nullptr, tmp, d_in, d_out, static_cast<int64_t>(0), n, rocprim::plus<int64_t>(), s));
-    void* d_tmp;
-    SL_TRY(ctx().buffer(tag, tmp ? tmp : 1, &d_tmp));
-    SL_HIP(rocprim::exclusive_scan(d_tmp, tmp, d_in, d_out, static_cast<int64_t>(0), n, rocprim::plus<int64_t>(), s));
-    return 0;
-}
-
 // state of the last sarlacc_dev_fastq_index call on this thread
 struct FqIndex {
     const uint8_t* text = nullptr;
@@ -280,7 +269,7 @@ int sarlacc_dev_fastq_index(const uint8_t* d_text, int64_t nbytes, int64_t* n_re
     SL_HIP(hipMemsetAsync(d_count + ntiles, 0, sizeof(long long), s));
     hipLaunchKernelGGL(k_fq_count, dim3(static_cast<unsigned>(ntiles)), dim3(FQ_THREADS), 0, s, d_text, static_cast<long long>(nbytes), d_count);
     SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan_i64("fq.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
+    SL_TRY(exclusive_scan("fq.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
     long long newlines = 0;
     SL_HIP(hipMemcpyAsync(&newlines, d_base + ntiles, sizeof newlines, hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));
@@ -312,8 +301,8 @@ int sarlacc_dev_fastq_index(const uint8_t* d_text, int64_t nbytes, int64_t* n_re
     hipLaunchKernelGGL(k_fq_records, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, s, d_text, d_lines, nrec,
                        d_rec, d_slen, d_nlen, d_bad);
     SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan_i64("fq.scan", d_slen, d_off, static_cast<size_t>(nrec) + 1, s));
-    SL_TRY(exclusive_scan_i64("fq.scan", d_nlen, d_noff, static_cast<size_t>(nrec) + 1, s));
+    SL_TRY(exclusive_scan("fq.scan", d_slen, d_off, static_cast<size_t>(nrec) + 1, s));
+    SL_TRY(exclusive_scan("fq.scan", d_nlen, d_noff, static_cast<size_t>(nrec) + 1, s));
     unsigned long long bad = 0;
     int64_t tb = 0, tn = 0;
     SL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
@@ -348,7 +337,7 @@ int sarlacc_dev_fastq_split(const uint8_t* d_text, int64_t nbytes, int64_t max_r
     SL_HIP(hipMemsetAsync(d_count + ntiles, 0, sizeof(long long), s));
     hipLaunchKernelGGL(k_fq_count, dim3(static_cast<unsigned>(ntiles)), dim3(FQ_THREADS), 0, s, d_text, static_cast<long long>(nbytes), d_count);
     SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan_i64("fq.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
+    SL_TRY(exclusive_scan("fq.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
     long long newlines = 0;
     SL_HIP(hipMemcpyAsync(&newlines, d_base + ntiles, sizeof newlines, hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));

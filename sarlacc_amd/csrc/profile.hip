@@ -12,8 +12,7 @@
 // pass, an exclusive scan of the counts (rocPRIM, plumbing) and a writing pass, so the lists come out in the reference's
 // order (alignment by alignment, left to right).  Not on the hot path.
 #include "common.hpp"
-
-#include <rocprim/rocprim.hpp>
+#include "devprim.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
@@ -201,12 +200,8 @@ __global__ void __launch_bounds__(64 * PF_WAVES) k_find_errors(const uint8_t* re
 
 static int scan_counts(const char* tag, long long* d_count, size_t n, long long* total, hipStream_t s) {
     // exclusive scan in place over n + 1 entries (the last one, zeroed, receives the total)
-    size_t tmp = 0;
     SL_HIP(hipMemsetAsync(d_count + n, 0, sizeof(long long), s));
-    SL_HIP(rocprim::exclusive_scan(nullptr, tmp, d_count, d_count, 0ll, n + 1, rocprim::plus<long long>(), s));
-    void* d_tmp;
-    SL_TRY(ctx().buffer((std::string(tag) + ".scantmp").c_str(), tmp ? tmp : 16, &d_tmp));
-    SL_HIP(rocprim::exclusive_scan(d_tmp, tmp, d_count, d_count, 0ll, n + 1, rocprim::plus<long long>(), s));
+    SL_TRY(exclusive_scan(std::string(tag) + ".scantmp", d_count, d_count, n + 1, s));
     SL_HIP(hipMemcpyAsync(total, d_count + n, sizeof(long long), hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));
     return 0;
