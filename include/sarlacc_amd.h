@@ -246,6 +246,26 @@ int sarlacc_dev_fastq_split(const uint8_t* d_text, int64_t nbytes, int64_t max_r
 int sarlacc_dev_fastq_extract(const uint8_t* d_text, uint8_t* d_seq, uint8_t* d_qual, int64_t* d_off,
                               uint8_t* d_names, int64_t* d_name_off, void* stream);
 
+/* SAM alignment records already in device memory -> ranges (sam2ranges, R/sam2ranges.R:8-95).  d_text holds
+ * body lines of a SAM file (no header), LF or CRLF, blank lines skipped; first_line is the 1-based file line
+ * number of its first line, used in error messages.  The caller reads the header: ref_names / ref_off (n_ref + 1
+ * offsets) are the seqinfo names in order, '*' included; a record's seqname code is its RNAME's index there.
+ * restricted_mask (n_ref bytes, NULL = no restriction) marks the seqinfo names in `restricted`, extra_names /
+ * extra_off (n_extra + 1 offsets) the `restricted` names that are not seqinfo names.  A record is kept when
+ * !(FLAG & 4), MAPQ >= minq (if use_minq) and RNAME is in `restricted` (if given).  FLAG and MAPQ of every line,
+ * and POS, RNAME and CIGAR of kept lines, are validated; the first bad line is the error.
+ * Step 1 reports the number of lines of the text (a last line without a newline counts), of kept records and of
+ * their QNAME bytes; step 2 fills, for the text indexed last on this thread, n_kept entries of d_ref, d_start,
+ * d_width, d_lclip, d_rclip (int32), d_strand ('+' / '-'), the QNAME bytes into d_names and n_kept + 1 offsets
+ * into d_name_off. */
+int sarlacc_dev_sam_index(const uint8_t* d_text, int64_t nbytes, int64_t first_line, const char* ref_names,
+                          const int64_t* ref_off, int64_t n_ref, const uint8_t* restricted_mask, const char* extra_names,
+                          const int64_t* extra_off, int64_t n_extra, int use_minq, int64_t minq, int64_t* n_lines,
+                          int64_t* n_kept, int64_t* kept_name_bytes, void* stream);
+int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_start, int32_t* d_width,
+                            uint8_t* d_strand, int32_t* d_lclip, int32_t* d_rclip, uint8_t* d_names,
+                            int64_t* d_name_off, void* stream);
+
 /* ------------------------------------------------------------------ */
 /* masked Levenshtein, neighbour search, clustering                      */
 

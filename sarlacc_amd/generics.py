@@ -637,3 +637,18 @@ def errorFinder(ref_aligned, read_aligned):
     barr = np.frombuffer(bases.encode(), dtype=np.uint8) if n else np.zeros(0, np.uint8)
     transition = np.array([[int(cols[y][barr == ord(x)].sum()) for y in "ACGT"] for x in "ACGT"], dtype=np.int64)
     return {"full": full, "transition": transition}
+
+
+# ---------------------------------------------------------------------------
+# sam2ranges (R/sam2ranges.R)
+
+def sam2ranges(sam, minq=10, restricted=None, block_bytes=256 << 20):
+    """sam2ranges (R/sam2ranges.R:8-95): one range per SAM record that is mapped (!(FLAG & 0x4)), has MAPQ >= `minq`
+    (unless `minq` is None) and lies on a reference in `restricted` (unless None), in file order.  The header is read
+    on the host; the body is read in blocks of `block_bytes` and parsed on the device (sam.hip).  Returns a dict in
+    place of the GRanges: "seqnames" (int32 codes into seqinfo["seqnames"], a factor), "start", "end", "width",
+    "left.clip", "right.clip" (int32), "strand" ('+' / '-'), "names" (the QNAMEs) and "seqinfo" ({"seqnames": the @SQ
+    names then '*', "seqlengths": int64, 0 for '*'}).  A header-only or empty file returns the empty result without a
+    device.  Departures from the reference: DESIGN.md §8, "Known deviations"."""
+    from .sam import sam2ranges as _sam2ranges
+    return _sam2ranges(sam, minq=minq, restricted=restricted, block_bytes=block_bytes)
