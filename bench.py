@@ -7,17 +7,23 @@ adaptor (9 fixed + 12 N + 9 fixed), quality-aware local DP with traceback and on
 section (the UMI), go=5, ge=1.  A "step" is one pass of adaptor_align over the
 whole read batch, which is generated once and stays resident in HBM; `value` = GCUPS.
 
-Second half of the headline metric (configs[2] + configs[3]), reported under "pipeline":
+A plain run does only what that figure needs: it sets up, warms up, times the steps, writes its outputs if
+--dump-outputs is given and prints the line (with the kernel time and roofline of the timed steps themselves).
+Everything else runs under --full only:
+
+Second half of the headline metric (configs[2] + configs[3]), reported under "pipeline" by --full runs:
 10^5 molecules x 10 reads x 2 kb generated in HBM, umiGroup (threshold 1, one pre-group
 per GPU) -> multiReadAlign (bandwidth 100) -> consensusReadSeq (quality vote), reads/min
 from the UMI strings to the consensus strings, with per-stage seconds, per-kernel
 milliseconds (HIP events on the launch stream) and a roofline entry for the two dominant
-kernels.
+kernels.  Beside it: spec v1, umiGroup at thresholds 1-3, configs[3] as worded, the giant pre-group leg, the
+host-pointer figures of both halves, the DP at the generic level, the qualityAlign-shaped call and the CPU baselines.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--read-len L] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--read-len L] [--dump-outputs DIR] [--full]
 
 --dump-outputs DIR writes what the timed paths computed (see dump_align / dump_consensus) so that two builds run with
-the same arguments, hence on the same seeded inputs, can be compared output for output.
+the same arguments, hence on the same seeded inputs, can be compared output for output.  A plain run makes the one
+pipeline pass whose consensus reads it dumps (untimed, and only when asked to dump).
 
 For N > 1: one rank per GPU under torch.distributed.run -- either started by the caller (RANK / WORLD_SIZE in
 the environment) or, when `python bench.py --gpus N` is run bare, by bench.py itself as a child process; --gpus
@@ -442,13 +448,18 @@ def main():
                     help="on ONE GPU: rehearse the giant pre-group leg at the size of an N = V run (see giant_group_leg)")
     ap.add_argument("--no-giant", action="store_true", help="skip the giant pre-group leg of N > 1 runs")
     ap.add_argument("--dump-outputs", metavar="DIR",
-                    help="after the timed steps, write rank 0's outputs of the last timed DP step and of the timed pipeline pass "
+                    help="after the timed steps, write rank 0's outputs of the last timed DP step and of the pipeline pass (timed under --full) "
                          "as DIR/<name>.npy (float32 / float64, at most 64 MB in all; fixed seeded samples of larger outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the pipeline half and everything beside the headline (see the module docstring); "
+                         "the --no-* and --giant-* options and --cpu-sample act on these legs")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.giant_virtual_ranks > 0 and not args.full:
+        raise SystemExit("--giant-virtual-ranks rehearses a leg of --full runs: add --full")
     if args.dump_outputs:
         os.makedirs(args.dump_outputs, exist_ok=True)
 
@@ -583,7 +594,7 @@ def main():
         }
 
     # PCIe-inclusive `.Call`-level figure: host pointers in, host pointers out (never `value`)
-    if rank == 0 and not args.no_host_pointer:
+    if rank == 0 and args.full and not args.no_host_pointer:
         h_off = off.cpu().numpy()
         hs = StringSet(seq.cpu().numpy(), h_off)
         hq = StringSet(qual.cpu().numpy(), h_off.copy())
@@ -598,7 +609,7 @@ def main():
         del hs, hq
     # generic level (SURVEY section 8d ii): adaptorAlign on the resident reads -- front / back windows of `tolerance` = 250 bases
     # (R/adaptorAlign.R:86-95), four alignments per read with traceback and sections (:186-189), strand choice
-    if rank == 0 and not args.no_host_pointer:
+    if rank == 0 and args.full and not args.no_host_pointer:
         from sarlacc_amd import generics
         from sarlacc_amd.resident import DevBuffer, DeviceReads
         h_off = off.cpu().numpy()
@@ -656,7 +667,7 @@ def main():
     # qualityAlign-shaped call (R/qualityAlign.R:13-15 -> src/general_align.cpp): the batch's first reads, globally, against a
     # reference as long as they are -- beyond the 1 024 columns one wavefront holds, so one workgroup per alignment: k_align_wide_q
     # (global mode, gapopen >= 0, one strip: wavefronts hand the row state on through LDS queues)
-    if rank == 0 and not args.no_quality_align:
+    if rank == 0 and args.full and not args.no_quality_align:
         # (reads of ONE molecule against that molecule -- what qualityAlign is called on: mockReads' error process, 5 % substitutions
         # and 1 % indel events, on host arrays; qualities of the DP batch)
         nq = min(n, 20000)
@@ -712,7 +723,7 @@ def main():
                     "reference columns, DPP inside a wavefront and LDS queues between wavefronts" % (nq, args.read_len, args.read_len)}
         del hs, hq
     cpu_sample = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # the GPU box gives a one-GPU job a share of 16 host cores (more threads than that only contend)
         cores = max(1, min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 16))
         # the sample stays in HBM until the CPU leg at the end: pulled to the host here (some 10^5 Python strings, 0.8 GB through
@@ -725,7 +736,18 @@ def main():
     sarlacc_amd._lib.lib().sarlacc_release_workspace()
 
     # ------------------------------------------------------------ pipeline (configs[2..4]) -----
-    if not args.no_pipeline:
+    if not args.no_pipeline and not args.full and args.dump_outputs:
+        # a plain run measures none of this: one pass, on the inputs of the --full run's timed pass, for its consensus reads
+        mol = devsynth.make_molecule_reads(args.molecules, args.copies, args.read_len, seed=2000 + rank, device=device)
+        umis = StringSet(mol["umi"].cpu().numpy(), mol["umi_off"].cpu().numpy())
+        fence()
+        r = pipeline.run_resident(umis, mol["seq"], mol["qual"], mol["off"].cpu().numpy(), enc, threshold=args.threshold, dist=D,
+                                  gather_device=device if backend == "nccl" else None)
+        fence()
+        if rank == 0:
+            dump_consensus(args.dump_outputs, r, DUMP_BYTES - dumped - 6 * DUMP_HEADER_BYTES)
+        del r, mol
+    if args.full and not args.no_pipeline:
         mol = devsynth.make_molecule_reads(args.molecules, args.copies, args.read_len, seed=2000 + rank, device=device)
         nr = mol["off"].numel() - 1
         off_host = mol["off"].cpu().numpy()

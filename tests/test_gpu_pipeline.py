@@ -298,7 +298,7 @@ def test_bench_two_ranks_prints_the_contract_line():
     env = dict(os.environ, SARLACC_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", SARLACC_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--reads", "20000", "--read-len", "500", "--molecules", "1500", "--copies", "6", "--no-cpu", "--no-host-pointer"]
+           "--reads", "20000", "--read-len", "500", "--molecules", "1500", "--copies", "6", "--no-cpu", "--no-host-pointer", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [x for x in res.stdout.splitlines() if x.startswith("{")]
@@ -339,7 +339,7 @@ def test_bench_starts_its_own_ranks_and_refuses_missing_gpus():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         base.pop(k, None)
     args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--reads", "8000",
-            "--read-len", "400", "--molecules", "600", "--copies", "6", "--no-cpu", "--no-host-pointer"]
+            "--read-len", "400", "--molecules", "600", "--copies", "6", "--no-cpu", "--no-host-pointer", "--full"]
     env = dict(base, SARLACC_DIST_BACKEND="gloo", SARLACC_BENCH_SHARE_GPU="1")
     res = subprocess.run(args, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -448,3 +448,41 @@ def test_bench_dumps_what_its_timed_steps_computed(tmp_path, enc):
     assert np.array_equal(got["align_scores"].view(np.int64), want[0].view(np.int64))
     for name, w in (("starts", want[1]), ("ends", want[2]), ("section_starts", want[3][0]), ("section_widths", want[4][0])):
         assert np.array_equal(got["align_" + name], w), name
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """bench.py without --full prints the headline line alone: the same figures of its timed DP steps as a --full run, none
+    of the legs beside them, which a --full run adds.  Both dump the same arrays: the plain run's one untimed pipeline pass
+    computes what the --full run's timed pass does."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        base.pop(k, None)
+    # (--full's qualityAlign-shaped leg takes the qualities of its 2 * 10^4 reads from the DP batch: the batch holds more reads)
+    args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "30000",
+            "--read-len", "600", "--molecules", "400", "--copies", "6"]
+    lines, dumps = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full"])):
+        d = tmp_path / mode
+        res = subprocess.run(args + extra + ["--dump-outputs", str(d)], env=base, capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-2000:]
+        found = [x for x in res.stdout.splitlines() if x.startswith("{")]
+        assert len(found) == 1
+        lines[mode] = json.loads(found[0])
+        dumps[mode] = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+    plain, full = lines["plain"], lines["full"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "kernel_ms", "roofline"):
+        assert key in plain and key in full, key
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "config"):
+        assert plain[key] == full[key], key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["steps"] == 2 and plain["warmup"] == 1
+    beside = {"host_pointer", "generic_level", "quality_align_2kb", "pipeline", "cpu_baseline"}
+    assert not beside & set(plain) and beside <= set(full)
+    assert {"spec_v1", "umi_group_thresholds", "c4_pure_groups", "cpu_baseline"} <= set(full["pipeline"])
+    assert sorted(dumps["plain"]) == sorted(dumps["full"]) and {"align_scores", "pipeline_consensus_bases"} <= set(dumps["plain"])
+    for k, v in dumps["plain"].items():
+        assert v.dtype == dumps["full"][k].dtype and np.array_equal(v, dumps["full"][k]), k

@@ -308,6 +308,17 @@ def test_bench_refuses_fewer_than_one_timed_step():
         assert not [x for x in res.stdout.splitlines() if x.startswith("{")]
 
 
+def test_bench_giant_rehearsal_needs_full():
+    """bench.py --giant-virtual-ranks rehearses a leg that only --full runs measure: without --full it is an argument error,
+    before any device is asked for, rather than a run that silently leaves the leg out."""
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--giant-virtual-ranks", "8"], capture_output=True, text=True,
+                         timeout=120)
+    assert res.returncode != 0 and "add --full" in res.stderr
+    assert not [x for x in res.stdout.splitlines() if x.startswith("{")]
+
+
 def test_bench_output_dump_sampling_and_budget(tmp_path, monkeypatch):
     """bench.py --dump-outputs: float32 / float64 files only, whole outputs while they fit, beyond that the same seeded
     sample on every call, within the byte budget."""

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Runs on the GPU box (via gpurun): the default bench line, then rocprofv3 kernel stats and separate
+# Runs on a machine with the GPU: the full bench line (bench.py --full), then rocprofv3 kernel stats and separate
 # PMC passes (FETCH_SIZE, WRITE_SIZE, two SQ/GRBM sets -- MI355X_MICROARCH.md "rocprofv3 PMC
 # slots") of the SAME bench command (DP steps + the 10^6-read pipeline), all into gpurun_out/<tag>/.
 # tools/pmc_summary.py turns the counter CSVs into one JSON per dominant kernel
@@ -29,8 +29,8 @@ info["gpu_agents"] = [l.strip() for l in rinfo.splitlines() if "Marketing Name" 
 json.dump(info, open(sys.argv[1], "w"), indent=1)
 print("box:", info["hostname"], [a for a in info["gpu_agents"] if "Uuid" in a and "GPU" in a][:1])
 PY
-BENCH="python3 $PWD/bench.py --steps 2 --warmup 1 --no-cpu --no-host-pointer $*"
-python3 bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+BENCH="python3 $PWD/bench.py --full --steps 2 --warmup 1 --no-cpu --no-host-pointer $*"
+python3 bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench done"; tail -c 1500 "$OUT/bench.json"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o stats -- $BENCH > "$OUT/stats.log" 2>&1
