@@ -65,11 +65,47 @@ struct ConsArgs {
     int* code_bad;             // smallest row with a quality below the encoding (INT_MAX: none)
 };
 
-__device__ __forceinline__ double dev_log1pexp(double x) {
+__host__ __device__ __forceinline__ double r_log1pexp(double x) {
     // R nmath log1pexp: x <= 18 -> log1p(exp x); 18 < x <= 33.3 -> x + exp(-x); else x
     if (x <= 18.) return log1p(exp(x));
     if (x > 33.3) return x;
     return x + exp(-x);
+}
+
+// The reference's log error of a column from its four scores in ascending order: a running log-sum-exp, less the
+// largest score.  Host and device compile the same source, each against its own libm.
+__host__ __device__ __forceinline__ double log_error(double a, double b, double c, double d) {
+    double denom = a;
+    denom += r_log1pexp(b - denom);
+    denom += r_log1pexp(c - denom);
+    const double err3 = denom;
+    denom += r_log1pexp(d - denom);
+    return err3 - denom;
+}
+
+// ascending sort of four scores (5 compare-exchanges)
+__device__ __forceinline__ void sort4(double& a, double& b, double& c, double& d) {
+    double t;
+    if (a > b) { t = a; a = b; b = t; }
+    if (c > d) { t = c; c = d; d = t; }
+    if (a > c) { t = a; a = c; c = t; }
+    if (b > d) { t = b; b = d; d = t; }
+    if (b > c) { t = b; b = c; c = t; }
+}
+
+// append a column whose Phred value lies within 1e-9 of a rounding boundary to the list the host re-evaluates;
+// GRP: also record its group (k_consensus_qf).  The list's fields come as arguments: a helper that reads them from
+// the kernel's ConsArgs changes the code the compiler makes around it.
+template <bool GRP = false>
+__device__ __forceinline__ void push_fix(int* count, int cap, long long* fpos, double* fval, int* fgrp, long long pos, double a,
+                                         double b, double c, double d, int grp = 0) {
+    const int slot = atomicAdd(count, 1);
+    if (slot < cap) {
+        fpos[slot] = pos;
+        if (GRP) fgrp[slot] = grp;
+        fval[4 * slot + 0] = a; fval[4 * slot + 1] = b;
+        fval[4 * slot + 2] = c; fval[4 * slot + 3] = d;
+    }
 }
 
 template <bool QUALITY>
@@ -186,19 +222,9 @@ __global__ void __launch_bounds__(64) k_consensus(const ConsArgs A) {
             double le;
             double f0, f1, f2 = 0, f3 = 0;
             if (QUALITY) {
-                // ascending sort of the four log-probabilities, then running log-sum-exp
-                double a = sA, b = sC, c = sG, d = sT, t;
-                if (a > b) { t = a; a = b; b = t; }
-                if (c > d) { t = c; c = d; d = t; }
-                if (a > c) { t = a; a = c; c = t; }
-                if (b > d) { t = b; b = d; d = t; }
-                if (b > c) { t = b; b = c; c = t; }
-                double denom = a;
-                denom += dev_log1pexp(b - denom);
-                denom += dev_log1pexp(c - denom);
-                const double err3 = denom;
-                denom += dev_log1pexp(d - denom);
-                le = err3 - denom;
+                double a = sA, b = sC, c = sG, d = sT;
+                sort4(a, b, c, d);
+                le = log_error(a, b, c, d);
                 f0 = a; f1 = b; f2 = c; f3 = d;
             } else {
                 int total = 0;
@@ -222,14 +248,7 @@ __global__ void __launch_bounds__(64) k_consensus(const ConsArgs A) {
                 A.cons[obase + o] = "ACGT"[best];
                 A.phred[obase + o] = static_cast<uint8_t>(static_cast<int>(qv) + 33);
                 if (A.lerr) A.lerr[obase + o] = le;
-                if (near) {
-                    const int slot = atomicAdd(A.fix_count, 1);
-                    if (slot < A.fix_cap) {
-                        A.fix_pos[slot] = obase + o;
-                        A.fix_val[4 * slot + 0] = f0; A.fix_val[4 * slot + 1] = f1;
-                        A.fix_val[4 * slot + 2] = f2; A.fix_val[4 * slot + 3] = f3;
-                    }
-                }
+                if (near) push_fix(A.fix_count, A.fix_cap, A.fix_pos, A.fix_val, A.fix_grp, obase + o, f0, f1, f2, f3);
             }
             outpos += __popcll(kmask);
         }
@@ -262,14 +281,7 @@ __global__ void __launch_bounds__(64) k_consensus(const ConsArgs A) {
 typedef uint32_t __attribute__((aligned(1))) cons_u32_unaligned;
 
 // exact fp64 log error of a column from its four sorted scores (out of line: rare, register-hungry)
-__device__ __noinline__ double exact_log_error(double a, double b, double c, double d) {
-    double denom = a;
-    denom += dev_log1pexp(b - denom);
-    denom += dev_log1pexp(c - denom);
-    const double err3 = denom;
-    denom += dev_log1pexp(d - denom);
-    return err3 - denom;
-}
+__device__ __noinline__ double exact_log_error(double a, double b, double c, double d) { return log_error(a, b, c, d); }
 
 __device__ __forceinline__ double fast_log1pexp(double x) {
     if (x > 33.3) return x;
@@ -419,12 +431,8 @@ __global__ void __launch_bounds__(256, 4) k_consensus_q4(const ConsArgs A) {
                 if (sC > bv) { bv = sC; best = 1; }
                 if (sG > bv) { bv = sG; best = 2; }
                 if (sT > bv) { bv = sT; best = 3; }
-                double a = sA, b = sC, c = sG, d = sT, t;
-                if (a > b) { t = a; a = b; b = t; }
-                if (c > d) { t = c; c = d; d = t; }
-                if (a > c) { t = a; a = c; c = t; }
-                if (b > d) { t = b; b = d; d = t; }
-                if (b > c) { t = b; b = c; c = t; }
+                double a = sA, b = sC, c = sG, d = sT;
+                sort4(a, b, c, d);
                 double denom = a;
                 denom += fast_log1pexp(b - denom);
                 denom += fast_log1pexp(c - denom);
@@ -444,14 +452,7 @@ __global__ void __launch_bounds__(256, 4) k_consensus_q4(const ConsArgs A) {
                 if (qv > 93.0) qv = 93.0;
                 A.cons[obase + o] = "ACGT"[best];
                 A.phred[obase + o] = static_cast<uint8_t>(static_cast<int>(qv) + 33);
-                if (near) {
-                    const int slot = atomicAdd(A.fix_count, 1);
-                    if (slot < A.fix_cap) {
-                        A.fix_pos[slot] = obase + o;
-                        A.fix_val[4 * slot + 0] = a; A.fix_val[4 * slot + 1] = b;
-                        A.fix_val[4 * slot + 2] = c; A.fix_val[4 * slot + 3] = d;
-                    }
-                }
+                if (near) push_fix(A.fix_count, A.fix_cap, A.fix_pos, A.fix_val, A.fix_grp, obase + o, a, b, c, d);
                 ++o;
             }
             outpos += nkept;
@@ -488,6 +489,54 @@ constexpr int QF_STRIP = 7;
 constexpr int QF_ROWB = QF_STRIP * QF_SLOTS * 8;   // 896 bytes per quality value
 constexpr int QF_RB = 6;                           // rows per batch: two scans of three packed counts
 constexpr int QF_THREADS = 1024;
+
+// The results of the kept columns of a lane in k_consensus_qf / k_consensus_code (accumulators in code order A, C, T, G),
+// written from output position obase + o on: the first maximum in the order A, C, G, T (std::max_element) and the
+// Phred character.  The Phred value is estimated in fp32: with u = score - max, S = sum of exp(u) over the three other
+// bases, the log error is log(S / (1 + S)) and the Phred value 10 log10(2) (log2(1 + S) - log2(S)).  Mathematically
+// the value of the reference's log1pexp chain; the fp32 error (< 1e-4 in the Phred value) only matters next to a
+// rounding boundary, where the exact chain is evaluated instead.  GRP: boundary entries record group g.
+// (One helper for the whole loop: a helper per column makes the compiler lay out the stores differently.)
+template <bool GRP>
+__device__ __forceinline__ void emit_columns(const ConsArgs& A, const double (&acc)[4][4], const bool (&keepk)[4], long long obase, int o,
+                                             long long g) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!keepk[k]) continue;
+        const double sA = acc[k][0], sC = acc[k][1], sG = acc[k][3], sT = acc[k][2];
+        const double mx = fmax(fmax(sA, sC), fmax(sG, sT));
+        const int best = sA == mx ? 0 : (sC == mx ? 1 : (sG == mx ? 2 : 3));
+        const float NEG = -1.0e30f;
+        const float uA = best == 0 ? NEG : static_cast<float>(sA - mx), uC = best == 1 ? NEG : static_cast<float>(sC - mx);
+        const float uG = best == 2 ? NEG : static_cast<float>(sG - mx), uT = best == 3 ? NEG : static_cast<float>(sT - mx);
+        const float L2E = 1.44269504088896341f;
+        const float S = (__builtin_amdgcn_exp2f(uA * L2E) + __builtin_amdgcn_exp2f(uC * L2E)) +
+                        (__builtin_amdgcn_exp2f(uG * L2E) + __builtin_amdgcn_exp2f(uT * L2E));
+        float xf = 3.01029995663981195f * (__builtin_amdgcn_logf(1.0f + S) - __builtin_amdgcn_logf(S));   // v_log_f32 = log2
+        const float fr = xf - floorf(xf);
+        int qv;
+        bool near = false;
+        double a = 0, b = 0, c = 0, d = 0;
+        if (xf < 93.4f && fabsf(fr - 0.5f) < 4e-4f) {     // too close for the estimate: the reference's chain in fp64
+            a = sA; b = sC; c = sG; d = sT;
+            sort4(a, b, c, d);
+            const double le = exact_log_error(a, b, c, d);
+            const double x = -10 * le / A.ln10;
+            const double frac = x - floor(x);
+            near = x < 93.4 && fabs(frac - 0.5) < 1e-9;
+            double q = round(x);
+            if (q > 93.0) q = 93.0;
+            qv = static_cast<int>(q);
+        } else {
+            xf = fminf(xf, 93.0f);                          // also takes +inf (S underflowed to 0)
+            qv = static_cast<int>(floorf(xf + 0.5f));
+        }
+        A.cons[obase + o] = "ACGT"[best];
+        A.phred[obase + o] = static_cast<uint8_t>(qv + 33);
+        if (near) push_fix<GRP>(A.fix_count, A.fix_cap, A.fix_pos, A.fix_val, A.fix_grp, obase + o, a, b, c, d, static_cast<int>(g));
+        ++o;
+    }
+}
 
 __device__ __forceinline__ unsigned qf_scan(unsigned x) {   // inclusive prefix sum over the wavefront
     x += static_cast<unsigned>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x111, 0xf, 0xf, false));   // row_shr:1
@@ -648,61 +697,7 @@ __global__ void __launch_bounds__(QF_THREADS) k_consensus_qf(const ConsArgs A) {
                 below_kept += __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0));
                 nkept += __popcll(m);
             }
-            int o = outpos + below_kept;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (!keepk[k]) continue;
-                const double sA = acc[k][0], sC = acc[k][1], sG = acc[k][3], sT = acc[k][2];
-                // first maximum in the order A, C, G, T (std::max_element)
-                const double mx = fmax(fmax(sA, sC), fmax(sG, sT));
-                const int best = sA == mx ? 0 : (sC == mx ? 1 : (sG == mx ? 2 : 3));
-                // Estimate of the Phred value in fp32: with u = score - max, S = sum of exp(u) over the three other
-                // bases, the log error is log(S / (1 + S)) and the Phred value 10 log10(2) (log2(1 + S) - log2(S)).
-                // Mathematically the value of the reference's log1pexp chain; the fp32 error (< 1e-4 in the Phred
-                // value) only matters next to a rounding boundary, where the exact chain is evaluated instead.
-                const float NEG = -1.0e30f;
-                const float uA = best == 0 ? NEG : static_cast<float>(sA - mx), uC = best == 1 ? NEG : static_cast<float>(sC - mx);
-                const float uG = best == 2 ? NEG : static_cast<float>(sG - mx), uT = best == 3 ? NEG : static_cast<float>(sT - mx);
-                const float L2E = 1.44269504088896341f;
-                const float S = (__builtin_amdgcn_exp2f(uA * L2E) + __builtin_amdgcn_exp2f(uC * L2E)) +
-                                (__builtin_amdgcn_exp2f(uG * L2E) + __builtin_amdgcn_exp2f(uT * L2E));
-                float xf = 3.01029995663981195f * (__builtin_amdgcn_logf(1.0f + S) - __builtin_amdgcn_logf(S));   // v_log_f32 = log2
-                float fr = xf - floorf(xf);
-                int qv;
-                bool near = false;
-                double a = 0, b = 0, c = 0, d = 0;
-                if (xf < 93.4f && fabsf(fr - 0.5f) < 4e-4f) {     // too close for the estimate: the reference's chain in fp64
-                    double t;
-                    a = sA; b = sC; c = sG; d = sT;
-                    if (a > b) { t = a; a = b; b = t; }
-                    if (c > d) { t = c; c = d; d = t; }
-                    if (a > c) { t = a; a = c; c = t; }
-                    if (b > d) { t = b; b = d; d = t; }
-                    if (b > c) { t = b; b = c; c = t; }
-                    const double le = exact_log_error(a, b, c, d);
-                    const double x = -10 * le / A.ln10;
-                    const double frac = x - floor(x);
-                    near = x < 93.4 && fabs(frac - 0.5) < 1e-9;
-                    double q = round(x);
-                    if (q > 93.0) q = 93.0;
-                    qv = static_cast<int>(q);
-                } else {
-                    xf = fminf(xf, 93.0f);                          // also takes +inf (S underflowed to 0)
-                    qv = static_cast<int>(floorf(xf + 0.5f));
-                }
-                A.cons[obase + o] = "ACGT"[best];
-                A.phred[obase + o] = static_cast<uint8_t>(qv + 33);
-                if (near) {
-                    const int slot = atomicAdd(A.fix_count, 1);
-                    if (slot < A.fix_cap) {
-                        A.fix_pos[slot] = obase + o;
-                        A.fix_grp[slot] = static_cast<int>(g);
-                        A.fix_val[4 * slot + 0] = a; A.fix_val[4 * slot + 1] = b;
-                        A.fix_val[4 * slot + 2] = c; A.fix_val[4 * slot + 3] = d;
-                    }
-                }
-                ++o;
-            }
+            emit_columns<true>(A, acc, keepk, obase, outpos + below_kept, g);
             outpos += nkept;
         }
         // every quality string consumed exactly, nothing unusual seen: the group is done
@@ -817,56 +812,7 @@ __global__ void __launch_bounds__(QF_THREADS) k_consensus_code(const ConsArgs A)
                 below_kept += __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0));
                 nkept += __popcll(m);
             }
-            int o = outpos + below_kept;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (!keepk[k]) continue;
-                const double sA = acc[k][0], sC = acc[k][1], sG = acc[k][3], sT = acc[k][2];
-                const double mx = fmax(fmax(sA, sC), fmax(sG, sT));
-                const int best = sA == mx ? 0 : (sC == mx ? 1 : (sG == mx ? 2 : 3));
-                // fp32 estimate of the Phred value, the reference's chain in fp64 next to a rounding boundary (see k_consensus_qf)
-                const float NEG = -1.0e30f;
-                const float uA = best == 0 ? NEG : static_cast<float>(sA - mx), uC = best == 1 ? NEG : static_cast<float>(sC - mx);
-                const float uG = best == 2 ? NEG : static_cast<float>(sG - mx), uT = best == 3 ? NEG : static_cast<float>(sT - mx);
-                const float L2E = 1.44269504088896341f;
-                const float S = (__builtin_amdgcn_exp2f(uA * L2E) + __builtin_amdgcn_exp2f(uC * L2E)) +
-                                (__builtin_amdgcn_exp2f(uG * L2E) + __builtin_amdgcn_exp2f(uT * L2E));
-                float xf = 3.01029995663981195f * (__builtin_amdgcn_logf(1.0f + S) - __builtin_amdgcn_logf(S));
-                const float fr = xf - floorf(xf);
-                int qv;
-                bool near = false;
-                double a = 0, b = 0, c = 0, d = 0;
-                if (xf < 93.4f && fabsf(fr - 0.5f) < 4e-4f) {
-                    double t;
-                    a = sA; b = sC; c = sG; d = sT;
-                    if (a > b) { t = a; a = b; b = t; }
-                    if (c > d) { t = c; c = d; d = t; }
-                    if (a > c) { t = a; a = c; c = t; }
-                    if (b > d) { t = b; b = d; d = t; }
-                    if (b > c) { t = b; b = c; c = t; }
-                    const double le = exact_log_error(a, b, c, d);
-                    const double x = -10 * le / A.ln10;
-                    const double frac = x - floor(x);
-                    near = x < 93.4 && fabs(frac - 0.5) < 1e-9;
-                    double q = round(x);
-                    if (q > 93.0) q = 93.0;
-                    qv = static_cast<int>(q);
-                } else {
-                    xf = fminf(xf, 93.0f);
-                    qv = static_cast<int>(floorf(xf + 0.5f));
-                }
-                A.cons[obase + o] = "ACGT"[best];
-                A.phred[obase + o] = static_cast<uint8_t>(qv + 33);
-                if (near) {
-                    const int slot = atomicAdd(A.fix_count, 1);
-                    if (slot < A.fix_cap) {
-                        A.fix_pos[slot] = obase + o;
-                        A.fix_val[4 * slot + 0] = a; A.fix_val[4 * slot + 1] = b;
-                        A.fix_val[4 * slot + 2] = c; A.fix_val[4 * slot + 3] = d;
-                    }
-                }
-                ++o;
-            }
+            emit_columns<false>(A, acc, keepk, obase, outpos + below_kept, g);
             outpos += nkept;
         }
         if (lane == 0) A.cons_len[g] = outpos;
@@ -888,10 +834,36 @@ __global__ void k_consensus_compact(const uint8_t* cons, const uint8_t* phred, c
 }
 
 // ---------------------------------------------------------------------------
-static double host_log1pexp(double x) {
-    if (x <= 18.) return std::log1p(std::exp(x));
-    if (x > 33.3) return x;
-    return x + std::exp(-x);
+// LDS table of k_consensus_qf (width QF_STRIP) and k_consensus_code (CODE_STRIP): per quality the strip (w w w r w ...)
+// of log(e/3) and log1p(-e), every double replicated for QF_SLOTS lanes; a zero row last
+static int upload_strip(const char* name, int width, const std::vector<double>& right, const std::vector<double>& wrong,
+                        const double** dev, hipStream_t s) {
+    const size_t n = right.size();
+    std::vector<double> strip((n + 1) * width * QF_SLOTS, 0.0);
+    for (size_t k = 0; k < n; ++k)
+        for (int i = 0; i < width; ++i)
+            for (int sl = 0; sl < QF_SLOTS; ++sl) strip[(k * width + i) * QF_SLOTS + sl] = (i == 3) ? right[k] : wrong[k];
+    double* d;
+    SL_TRY(upload(name, strip.data(), strip.size(), &d, s));
+    *dev = d;
+    return 0;
+}
+
+// The row table of the alignments in a.aln: row offsets from the first row (rel, one entry past the last row, which is
+// the rows' byte count), first row of every group (grows, ngroups + 1 entries) and output offset of every group.
+static int upload_rows(ConsArgs& a, const std::vector<int64_t>& rel, const int64_t* grows, int64_t ngroups,
+                       const std::vector<int64_t>& out_off, int max_rows, hipStream_t s) {
+    int64_t* d_aoff; int64_t* d_grows; int64_t* d_ooff;
+    SL_TRY(upload("cons.aoff", rel.data(), rel.size(), &d_aoff, s));
+    SL_TRY(upload("cons.grows", grows, static_cast<size_t>(ngroups) + 1, &d_grows, s));
+    SL_TRY(upload("cons.ooff", out_off.data(), out_off.size(), &d_ooff, s));
+    a.aln_off = d_aoff; a.grp_rows = d_grows; a.out_off = d_ooff; a.max_rows = max_rows; a.aln_bytes = rel.back();
+    return 0;
+}
+
+template <typename K>
+static hipError_t allow_lds(K* kernel, size_t bytes) {   // dynamic LDS beyond the default 64 KB
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
 }
 
 static char phred_char(double le) {
@@ -935,25 +907,8 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
         SL_TRY(upload("cons.vec", vec.data(), vec.size(), &d_vec, s));
         a.vec = d_vec;
         a.qoffset = static_cast<int>(enc_names[0]); a.navail = enc_n;
-        // k_consensus_qf: per quality the strip (w w w r w w w), every double replicated for QF_SLOTS lanes; zero row last
-        std::vector<double> strip(static_cast<size_t>(enc_n + 1) * QF_STRIP * QF_SLOTS, 0.0);
-        for (int k = 0; k < enc_n; ++k)
-            for (int i = 0; i < QF_STRIP; ++i)
-                for (int sl = 0; sl < QF_SLOTS; ++sl)
-                    strip[(static_cast<size_t>(k) * QF_STRIP + i) * QF_SLOTS + sl] = (i == 3) ? right[k] : wrong[k];
-        double* d_strip;
-        SL_TRY(upload("cons.strip", strip.data(), strip.size(), &d_strip, s));
-        a.strip = d_strip;
-        if (a.codes) {   // k_consensus_code: (w w w r w w w w) per quality, zero row last
-            std::vector<double> strip8(static_cast<size_t>(enc_n + 1) * CODE_STRIP * QF_SLOTS, 0.0);
-            for (int k = 0; k < enc_n; ++k)
-                for (int i = 0; i < CODE_STRIP; ++i)
-                    for (int sl = 0; sl < QF_SLOTS; ++sl)
-                        strip8[(static_cast<size_t>(k) * CODE_STRIP + i) * QF_SLOTS + sl] = (i == 3) ? right[k] : wrong[k];
-            double* d_strip8;
-            SL_TRY(upload("cons.strip8", strip8.data(), strip8.size(), &d_strip8, s));
-            a.strip8 = d_strip8;
-        }
+        SL_TRY(upload_strip("cons.strip", QF_STRIP, right, wrong, &a.strip, s));                        // k_consensus_qf
+        if (a.codes) SL_TRY(upload_strip("cons.strip8", CODE_STRIP, right, wrong, &a.strip8, s));   // k_consensus_code
     }
     a.ngroups = ng_eval;
     a.mincov = min_cov; a.pseudo = pseudo; a.ln10 = std::log(10);
@@ -996,7 +951,7 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
         if (a.codes) {
             // rows written as vote codes by the MSA stage: nothing to decode
             const size_t ldsc = static_cast<size_t>(enc_n + 1) * QC_ROWB;
-            SL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_consensus_code), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsc)));
+            SL_HIP(allow_lds(&k_consensus_code, ldsc));
             const int gridc = static_cast<int>(std::min<int64_t>((ng_eval + QF_THREADS / 64 - 1) / (QF_THREADS / 64), c.num_cu));
             hipLaunchKernelGGL(k_consensus_code, dim3(gridc), dim3(QF_THREADS), ldsc, s, a);
         } else if (q4) {
@@ -1006,7 +961,7 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
             const bool qf = a.aln_bytes > 0 && a.qual_bytes > 0 && enc_n <= 127 && a.qoffset + enc_n <= 255 && ldsf <= 150 * 1024 &&
                             !option(OPT_CONSENSUS_GENERIC);
             if (qf) {
-                SL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_consensus_qf), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ldsf)));
+                SL_HIP(allow_lds(&k_consensus_qf, ldsf));
                 const int gridf = static_cast<int>(std::min<int64_t>((ng_eval + QF_THREADS / 64 - 1) / (QF_THREADS / 64), c.num_cu));
                 hipLaunchKernelGGL(k_consensus_qf, dim3(gridf), dim3(QF_THREADS), ldsf, s, a);
                 SL_HIP(hipGetLastError());
@@ -1015,10 +970,8 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
             const int grid4 = static_cast<int>(std::min<int64_t>((ng_eval + 3) / 4, static_cast<int64_t>(c.num_cu) * 64));
             hipLaunchKernelGGL(k_consensus_q4, dim3(grid4), dim3(256), lds4, s, a);
         } else {
-            if (lds > 48 * 1024) {   // alignments of thousands of rows: more than the default 64 KB of dynamic LDS
-                SL_HIP(hipFuncSetAttribute(quality ? reinterpret_cast<const void*>(&k_consensus<true>) : reinterpret_cast<const void*>(&k_consensus<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-            }
+            if (lds > 48 * 1024)   // alignments of thousands of rows: more than the default 64 KB of dynamic LDS
+                SL_HIP(quality ? allow_lds(&k_consensus<true>, lds) : allow_lds(&k_consensus<false>, lds));
             if (quality) hipLaunchKernelGGL(k_consensus<true>, dim3(grid), dim3(64), lds, s, a);
             else hipLaunchKernelGGL(k_consensus<false>, dim3(grid), dim3(64), lds, s, a);
         }
@@ -1103,16 +1056,8 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
         for (int k = 0; k < fixn; ++k) {
             if (fg[k] >= 0 && !gflag.empty() && gflag[static_cast<size_t>(fg[k])]) continue;
             double le;
-            if (quality) {
-                double denom = fv[4 * k];
-                denom += host_log1pexp(fv[4 * k + 1] - denom);
-                denom += host_log1pexp(fv[4 * k + 2] - denom);
-                const double err3 = denom;
-                denom += host_log1pexp(fv[4 * k + 3] - denom);
-                le = err3 - denom;
-            } else {
-                le = std::log1p(-((fv[4 * k] + pseudo / 4) / (fv[4 * k + 1] + pseudo)));
-            }
+            if (quality) le = log_error(fv[4 * k], fv[4 * k + 1], fv[4 * k + 2], fv[4 * k + 3]);
+            else le = std::log1p(-((fv[4 * k] + pseudo / 4) / (fv[4 * k + 1] + pseudo)));
             // fix_pos is an index into the uncompacted layout: find its alignment, then its slot
             const long long pos = fp[k];
             const int64_t g = static_cast<int64_t>(std::upper_bound(out_off.begin(), out_off.begin() + ng_eval, pos) - out_off.begin()) - 1;
@@ -1167,13 +1112,10 @@ static int run_consensus(bool quality, const char* aln, const int64_t* aln_off, 
     for (int64_t g = 0; g < ngroups; ++g) out_off[g] = rel[grp_rows[g]];
 
     ConsArgs a{};
-    uint8_t* d_aln; int64_t* d_aoff; int64_t* d_grows; int64_t* d_ooff;
+    uint8_t* d_aln;
     SL_TRY(upload("cons.aln", reinterpret_cast<const uint8_t*>(aln) + base, static_cast<size_t>(total), &d_aln, s));
-    SL_TRY(upload("cons.aoff", rel.data(), rel.size(), &d_aoff, s));
-    SL_TRY(upload("cons.grows", grp_rows, static_cast<size_t>(ngroups) + 1, &d_grows, s));
-    SL_TRY(upload("cons.ooff", out_off.data(), out_off.size(), &d_ooff, s));
-    a.aln = d_aln; a.aln_off = d_aoff; a.grp_rows = d_grows; a.out_off = d_ooff; a.max_rows = max_rows;
-    a.aln_bytes = total;
+    a.aln = d_aln;
+    SL_TRY(upload_rows(a, rel, grp_rows, ngroups, out_off, max_rows, s));
     if (quality) {
         const int64_t qrows = qgrp_rows[ng_eval];
         const int64_t qbase = qual_off[0];
@@ -1284,12 +1226,8 @@ static int msa_consensus_impl(const int64_t* grp_off, const int32_t* grp, int64_
     grows[ngroups] = row;
     rel[nrows] = total;
     ConsArgs a{};
-    int64_t* d_aoff; int64_t* d_grows; int64_t* d_ooff;
-    SL_TRY(upload("cons.aoff", rel.data(), rel.size(), &d_aoff, s));
-    SL_TRY(upload("cons.grows", grows.data(), grows.size(), &d_grows, s));
-    SL_TRY(upload("cons.ooff", out_off.data(), out_off.size(), &d_ooff, s));
-    a.aln = res.d_out; a.aln_off = d_aoff; a.grp_rows = d_grows; a.out_off = d_ooff; a.max_rows = max_rows;
-    a.aln_bytes = total;
+    a.aln = res.d_out;
+    SL_TRY(upload_rows(a, rel, grows.data(), ngroups, out_off, max_rows, s));
     if (codes) { a.codes = res.d_codes; a.code_bad = res.code.d_bad; }
     if (quality) { a.qual = d_q; a.qual_off = d_qoff; a.row_read = res.d_members; a.qual_bytes = qrel[static_cast<size_t>(nseq)]; }
     return consensus_core(quality, a, ngroups, ngroups, nrows, total, out_off, nullptr, 0, min_cov, pseudo_count, enc_errors,

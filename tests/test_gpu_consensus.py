@@ -137,3 +137,76 @@ def test_consensus_of_a_very_deep_alignment(oracle, oenc, enc):
     gb = calls.create_consensus_basic_loop([rows], 0.6, 1.0)
     wb = oracle.create_consensus_basic_loop([rows], 0.6, 1.0)
     assert gb[0] == list(wb[0]) and gb[1] == list(wb[1])
+
+
+def _phred_value(scores):
+    """The reference's Phred value of a column from its four scores (sorted, log1pexp chain), in numpy."""
+    def log1pexp(x):
+        return np.log1p(np.exp(x)) if x <= 18 else (x if x > 33.3 else x + np.exp(-x))
+    a, b, c, d = sorted(scores)
+    denom = a + log1pexp(b - a)
+    denom += log1pexp(c - denom)
+    err3 = denom
+    denom += log1pexp(d - denom)
+    return -10 * (err3 - denom) / np.log(10)
+
+
+def test_rounding_boundary_columns(oracle):
+    """Columns whose Phred value lies within 1e-9 of k + 0.5 are re-evaluated on the host; every kernel must give the
+    oracle's Phred character there."""
+    from sarlacc_amd import calls
+    from sarlacc_amd.encoding import Encoding
+    rng = np.random.default_rng(23)
+    # basic vote: n agreeing rows, Phred value 10 log10((n + pc) / (0.75 pc)) = 20.5
+    n = 5
+    pc = n / (0.75 * 10 ** 2.05 - 1)
+    x = -10 * np.log1p(-((n + pc / 4) / (n + pc))) / np.log(10)
+    assert abs(x - 20.5) < 1e-9
+    aln = ["".join(rng.choice(list("ACGT"), 40))] * n
+    want = oracle.create_consensus_basic(aln, 0.6, pc)
+    got = calls.create_consensus_basic(aln, 0.6, pc)
+    assert got[0] == want[0]
+    assert np.allclose(got[1], want[1], rtol=1e-11, atol=0)
+    wl = oracle.create_consensus_basic_loop([aln, TEST_ALIGN], 0.6, pc)
+    assert calls.create_consensus_basic_loop([aln, TEST_ALIGN], 0.6, pc) == [list(wl[0]), list(wl[1])]
+
+    # quality vote: n agreeing rows of quality '%' give 10 log10(1 + (3 (1 - e) / e)^n / 3) = 25.5; e = 0.43 keeps the
+    # encoding's errors decreasing
+    e = 3 / ((3 * (10 ** 2.55 - 1)) ** (1 / n) + 3)
+    errors = np.power(10.0, -np.arange(94) / 10.0)
+    errors[ord("%") - 33] = e
+    names = bytes(range(33, 127))
+    enc, oenc = Encoding(errors, names), (errors, names)
+    right, wrong = 0.0, 0.0
+    for _ in range(n):
+        right += np.log1p(-e)
+        wrong += np.log(e / 3)
+    assert abs(_phred_value([right, wrong, wrong, wrong]) - 25.5) < 1e-9
+    ngroups, width = 6, 300
+    alns, quals = [], []
+    for g in range(ngroups):
+        row = "".join(rng.choice(list("ACGT"), width))
+        q = "".join("%" if rng.random() < 0.3 else chr(int(rng.integers(40, 75))) for _ in range(width))
+        alns.append([row] * n)
+        quals.append([q] * n)
+    wl = oracle.create_consensus_quality_loop(alns, 0.6, quals, oenc)
+    want = [list(wl[0]), list(wl[1])]
+    got = calls.create_consensus_quality(alns[0], 0.6, quals[0], enc)    # with log errors: the one-column kernel
+    w = oracle.create_consensus_quality(alns[0], 0.6, quals[0], oenc)
+    assert got[0] == w[0]
+    assert np.allclose(got[1], w[1], rtol=1e-11, atol=1e-300)
+    goff = np.arange(0, ngroups * n + 1, n, dtype=np.int64)
+    gvals = np.arange(1, ngroups * n + 1, dtype=np.int32)
+    reads = [r for a in alns for r in a]
+    rquals = [q for qs in quals for q in qs]
+    try:
+        for generic in (0, 1):
+            calls.set_option("consensus_generic", generic)
+            assert calls.create_consensus_quality_loop(alns, 0.6, quals, enc) == want
+            for chars in (0, 1):
+                calls.set_option("consensus_chars", chars)
+                got = calls.msa_consensus_flat(goff, gvals, reads, 0, -1, -5, -1, 100, 0.6, quals=rquals, encoding=enc)
+                assert [got[0].to_strings(), got[1].to_strings()] == want, (generic, chars)
+    finally:
+        calls.set_option("consensus_generic", 0)
+        calls.set_option("consensus_chars", 0)
