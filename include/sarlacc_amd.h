@@ -347,7 +347,8 @@ int sarlacc_set_msa_spec(int spec);
  *   "align_wide_band" (rows either side of the main diagonal whose cells carry traceback codes in k_align_wide_q's first launch; -1: all),
  *   "msa2_budget_gb" (GB a batch of groups may take), "msa2_max_columns" (a lower ceiling of spec v2's profiles),
  *   "msa2_simple_extend" (the extended library by the one-position-per-lane kernel everywhere), "msa2_wide_extend" (largest
- *   group size of the four-positions-per-lane kernel).
+ *   group size of the four-positions-per-lane kernel), "align_locate" (adaptor_align: -1 the snapshot path alone, 1 every read
+ *   through the locator's redo list; sarlacc_stage_count "align_redo" / "align_stalls" report the last such call).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a
  * value.  Nothing in the reference corresponds. */
 int sarlacc_set_option(const char* name, int value);

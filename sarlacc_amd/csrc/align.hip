@@ -85,6 +85,16 @@ struct AlignArgs {
                                        // main diagonal (0: codes of every cell); a walk that leaves them puts its read on the redo list
     int* wide_redo;                    // [0] number of reads on the list, [1 ...] their indices (written by the banded launch)
     const int* wide_list;              // the redo launch: the reads to align (count read from the device: wide_list[-1]); null: reads 0 .. n - 1
+    // MODE 4 (integer locator fill + fp64 window, see LOC_NEG) and its redo launch
+    const int* loc_tab;                // integer cost table: the rows of `tables` scaled by 2^k and rounded, int32 (addressed by colbase / 2)
+    const int* loc_rz;                 // [R+1] integer row 0
+    int loc_GO, loc_GE, loc_D;         // penalties in integer units; candidate margin D
+    int loc_force;                     // testing: every read goes on the redo list
+    double loc_unit, loc_slack, loc_top;  // 2^-k; Delta_int + eps_fp; sum+ smax + max(0, row 0) + 1 (window certificate)
+    int* loc_redo;                     // [0] reads on the redo list, [2 ...] their indices (reset per launch)
+    int* loc_stats;                    // [0] reads redone, [1] walks that stalled at the window top (summed over a call)
+    int* loc_out;                      // [3 n] per read: I_max, lo, hi (x2 units) from MODE 5 for MODE 4
+    const int* read_list;              // the MODE 3 redo launch: loc_redo of the MODE 4 launch ([0] count, reads from [2]); null: reads 0 .. n - 1
 };
 
 // Traceback code of one cell, 4 bits -- the raw outcomes of the cell's four comparisons:
@@ -105,6 +115,7 @@ struct AlignArgs {
 using mask_t = unsigned long long;
 typedef const double __attribute__((address_space(3))) lds_cdouble;
 typedef const uint16_t __attribute__((address_space(3))) lds_cu16;
+typedef const int __attribute__((address_space(3))) lds_cint;
 
 __device__ __forceinline__ int sel32(int if0, int if1, mask_t m) {
     int r;
@@ -168,9 +179,44 @@ static inline int snap_head(int R) { return R + R / 4 + 4; }
 // steps per window: SNAP_P - 1 + head + W lanes + 1, rounded up to the 8-step store granule
 static inline int snap_win(int R, int W) { return (SNAP_P + snap_head(R) + W + 7) / 8 * 8; }
 
+// MODE 4 (adaptor_align, local, gapopen >= 0, dyadic penalties, eight alignments per wave): the same outputs as MODE 3
+// without an fp64 fill.  F is the reference's fp64 DP, T the same DP in real arithmetic, GO = gapopen + gapext, GE = gapext.
+//   * Pass 1, the locator: the DP in int32 with every cost table entry, row 0, GO and GE scaled by 2^k and the table
+//     entries rounded to the nearest integer (-inf -> LOC_NEG).  GO 2^k and GE 2^k must be integers, so the recurrence
+//     itself is exact and every path's value is within (R + 1) / 2 units of 2^k times its real value: |I / 2^k - T| <=
+//     Delta_int = (R + 1) 2^-(k+1) cell for cell.  fl(a + t) is monotone in a and max is exact, so every cell of F is the
+//     fp64 chain of the path it picked and at least the chain of any other path into it; chains whose values are cells
+//     stay inside [-(GO + GE R), sum+ smax] and take at most 2R + 4 + (2 sum+ + GO + GE R) / GE rounded operations, which
+//     bounds |F - T| by eps_fp (host: plan_locate).  The score is max_i X(i), X(i) = max(match, horizontal) at (i, R), and
+//     its landing row l is the first row that reaches it; every row with X(i) = score has I(i) >= I_max - D,
+//     D = ceil(2 (Delta_int + eps_fp) 2^k) + 1.  The fill reports I_max and a superset [lo, hi] of those rows, at the
+//     granularity of an 8-cell block (lo: the last block that lifted column R by more than D; hi: the last block whose X
+//     came within D of column R).
+//   * Window certificate.  A path that visits a row above r0 = lo - Wc and reaches (i >= lo, R) other than by a vertical
+//     step in column R takes at least Wc + 1 - R vertical steps in columns < R: its real value is at most
+//     U = sum+ smax + max(0, row 0) - GO - GE (Wc - R).  Wc is chosen per read from I_max so that U + GO + 1 stays below
+//     F_low = I_max 2^-k - Delta_int - eps_fp <= F(l, R) (the + GO covers an alternative that beats a gap continuation of
+//     the path, which pays GO instead of GE to rejoin it; the + 1 every rounding of such a chain, checked on the host).
+//   * Pass 2: the fp64 DP with traceback codes from r0 (rounded down to 8 rows; r0 < 8: the true row 0) with -inf above it
+//     and zeros in column 0, through hi.  Its cells are <= F and >= every path that stays below r0, so every value on the
+//     reference's path and every comparison the walk reads (one side on the path, the other only smaller in the window,
+//     or, where the other side wins, an alternative the certificate excludes) is the same as in the full DP: the score,
+//     the move bits, both "jump continued" bits and the landing row (the last row of the window's column R that improved
+//     on the row above).  The walk reads only such cells; one that reaches a row above r0 contradicts the proof and is
+//     counted as a stall.
+//   * Safety net: a read whose window exceeds the code tile (snap_win steps: two near-equal hits far apart, a weak best
+//     hit) or whose walk stalls goes on a device-side list, which the MODE 3 kernel then aligns (read_list).
+// Pass 1 runs as a kernel of its own (MODE 5: int32 state only, no walk, a third of the LDS) and hands {I_max, lo, hi} per
+// read to the window kernel (MODE 4) through HBM (12 B per read).
+constexpr int LOC_NEG = -(1 << 29);   // -inf of the integer DP (and of its table entries); cells stay above -2^27
+// resident wavefronts per SIMD of the locator kernel: at 4 it takes 110 VGPRs and spills nothing (at 6 and 8 its steady
+// state reloads spilled registers from scratch)
+constexpr int LOC_WAVES = 4;
+
 // MODE 0: scores only.  MODE 1: scores + reference->read map (adaptor_align), codes streamed.
 // MODE 2: scores + gapped strings + edit distance (general_align).
 // MODE 3: as MODE 1 by snapshots + windowed recompute (LOCAL, !PENSEL only; see SNAP_P).
+// MODE 4: as MODE 3 by an integer locator fill + one fp64 window (ROWF 2 only; see LOC_NEG).
 // LOCAL: free leading read bases + free vertical gaps in the last column (adaptor mode).
 // ROWF: 0 alignments of any width, wave-wide shifts; 1 alignments are 16 lanes wide and start on DPP row
 // boundaries; 2 alignments are 8 lanes wide, two interleaved per DPP row (see lane_shr1).
@@ -190,7 +236,7 @@ static inline int snap_win(int R, int W) { return (SNAP_P + snap_head(R) + W + 7
 template <int K, int MODE, bool LOCAL, int ROWF, int KLAST, bool PENSEL>
 // (six wavefronts per SIMD for the snapshot mode; five with eight alignments per wavefront: four columns per lane need the registers --
 // at six the recompute code spilled -- 2 182 -> 2 213 GCUPS on the same box)
-__global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5) k_align(const AlignArgs A) {
+__global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 3 && ROWF != 2) ? 6 : 5) k_align(const AlignArgs A) {
     constexpr bool ROW16 = ROWF != 0;                      // leaders keep their column-0 inputs through the DPP fill operand
     constexpr int NG = ROWF == 2 ? NGMAX2 : NGMAX;         // alignments per wavefront at most
     // uint16 entries per alignment's ring slot: 512 B slots let a ring address be base | offset; with eight
@@ -224,12 +270,21 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
     const double GO = A.GO, GE = A.GE;
     const int GOhi = hi32(GO), GOlo = lo32(GO), GEhi = hi32(GE), GElo = lo32(GE);
 
-    for (int x = threadIdx.x; x < A.tab_doubles; x += 64 * NWAVES) s_tab[x] = A.tables[x];
+    static_assert(MODE < 4 || (ROWF == 2 && LOCAL && !PENSEL), "the locator runs the interleaved local shape only");
+    // the redo launch after a locator pass with an empty list: nothing to stage
+    if (A.read_list && A.read_list[0] == 0) return;
+    // MODE 5: the integer table (4-byte entries, rows half as long) in place of the fp64 one
+    int* const s_tabi = reinterpret_cast<int*>(smem + RING_BYTES);
+    if (MODE == 5)
+        for (int x = threadIdx.x; x < A.tab_doubles; x += 64 * NWAVES) s_tabi[x] = A.loc_tab[x];
+    else
+        for (int x = threadIdx.x; x < A.tab_doubles; x += 64 * NWAVES) s_tab[x] = A.tables[x];
     uint16_t* const s_ring = reinterpret_cast<uint16_t*>(smem) + wave * NG * SLOT;
     int32_t* const s_map = reinterpret_cast<int32_t*>(s_tab + A.tab_doubles) + wave * A.ngroups * (R + 1);
 
     double vgo[K], vge[K], rz[K];
     int colbase[K];  // LDS byte address of the table rows this column reads (see build_tables)
+    int colbi[K], vgoi[K], vgei[K], rzi[K];   // MODE 4: the same for the integer DP
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int c = c0 + k;
@@ -242,6 +297,12 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
         vgo[k] = last ? 0.0 : GO;
         vge[k] = last ? 0.0 : GE;
         rz[k] = A.rowzero[cc];
+        if (MODE == 5) {
+            colbi[k] = lds0 + RING_BYTES + static_cast<int>(A.colbase[cc] >> 1);
+            vgoi[k] = last ? 0 : A.loc_GO;
+            vgei[k] = last ? 0 : A.loc_GE;
+            rzi[k] = A.loc_rz[cc];
+        }
     }
     const double rz_left = A.rowzero[c0 - 1 <= R ? c0 - 1 : R];
     const int jlast = (R - 1) / K, klast = KLAST >= 0 ? KLAST : (R - 1) % K;
@@ -254,10 +315,12 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
     const int ring_g = lds0 + (wave * NG + g) * static_cast<int>(SLOT * sizeof(uint16_t));  // byte address of this alignment's ring
     __syncthreads();
 
-    const long long nitems = (A.n + A.ngroups - 1) / A.ngroups;
+    const long long nreads = A.read_list ? static_cast<long long>(A.read_list[0]) : A.n;   // redo launch: the list's length
+    const long long nitems = (nreads + A.ngroups - 1) / A.ngroups;
     for (long long item = gwave; item < nitems; item += nwaves) {
-        const long long read = item * A.ngroups + g;
-        const bool valid = lane_on && read < A.n;
+        const long long slot_r = item * A.ngroups + g;
+        const bool valid = lane_on && slot_r < nreads;
+        const long long read = A.read_list ? (valid ? static_cast<long long>(A.read_list[2 + slot_r]) : 0) : slot_r;
         long long start = 0;
         int L = 0;
         if (valid) {
@@ -278,7 +341,7 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
             glen[gg] = gg < A.ngroups ? len : 0;
             Lmax = max(Lmax, glen[gg]);
             // reads past the end of the batch (last work item) compute garbage nobody stores
-            if (gg < A.ngroups && item * A.ngroups + gg < A.n) Lmin = min(Lmin, glen[gg]);
+            if (gg < A.ngroups && item * A.ngroups + gg < nreads) Lmin = min(Lmin, glen[gg]);
         }
 
         // Read staging, one refill (64 positions per alignment) ahead of use: lane -> (alignment sg = lane / 16, four
@@ -351,7 +414,7 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                 const uint32_t code = ((v.b >> (8 + e)) & 1u) ? 4u : ((v.b >> (2 * e)) & 3u);
                 ent[e] = (r + e < slen) ? code * static_cast<uint32_t>(A.row_bytes) + static_cast<uint32_t>(qi << 3) : 0u;
             }
-            if (bad) atomicMin(A.badqual, A.read_base + static_cast<int>(item * A.ngroups + sg));
+            if (bad && !A.read_list) atomicMin(A.badqual, A.read_base + static_cast<int>(item * A.ngroups + sg));
             const uint2 w = make_uint2(ent[0] | (ent[1] << 16), ent[2] | (ent[3] << 16));
             uint16_t* const slot = s_ring + sg * SLOT + (r & (RING - 1));   // r is a multiple of 4: 8-byte aligned
             *reinterpret_cast<uint2*>(slot) = w;
@@ -393,11 +456,13 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
         // alignment of the wave is inside its read, nothing is predicated and all flags are
         // lane masks in SGPRs.
         // TR: 0 no traceback, 1 codes streamed to the per-wave tile (MODE 1/2), 2 landing row +
-        // snapshots (MODE 3 fill), 3 codes of a recomputed window (MODE 3; t counts from toff[])
+        // snapshots (MODE 3 fill), 3 codes of a recomputed window (MODE 3; t counts from toff[]), 5 codes + landing row of
+        // the MODE 4 window
         auto run = [&](auto guard_tag, auto trace_tag, int t_begin, int t_end) {
             constexpr bool GUARD = decltype(guard_tag)::value;
             constexpr int TR = decltype(trace_tag)::value;
-            constexpr bool CODES = TR == 1 || TR == 3;
+            constexpr bool CODES = TR == 1 || TR == 3 || TR == 5;
+            constexpr bool LAND = TR == 2 || TR == 5;
             mask_t m_vnl = GUARD ? 0 : __builtin_amdgcn_ballot_w64(vnl != 0);
             for (int t0 = t_begin; t0 < t_end; t0 += UNR) {
                 if ((t0 & 63) == 0) {
@@ -479,7 +544,7 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                                     vp_hi[k] = sel32(hi32(vgo[k]), hi32(vge[k]), m_vn);
                                     vp_lo[k] = sel32(lo32(vgo[k]), lo32(vge[k]), m_vn);
                                 }
-                                if (TR == 2 && is_last) {
+                                if (LAND && is_last) {
                                     // Column R's score never decreases down the rows (free vertical gaps), so
                                     // "some row of this block improved it" is one comparison per block: the
                                     // score after the block against the running maximum before it.  The
@@ -510,7 +575,7 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                                     vp_hi[k] = vn ? hi32(vge[k]) : hi32(vgo[k]);
                                     vp_lo[k] = vn ? lo32(vge[k]) : lo32(vgo[k]);
                                 }
-                                if (TR == 2) {
+                                if (LAND) {
                                     if (is_last && best > V) land_x2 = x2;
                                 }
                                 if (CODES) {
@@ -547,7 +612,7 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                     x2 += 2;
                 }
                 if (TR == 1) __builtin_nontemporal_store(pk, scr + static_cast<size_t>(t0 / UNR) * 64 + lane);
-                if (TR == 3) scr[static_cast<size_t>(t0 / UNR) * 64 + lane] = pk;
+                if (TR == 3 || TR == 5) scr[static_cast<size_t>(t0 / UNR) * 64 + lane] = pk;
             }
             if (!GUARD) vnl = sel32(0, 1, m_vnl);
         };
@@ -557,22 +622,112 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
         int t_b = Lmin == 0x7fffffff ? 0 : ((Lmin + 1) / UNR) * UNR;  // first block leaving the shortest read
         t_a = min(t_a, nsteps);
         t_b = min(max(t_b, t_a), nsteps);
-        constexpr int TR_FILL = MODE == 3 ? 2 : (MODE >= 1 ? 1 : 0);
-        run(Flag<true>{}, Int<TR_FILL>{}, 0, t_a);
-        run(Flag<false>{}, Int<TR_FILL>{}, t_a, t_b);
-        run(Flag<true>{}, Int<TR_FILL>{}, t_b, nsteps);
+        // MODE 5, pass 1 (see LOC_NEG): the lane of column R ends with I_max and the candidate rows [lo, hi] (x2 units),
+        // which MODE 4 reads back
+        int loc_max = 0, loc_lo = -2, loc_hi = -2;
+        if constexpr (MODE == 4) {
+            if (valid && j == jlast) {
+                loc_max = A.loc_out[3 * read];
+                loc_lo = A.loc_out[3 * read + 1];
+                loc_hi = A.loc_out[3 * read + 2];
+            }
+        } else if constexpr (MODE == 5) {
+            int Si[K], UJi[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) { Si[k] = rzi[k]; UJi[k] = LOC_NEG; }
+            int si_in = 0, lji_in = LOC_NEG, di_prev = A.loc_rz[c0 - 1 <= R ? c0 - 1 : R];
+            const int GOi = A.loc_GO, GEi = A.loc_GE, D = A.loc_D;
+            auto run_loc = [&](auto guard_tag, int t_begin, int t_end) {
+                constexpr bool GUARD = decltype(guard_tag)::value;
+                for (int t0 = t_begin; t0 < t_end; t0 += UNR) {
+                    if ((t0 & 63) == 0) {
+                        int t0s = t0;
+                        asm volatile("" : "+s"(t0s));
+#pragma unroll
+                        for (int ps = 0; ps < NPASS; ++ps) {
+                            stage4(sgs[ps], slens[ps], t0s, pf[ps]);
+                            pf[ps] = fetch4(slens[ps], sstarts[ps], t0s + 64);
+                        }
+                    }
+                    int s_before = 0, xacc = LOC_NEG;   // column R before the block; max of X over the block
+                    const uint32_t ring_blk = static_cast<uint32_t>(ring_g + (x2 & 0xff));
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u) {
+                        int left = si_in, lj = lji_in;
+                        const int s_two_back = di_prev;
+                        bool act = true;
+                        if (GUARD) act = x2 >= 0 && x2 <= x2max;
+                        if (act) {
+                            // staged entries are byte offsets into the fp64 rows: half of one addresses the int32 rows
+                            const int rd = static_cast<int>(*reinterpret_cast<lds_cu16*>(ring_blk + 2u * u)) >> 1;
+                            int diag = di_prev;
+                            di_prev = si_in;
+#pragma unroll
+                            for (int k = 0; k < K; ++k) {
+                                const int H = max(lj - GEi, left - GOi);
+                                lj = H;
+                                const int V = max(UJi[k] - vgei[k], Si[k] - vgoi[k]);
+                                UJi[k] = V;
+                                const int M = diag + *reinterpret_cast<lds_cint*>(static_cast<uint32_t>(colbi[k] + rd));
+                                diag = Si[k];
+                                const int X = max(M, H);
+                                const int best = max(X, V);
+                                Si[k] = best;
+                                left = best;
+                                const bool is_last = KLAST >= 0 ? (k == KLAST) : (k == klast);
+                                if (is_last) {
+                                    // V is column R's running maximum before this row (free vertical gaps)
+                                    if (GUARD) {
+                                        if (best - D > V) loc_lo = x2;
+                                        if (X + D >= best) loc_hi = x2;
+                                    } else {
+                                        if (u == 0) s_before = V;
+                                        xacc = max(xacc, X);
+                                        if (u == UNR - 1) {
+                                            loc_lo = sel32(loc_lo, x2 - 2 * (UNR - 1), __builtin_amdgcn_ballot_w64(best - D > s_before));
+                                            loc_hi = sel32(loc_hi, x2, __builtin_amdgcn_ballot_w64(xacc + D >= best));
+                                        }
+                                    }
+                                }
+                            }
+                        }
+                        si_in = GUARD ? lane_shr1<ROWF>(left, si_in) : lane_shr1<ROWF>(left, s_two_back);
+                        lji_in = lane_shr1<ROWF>(lj, lji_in);
+                        x2 += 2;
+                    }
+                }
+            };
+            run_loc(Flag<true>{}, 0, t_a);
+            run_loc(Flag<false>{}, t_a, t_b);
+            run_loc(Flag<true>{}, t_b, nsteps);
+            loc_max = Si[0];
+#pragma unroll
+            for (int k = 1; k < K; ++k) loc_max = (k == klast) ? Si[k] : loc_max;
+            if (valid && j == jlast) {
+                A.loc_out[3 * read] = loc_max;
+                A.loc_out[3 * read + 1] = loc_lo;
+                A.loc_out[3 * read + 2] = loc_hi;
+            }
+            continue;
+        } else {
+            constexpr int TR_FILL = MODE == 3 ? 2 : (MODE >= 1 ? 1 : 0);
+            run(Flag<true>{}, Int<TR_FILL>{}, 0, t_a);
+            run(Flag<false>{}, Int<TR_FILL>{}, t_a, t_b);
+            run(Flag<true>{}, Int<TR_FILL>{}, t_b, nsteps);
+        }
 
-        if (valid && j == jlast) {
+        if (MODE < 4 && valid && j == jlast) {
             double sc = S[0];
 #pragma unroll
             for (int k = 1; k < K; ++k) sc = (k == klast) ? S[k] : sc;
             A.scores[read] = sc;
         }
 
-        if (MODE == 3) {
+        if (MODE == 3 || MODE == 4) {
             int32_t* map = s_map + g * (R + 1);
             const Word* const wtile = scr;
-            // walk state of the group's leader: position, and the jump chain being measured
+            // walk state of the group's leader: position, and the jump chain being measured (MODE 4: the row is set
+            // after the window)
             int row = (__shfl(land_x2, lane_of(g, jlast)) >> 1) + 1, c = R;
             int phase = 0, chain_n = 0, chain_at = 0;
             unsigned cur = 0;
@@ -580,14 +735,36 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
             int pending = valid ? 1 : 0;
             // every round moves at least one alignment to an earlier snapshot, so the number of rounds
             // is bounded; the explicit bound guarantees that the wave leaves the loop whatever the codes say
-            int rounds_left = (Lmax + W) / SNAP_P + 8;
+            int rounds_left = MODE == 4 ? 1 : (Lmax + W) / SNAP_P + 8;
+            int ts4 = 0;            // MODE 4: first row of the window (0: the true row 0)
+            auto push_redo = [&]() {   // MODE 4: the MODE 3 kernel aligns this read
+                const int at = atomicAdd(A.loc_redo, 1);
+                A.loc_redo[2 + at] = static_cast<int>(read);
+                atomicAdd(A.loc_stats, 1);
+            };
+            if (MODE == 4) {
+                const int lane_r = lane_of(g, jlast);
+                const int imax = __shfl(loc_max, lane_r);
+                const int lo = (__shfl(loc_lo, lane_r) >> 1) + 1, hi = (__shfl(loc_hi, lane_r) >> 1) + 1;
+                // the window certificate: U + GO + 1 < F_low, U = top - 1 - GO - GE (Wc - R)
+                const double f_low = static_cast<double>(imax) * A.loc_unit - A.loc_slack;
+                const double over = floor((A.loc_top - f_low) / GE) + 1.0;
+                const int wc = R + (over > 0.0 ? static_cast<int>(fmin(over, 1.0e6)) : 0);
+                const int r0 = lo - wc;
+                ts4 = r0 < 8 ? 0 : (r0 & ~7);
+                want = hi;
+                if (valid && (want + W + 1 - ts4 > A.snap_win || A.loc_force)) {
+                    if (leader) push_redo();
+                    pending = 0;
+                }
+            }
             while (__builtin_amdgcn_ballot_w64(pending != 0)) {
                 if (--rounds_left < 0) {
                     if (lane == 0) atomicExch(A.badqual + 1, 1);
                     break;
                 }
                 // ---- recompute the window that holds row `want` (per alignment) ----
-                const int ts = pending ? (max(want - A.snap_head, 0) / SNAP_P) * SNAP_P : 0;
+                const int ts = !pending ? 0 : MODE == 4 ? ts4 : (max(want - A.snap_head, 0) / SNAP_P) * SNAP_P;
                 // steps [0, nwin) of the window; [t_wa, t_wb) of them have every lane of every
                 // pending alignment inside its read (the others compute garbage nobody reads)
                 int nwin = 0, t_wa = 0, t_wb = 0x7fffffff;
@@ -608,26 +785,52 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                 t_wb = min(max((t_wb / UNR) * UNR, t_wa), nwin);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                const double* sp = snap + static_cast<size_t>(ts / SNAP_P) * (NSV * 64) + lane;
+                if (MODE == 3) {
+                    const double* sp = snap + static_cast<size_t>(ts / SNAP_P) * (NSV * 64) + lane;
 #pragma unroll
-                for (int k = 0; k < K; ++k) { S[k] = sp[(2 * k) * 64]; UJ[k] = sp[(2 * k + 1) * 64]; }
-                s_in = sp[(2 * K) * 64];
-                lj_in = sp[(2 * K + 1) * 64];
-                diag_prev = sp[(2 * K + 2) * 64];
+                    for (int k = 0; k < K; ++k) { S[k] = sp[(2 * k) * 64]; UJ[k] = sp[(2 * k + 1) * 64]; }
+                    s_in = sp[(2 * K) * 64];
+                    lj_in = sp[(2 * K + 1) * 64];
+                    diag_prev = sp[(2 * K + 2) * 64];
+                } else {
+                    // ts > 0: -inf above row ts, zeros in column 0 (the leaders' inputs); ts == 0: the true row 0
+                    const bool fresh = ts > 0;
+#pragma unroll
+                    for (int k = 0; k < K; ++k) { S[k] = fresh ? NEG_INF : rz[k]; UJ[k] = NEG_INF; }
+                    s_in = (fresh && !leader) ? NEG_INF : 0.0;
+                    lj_in = NEG_INF;
+                    diag_prev = fresh ? (leader ? 0.0 : NEG_INF) : rz_left;
+                    land_x2 = -2;
+                }
                 x2 = 2 * (ts - j - 1);
                 x2max = pending ? 2 * L - 2 : -2;
 #pragma unroll
                 for (int ps = 0; ps < NPASS; ++ps) {
                     const int q = lane >> 4;   // sgs[ps] = q + 4 * ps
                     stoffs[ps] = q == 0 ? toff[4 * ps] : q == 1 ? toff[4 * ps + 1] : q == 2 ? toff[4 * ps + 2] : toff[4 * ps + 3];
+                    // the rows just above the window (lanes 1 .. W - 1 start there); MODE 4 windows may start at any multiple of 8
                     if (stoffs[ps] >= 64) stage4(sgs[ps], slens[ps], stoffs[ps] - 64, fetch4(slens[ps], sstarts[ps], stoffs[ps] - 64));
+                    else if (MODE == 4 && stoffs[ps] > 0) stage4(sgs[ps], slens[ps], 0, fetch4(slens[ps], sstarts[ps], 0));
                     pf[ps] = fetch4(slens[ps], sstarts[ps], stoffs[ps]);
                 }
-                run(Flag<true>{}, Int<3>{}, 0, t_wa);
-                run(Flag<false>{}, Int<3>{}, t_wa, t_wb);
-                run(Flag<true>{}, Int<3>{}, t_wb, nwin);
+                constexpr int TR_WIN = MODE == 4 ? 5 : 3;
+                run(Flag<true>{}, Int<TR_WIN>{}, 0, t_wa);
+                run(Flag<false>{}, Int<TR_WIN>{}, t_wa, t_wb);
+                run(Flag<true>{}, Int<TR_WIN>{}, t_wb, nwin);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                // rows above this one hold no cell of the full DP (MODE 4 with a fresh boundary)
+                const int rtop = (MODE == 4 && ts > 0) ? ts : 0;
+                if (MODE == 4) {
+                    // the score and the landing row come from the window (column R through hi >= l)
+                    row = (__shfl(land_x2, lane_of(g, jlast)) >> 1) + 1;
+                    if (pending && j == jlast) {
+                        double sc = S[0];
+#pragma unroll
+                        for (int k = 1; k < K; ++k) sc = (k == klast) ? S[k] : sc;
+                        A.scores[read] = sc;
+                    }
+                }
 
                 // ---- leaders walk (src/reference_align.cpp:231-278) until done or out of window ----
                 if (pending && leader) {
@@ -635,7 +838,7 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                     auto code_at = [&](int cc, int rr, unsigned& out) -> bool {
                         const int jj = (cc - 1) / K, kk = (cc - 1) % K;
                         const int tt = rr + jj - ts;
-                        if (tt < 0) return false;
+                        if (tt < 0 || rr < rtop) return false;
                         const Word w = wtile[static_cast<size_t>(tt / UNR) * 64 + lane_of(g, jj)];
                         out = static_cast<unsigned>(w >> (4 * (CELLS - 1 - ((tt % UNR) * K + kk)))) & 15u;
                         return true;
@@ -647,7 +850,7 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                             while (c > 0 && row > 0) {
                                 const int jj = (c - 1) / K, kk = (c - 1) % K;
                                 const int tt = row + jj - ts;
-                                if (tt < 0) break;
+                                if (tt < 0 || row < rtop) break;
                                 const Word w = wtile[static_cast<unsigned>(tt / UNR) * 64u + static_cast<unsigned>(lane_of(g, jj))];
                                 if (!((w >> (4 * (CELLS - 1 - ((tt % UNR) * K + kk)))) & 2u)) break;
                                 map[c] = row * 2 + 1;
@@ -684,6 +887,11 @@ __global__ void __launch_bounds__(64 * NWAVES, (MODE == 3 && ROWF != 2) ? 6 : 5)
                             row -= 1 + chain_n;  // up moves leave the map untouched (:286)
                             phase = 0;
                         }
+                    }
+                    if (MODE == 4 && stalled) {
+                        atomicAdd(A.loc_stats + 1, 1);
+                        push_redo();
+                        pending = 0;
                     }
                     if (!stalled) {
                         pending = 0;
@@ -1573,6 +1781,60 @@ static void build_cost_rows(const std::vector<double>& tab, int n, const uint32_
     colbase[0] = colbase[R ? 1 : 0];
 }
 
+// MODE 4 (see LOC_NEG): the integer tables and the constants of the exactness argument, or false when the call is not
+// eligible (it then runs MODE 3): GE > 0, gapopen >= 0, GO 2^k and GE 2^k integers, and an integer range that fits.
+struct LocPlan {
+    std::vector<int> tab, rz;
+    int k = 0, GO = 0, GE = 0, D = 0;
+    double unit = 0, slack = 0, top = 0;
+};
+static bool plan_locate(const std::vector<double>& rows, const std::vector<uint32_t>& colbase, int n, int R, double GO,
+                        double GE, const std::vector<double>& rowzero, int64_t max_len, LocPlan& p) {
+    if (!(GE > 0) || !(GO >= GE) || !std::isfinite(GO) || R < 1) return false;
+    double splus = 0, wmax = 0;   // sum over columns of max(0, largest entry); largest finite |entry|
+    for (double v : rows) {
+        if (std::isnan(v) || v == std::numeric_limits<double>::infinity()) return false;
+        if (std::isfinite(v)) wmax = std::max(wmax, std::fabs(v));
+    }
+    for (int col = 1; col <= R; ++col) {
+        double smax = 0;
+        const size_t b = colbase[col] / sizeof(double);
+        for (size_t x = 0; x < static_cast<size_t>(5 * n); ++x) smax = std::max(smax, rows[b + x]);
+        splus += smax;
+    }
+    double rzplus = 0, rzmag = 0;
+    for (double v : rowzero) { rzplus = std::max(rzplus, v); rzmag = std::max(rzmag, std::fabs(v)); }
+    const double bneg = GO + GE * R + rzmag;   // every cell is >= -bneg (the horizontal path from column 0, or row 0)
+    const double bpos = splus + rzplus;        // ... and <= bpos
+    const double bmag = std::max(bneg, bpos) + wmax + GO;   // largest intermediate of a chain whose values are cells
+    // a chain of cells falls by at most 2 bpos + bneg in all, at least GE per vertical step
+    const double nops = 2.0 * R + 4.0 + (2.0 * bpos + bneg) / GE;
+    const double eps = 2.0 * nops * bmag * std::ldexp(1.0, -53);
+    // any chain of the window certificate, at most 2 (max_len + R) operations on values above -(bmag + GE max_len)
+    const double lenx = static_cast<double>(max_len) + R + 2.0;
+    const double eps_alt = 2.0 * 2.0 * lenx * (bmag + GE * lenx) * std::ldexp(1.0, -53);
+    if (!(eps + eps_alt < 0.25)) return false;
+    // largest k whose range (with the margin D ~ R + 3 units) stays below 2^27 in magnitude
+    int k = 24;
+    while (k > 0 && (bmag + GE) * std::ldexp(1.0, k) + 2.0 * (R + 4) > std::ldexp(1.0, 27)) --k;
+    if ((bmag + GE) * std::ldexp(1.0, k) + 2.0 * (R + 4) > std::ldexp(1.0, 27)) return false;
+    const double go = std::ldexp(GO, k), ge = std::ldexp(GE, k);
+    if (go != std::floor(go) || ge != std::floor(ge)) return false;   // not dyadic at this k: nor at any smaller one
+    p.k = k;
+    p.GO = static_cast<int>(go);
+    p.GE = static_cast<int>(ge);
+    p.tab.resize(rows.size());
+    for (size_t x = 0; x < rows.size(); ++x)
+        p.tab[x] = std::isfinite(rows[x]) ? static_cast<int>(std::nearbyint(std::ldexp(rows[x], k))) : LOC_NEG;
+    p.rz.resize(rowzero.size());
+    for (size_t x = 0; x < rowzero.size(); ++x) p.rz[x] = static_cast<int>(std::nearbyint(std::ldexp(rowzero[x], k)));
+    p.D = (R + 1) + static_cast<int>(std::ceil(2.0 * eps * std::ldexp(1.0, k))) + 1;
+    p.unit = std::ldexp(1.0, -k);
+    p.slack = (R + 1) * std::ldexp(1.0, -(k + 1)) + eps;
+    p.top = bpos + 1.0;
+    return true;
+}
+
 struct Shape { int K, W, ngroups, rowf; };   // rowf: see k_align's ROWF
 
 // Columns per lane / lanes per alignment / alignments per wave for a reference
@@ -1623,7 +1885,16 @@ static int launch_pen(bool pensel, int mode, bool local, const AlignArgs& a, int
 
 template <int K, int KLAST>
 static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStream_t s) {
-    if (mode == 3) hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
+    if (mode == 4) {
+        // the locator (its LDS: rings + the integer table), the windows, then the snapshot kernel on the reads the windows
+        // put on their list (count read on the device)
+        const size_t lds5 = sizeof(uint16_t) * NWAVES * NGMAX2 * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
+        hipLaunchKernelGGL((k_align<K, 5, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
+        hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
+        AlignArgs r = a;
+        r.read_list = a.loc_redo;
+        hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, r);
+    } else if (mode == 3) hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
     else hipLaunchKernelGGL((k_align<K, 0, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
     SL_HIP(hipGetLastError());
     return 0;
@@ -1634,7 +1905,7 @@ static int launch_k(int K, int rowf, int R, bool pensel, int mode, bool local, c
     const int klast = (R - 1) % K;
     if (rowf == 2) {
         // interleaved alignments: local mode without penalty selects only (adaptor_align by snapshots, score-only)
-        if (!local || pensel || !(mode == 3 || mode == 0)) return fail("sarlacc_amd: interleaved alignments serve local modes 0 and 3 only");
+        if (!local || pensel || !(mode == 3 || mode == 4 || mode == 0)) return fail("sarlacc_amd: interleaved alignments serve local modes 0 and 3 only");
         const int key = K * 4 + klast;
         switch (key) {
             case 2 * 4 + 0: return launch_il<2, 0>(mode, a, grid, lds, s);
@@ -1870,6 +2141,12 @@ static int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t
         per_wave_elems = static_cast<size_t>(snap_win(R, sh.W) / tb_steps) * 64 +
                          nsnap * (2 * sh.K + 3) * 64 * (sizeof(double) / word_bytes);
     }
+    // ... and, where eligible, by the integer locator + one fp64 window, the snapshot kernel redoing the reads it
+    // cannot certify (same tiles).  align_locate = -1: the snapshot path alone (A/B)
+    LocPlan lp;
+    if (kernel_mode == 3 && sh.rowf == 2 && option(OPT_ALIGN_LOCATE) >= 0 &&
+        plan_locate(rows, colbase, enc_n, R, GO, GE, rowzero, max_len, lp))
+        kernel_mode = 4;
     // Far more workgroups than fit at once: each wave then owns only a few work items and the
     // hardware hands out workgroups as CUs free up, which balances the load much better than an
     // exactly resident grid with a static stride (1.74 -> 2.07 TCUPS at 1M x 2kb; flat from 128 to
@@ -1899,6 +2176,27 @@ static int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t
     a.read_base = co.read_base; a.sec_stride = co.sec_stride ? co.sec_stride : n;
     a.snap_head = snap_head(R); a.snap_win = snap_win(R, sh.W);
     a.aln_ref = out.d_aln_ref; a.aln_qry = out.d_aln_qry; a.aln_len = out.d_aln_len; a.edits = out.d_edits;
+    int* d_stats = nullptr;
+    if (kernel_mode == 4) {
+        int *d_ltab, *d_lrz, *d_redo;
+        if (co.init_bad) {
+            SL_TRY(upload("align.ltab", lp.tab.data(), lp.tab.size(), &d_ltab, stream));
+            SL_TRY(upload("align.lrz", lp.rz.data(), lp.rz.size(), &d_lrz, stream));
+            const int zero[2] = {0, 0};
+            SL_TRY(upload("align.lstats", zero, 2, &d_stats, stream));
+            if (!co.finish) SL_HIP(hipStreamSynchronize(stream));
+        } else {
+            SL_TRY(scratch("align.ltab", lp.tab.size(), &d_ltab));
+            SL_TRY(scratch("align.lrz", lp.rz.size(), &d_lrz));
+            SL_TRY(scratch("align.lstats", 2, &d_stats));
+        }
+        SL_TRY(scratch("align.lredo", static_cast<size_t>(n) + 2, &d_redo));
+        SL_TRY(scratch("align.lout", static_cast<size_t>(n) * 3, &a.loc_out));
+        SL_HIP(hipMemsetAsync(d_redo, 0, 2 * sizeof(int), stream));
+        a.loc_tab = d_ltab; a.loc_rz = d_lrz; a.loc_redo = d_redo; a.loc_stats = d_stats;
+        a.loc_GO = lp.GO; a.loc_GE = lp.GE; a.loc_D = lp.D; a.loc_force = option(OPT_ALIGN_LOCATE) == 1 ? 1 : 0;
+        a.loc_unit = lp.unit; a.loc_slack = lp.slack; a.loc_top = lp.top;
+    }
 
     const size_t lds = sizeof(uint16_t) * NWAVES * (sh.rowf == 2 ? NGMAX2 * (RING + RING_MIRROR) : NGMAX * RING_SLOT) + sizeof(double) * rows.size() +
                        sizeof(int32_t) * NWAVES * sh.ngroups * (R + 1) + 16;
@@ -1910,10 +2208,17 @@ static int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t
     c.timed = true;
 
     if (!co.finish) return 0;
-    int flags[2] = {0, 0};
+    int flags[2] = {0, 0}, lstats[2] = {0, 0};
     SL_HIP(hipMemcpyAsync(flags, d_bad, sizeof flags, hipMemcpyDeviceToHost, stream));
+    if (d_stats) SL_HIP(hipMemcpyAsync(lstats, d_stats, sizeof lstats, hipMemcpyDeviceToHost, stream));
     SL_HIP(hipStreamSynchronize(stream));
     *bad_qual_read = flags[0];
+    // adaptor_align calls: reads the locator handed to the snapshot kernel, and walks of its window that stalled (-1: the
+    // call ran the snapshot path alone)
+    if (kernel_mode == 3 || kernel_mode == 4) {
+        c.counts["align_redo"] = d_stats ? lstats[0] : -1.0;
+        c.counts["align_stalls"] = d_stats ? lstats[1] : -1.0;
+    }
     if (flags[1]) return fail("sarlacc_amd: internal error: an alignment traceback exceeded its bound");
     return 0;
 }

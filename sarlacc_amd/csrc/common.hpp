@@ -67,6 +67,7 @@ enum Opt {
     OPT_ALIGN_WIDE_BAND,      // k_align_wide_q with traceback: rows either side of the main diagonal that carry codes in the first launch (default 96; -1: every cell)
     OPT_MSA2_SIMPLE_EXTEND,   // spec v2: the extended library by the one-position-per-lane kernel also for unit weights (A/B, tests)
     OPT_MSA2_WIDE_EXTEND,     // spec v2: largest group size that takes the four-positions-per-lane extension kernel (default 12; A/B)
+    OPT_ALIGN_LOCATE,         // adaptor_align: -1 the snapshot path instead of the integer locator fill + fp64 window (A/B); 1 every read on the redo list (tests)
     OPT_N
 };
 int option(Opt o);
