@@ -86,7 +86,7 @@ def cost_tables(errors):
 
 def align_one(ref, seq, qual, encoding, gapopen, gapext, local=True, want_dirs=False):
     errors, names, nenc = _enc(encoding)
-    ref_b, seq_b, qual_b = ref.encode(), seq.encode(), qual.encode()
+    ref_b, seq_b, qual_b = ref.encode(), seq.encode(), qual.encode() if isinstance(qual, str) else bytes(qual)
     score = C.c_double()
     L, R = len(seq_b), len(ref_b)
     dirs = np.zeros((R + 1, L + 1), dtype=np.int32) if want_dirs else None

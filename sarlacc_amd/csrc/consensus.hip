@@ -958,8 +958,10 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
             // clean groups on the fast kernel (one 1024-thread workgroup per CU around a ~85 KB strip table in LDS);
             // whatever it flags is redone by the generic kernel
             const size_t ldsf = static_cast<size_t>(enc_n + 1) * QF_ROWB;
-            const bool qf = a.aln_bytes > 0 && a.qual_bytes > 0 && enc_n <= 127 && a.qoffset + enc_n <= 255 && ldsf <= 150 * 1024 &&
-                            !option(OPT_CONSENSUS_GENERIC);
+            // (its byte-parallel index arithmetic -- QOFF4, QZERO4, KHI -- takes the first name and first name + enc_n as
+            // bytes 0..255: a table whose names start at or above byte 128, a negative signed char, goes to k_consensus_q4)
+            const bool qf = a.aln_bytes > 0 && a.qual_bytes > 0 && enc_n <= 127 && a.qoffset >= 0 && a.qoffset + enc_n <= 255 &&
+                            ldsf <= 150 * 1024 && !option(OPT_CONSENSUS_GENERIC);
             if (qf) {
                 SL_HIP(allow_lds(&k_consensus_qf, ldsf));
                 const int gridf = static_cast<int>(std::min<int64_t>((ng_eval + QF_THREADS / 64 - 1) / (QF_THREADS / 64), c.num_cu));

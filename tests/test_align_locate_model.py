@@ -13,6 +13,8 @@ import math
 import numpy as np
 import pytest
 
+from tests.encodings import TABLE_IDS, TABLES, draw_quals
+
 LOC_NEG = -(1 << 29)
 ADAPTOR = "ACGATCAGC" + "N" * 12 + "GTCAGTCAG"
 FILLED = "ACGATCAGC" + "ACGTTGCAAGTC" + "GTCAGTCAG"
@@ -23,7 +25,7 @@ def costs(oracle, oenc, ref, reads, quals):
     entries each column can address and every entry of the device table (for plan_locate)."""
     errors, names = oenc
     m, mm = oracle.cost_tables(errors)
-    n, off = len(errors), names[0]
+    n, off = len(errors), int(np.int8(np.uint8(names[0])))   # the first name as the reference reads it: a signed char
     Lmax = max(1, max(len(r) for r in reads))
     w = np.zeros((len(reads), Lmax, len(ref)))
     colvals, used = [], [m[0], mm[0]]
@@ -37,7 +39,7 @@ def costs(oracle, oenc, ref, reads, quals):
         for b, (s, q) in enumerate(zip(reads, quals)):
             if not s:
                 continue
-            loc = np.minimum(np.frombuffer(q.encode(), np.uint8).astype(int) - off, n - 1)
+            loc = np.minimum(np.frombuffer(q.encode() if isinstance(q, str) else q, np.int8).astype(int) - off, n - 1)
             if r in "ACGT":
                 hit = np.frombuffer(s.encode(), np.uint8) == ord(r)
                 w[b, :len(s), c] = np.where(hit, m[0][loc], mm[0][loc])
@@ -49,6 +51,8 @@ def costs(oracle, oenc, ref, reads, quals):
 def plan_locate(colvals, entries, R, GO, GE, max_len):
     """align.hip plan_locate, statement by statement."""
     if not (GE > 0 and GO >= GE):
+        return None
+    if np.isnan(entries).any() or (entries == np.inf).any():
         return None
     fin = entries[np.isfinite(entries)]
     wmax = float(np.max(np.abs(fin))) if fin.size else 0.0
@@ -67,12 +71,20 @@ def plan_locate(colvals, entries, R, GO, GE, max_len):
     k = 24
     while k > 0 and (bmag + GE) * 2.0 ** k + 2.0 * (R + 4) > 2.0 ** 27:
         k -= 1
+    if (bmag + GE) * 2.0 ** k + 2.0 * (R + 4) > 2.0 ** 27:
+        return None
     go, ge = math.ldexp(GO, k), math.ldexp(GE, k)
     if go != math.floor(go) or ge != math.floor(ge):
         return None
     return dict(k=k, GO=int(go), GE=int(ge), D=(R + 1) + int(math.ceil(2.0 * eps * 2.0 ** k)) + 1,
                 unit=2.0 ** -k, slack=(R + 1) * 2.0 ** -(k + 1) + eps, top=bpos + 1.0,
                 rz=[int(np.rint(math.ldexp(v, k))) for v in rowzero])
+
+
+def locator_plan(oracle, oenc, ref, gapopen, gapext, max_len):
+    """plan_locate for a call of adaptor_align as the host makes it (None: the call takes the snapshot path)."""
+    _, colvals, entries = costs(oracle, oenc, ref, [""], [""])
+    return plan_locate(colvals, entries, len(ref), gapopen + gapext, gapext, max_len)
 
 
 def locate(w, lens, plan, R, block=None):
@@ -304,6 +316,25 @@ def test_model_matches_oracle(oracle, oenc, qlo, qhi):
     reads = _families(qlo + qhi, 300)
     quals = _quals(reads, qhi, qlo, qhi)
     assert check(oracle, oenc, reads, quals, ADAPTOR, 5, 1, [9], [21]) == 0
+
+
+# Tables the model's plan_locate refuses at (ADAPTOR, 5 / 1); every other table of tests/encodings.py is eligible.  The
+# GPU test (tests/test_gpu_encodings.py) expects the locator path exactly where this says so.
+REFUSED = ()
+
+
+@pytest.mark.parametrize("table", TABLES, ids=TABLE_IDS)
+def test_model_matches_oracle_under_other_tables(oracle, table):
+    """The exactness argument's constants (k, D, slack, top) come from the table: the same families under every table
+    of tests/encodings.py, qualities drawn from the first name to six past the last."""
+    reads = _families(5, 60)
+    quals = draw_quals(table, [len(r) for r in reads], 17)
+    plan = locator_plan(oracle, table.oenc, ADAPTOR, 5, 1, max(len(r) for r in reads))
+    if table.name in REFUSED:
+        assert plan is None
+        return
+    assert plan is not None and 0 < plan["k"] <= 24
+    assert check(oracle, table.oenc, reads, quals, ADAPTOR, 5, 1, [9], [21]) == 0
 
 
 @pytest.mark.parametrize("ref,go,ge", [("ACGTACGTAC", 2, 0.5), (ADAPTOR, 0, 1), ("ACGTNNNNACGTRYACGTVHACGT", 5, 1), ("A", 3, 1)])

@@ -24,7 +24,12 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
-def rand_quals(reads, seed, lo=33, hi=126):
+def rand_quals(reads, seed, lo=33, hi=126, table=None):
+    """Phred+33 characters lo..hi as str; with a table of tests/encodings.py, bytes drawn over that table (every entry,
+    the first and last names, characters past the last)."""
+    if table is not None:
+        from tests.encodings import draw_quals
+        return draw_quals(table, [len(r) for r in reads], seed)
     rng = np.random.default_rng(seed)
     return [rng.integers(lo, hi + 1, len(r)).astype(np.uint8).tobytes().decode() for r in reads]
 

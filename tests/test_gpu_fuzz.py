@@ -15,3 +15,13 @@ def test_fuzz_slice(block):
         seed = 7_000_003 * (block + 1) + k
         fuzz.CASES[k % len(fuzz.CASES)](np.random.default_rng(seed))
     fuzz.case_umi_large(np.random.default_rng(11 * (block + 1)))
+
+
+@pytest.mark.parametrize("block", range(2))
+def test_fuzz_slice_other_encodings(block):
+    """The quality-aware cases with the table drawn from tests/encodings.py (alignment, consensus, masking, the fused
+    MSA + consensus)."""
+    from tools import fuzz
+    for k in range(120):
+        seed = 9_000_011 * (block + 1) + k
+        fuzz.ENC_CASES[k % len(fuzz.ENC_CASES)](np.random.default_rng(seed))

@@ -130,6 +130,74 @@ def test_scores_equal_textbook_dp(oracle, oenc, seed):
         assert abs(s_glo - gotoh(ref, read, errs_of(qual), go, ge, False)) < 1e-8
 
 
+def table_errs(table, qual):
+    """The error probability of every quality byte under a table of tests/encodings.py, restated: the index is the
+    signed char minus the signed first name, clamped to the last entry."""
+    idx = [(b - 256 if b >= 128 else b) - table.first for b in qual]
+    assert min(idx, default=0) >= 0
+    return [float(table.errors[min(i, len(table) - 1)]) for i in idx]
+
+
+@pytest.mark.parametrize("name", ["solexa", "n128_high", "n256", "zero_tail", "one_head", "tiny"])
+def test_scores_equal_textbook_dp_under_other_tables(oracle, name):
+    """The same restatement under tables other than Phred+33: names at and above byte 128, every byte a name, entries of
+    exactly 0.0 and 1.0 (costs of -inf), qualities past the last name."""
+    from tests.encodings import BY_NAME, draw_quals
+    table = BY_NAME[name]
+    rng = np.random.default_rng(len(name))
+    seen_inf = False
+    for trial in range(40):
+        R = int(rng.integers(1, 25))
+        L = int(rng.integers(0, 40))
+        ref = "".join(rng.choice(list("ACGTMRWSYKVHDBN") if trial % 2 else list("ACGT"), R))
+        read = "".join(rng.choice(list("ACGT"), L))
+        qual = draw_quals(table, [L], trial)[0]
+        go, ge = ((5, 1), (20, 1), (1, 1), (2.5, 0.75))[int(rng.integers(0, 4))]
+        s_loc = oracle.adaptor_align([read], [qual], table.oenc, go, ge, ref)[0][0]
+        s_glo = oracle.barcode_align([read], [qual], table.oenc, go, ge, ref)[0]
+        for got, local in ((s_loc, True), (s_glo, False)):
+            want = gotoh(ref, read, table_errs(table, qual), go, ge, local)
+            seen_inf = seen_inf or want == -math.inf
+            assert got == want if math.isinf(want) else abs(got - want) < 1e-8, (trial, local)
+
+
+def test_cost_tables_against_higher_precision(oracle):
+    """cost_tables against log2(g (1 - e) 4 + (1 - g) e 4/3) evaluated in exact rationals (the argument) and
+    numpy.longdouble (the logarithm), for every table of tests/encodings.py; entries of 0.0 and 1.0 give -inf exactly
+    where the argument is zero.  Tolerance: the argument is computed in three rounded fp64 operations and the quotient
+    log / ln 2 in two more, each within 2^-53 relative; the logarithm turns a relative error d of its argument into an
+    absolute d / ln 2, so 8 x 2^-53 absolute plus 4 x 2^-53 relative covers it."""
+    from fractions import Fraction
+
+    from tests.encodings import TABLES
+    ld = np.longdouble
+    ln2 = np.log(ld(2))
+
+    def log_int(n):
+        """ln of a positive integer of any size: its leading 64 bits as a long double (relative error 2^-63)."""
+        sh = max(n.bit_length() - 64, 0)
+        return np.log(ld(n >> sh)) + sh * ln2
+
+    for table in TABLES:
+        m, mm = oracle.cost_tables(table.errors)
+        for mode in range(4):
+            g = Fraction(1, mode + 1)
+            for j, e in enumerate(table.errors):
+                ef = Fraction(float(e))
+                for got, gg in ((m[mode][j], g), (mm[mode][j], 1 - g)):
+                    arg = gg * (1 - ef) * 4 + (1 - gg) * ef * Fraction(4, 3)
+                    if arg == 0:
+                        assert got == -np.inf, (table.name, mode, j)
+                        continue
+                    want = (log_int(arg.numerator) - log_int(arg.denominator)) / ln2
+                    assert np.isfinite(got), (table.name, mode, j)
+                    assert abs(ld(got) - want) <= 2.0 ** -50 + 2.0 ** -51 * abs(want), (table.name, mode, j, got, want)
+    # (the Phred control of the quirks test, and the two -inf entries by name)
+    from tests.encodings import BY_NAME
+    assert oracle.cost_tables(BY_NAME["zero_tail"].errors)[1][0][-1] == -np.inf
+    assert oracle.cost_tables(BY_NAME["one_head"].errors)[0][0][0] == -np.inf
+
+
 def test_sections_match_alignment_strings(oracle, oenc):
     # section extraction must agree with the columns of the gapped strings (same idea as
     # test-adaptor-align.R:87-118, with general_align's strings standing in for alignedPattern)

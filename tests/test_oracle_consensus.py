@@ -106,6 +106,30 @@ def test_quality_matches_qualfun(oracle, oenc, aln, upper):
         assert np.allclose(lerr, we, rtol=1e-9, atol=1e-9)
 
 
+@pytest.mark.parametrize("name", ["solexa", "n128_high", "n150_wrap", "zero_tail"])
+@pytest.mark.parametrize("aln", [TEST_ALIGN, N_ALIGN])
+def test_quality_matches_qualfun_under_other_tables(oracle, name, aln):
+    """The same restatement of the quality vote under tables other than Phred+33, qualities drawn from the first name to
+    six past the last (those take the last entry's probability)."""
+    from tests.encodings import BY_NAME, draw_quals
+    from tests.test_oracle_align import table_errs
+    table = BY_NAME[name]
+    last = table.first + len(table) - 1
+    total = sum(len(r.replace("-", "")) for r in aln)
+    # the whole table; then its last 40 entries and the characters past them (not fewer: probabilities below 1e-8 are
+    # raised to 1e-8, and a column of equal weights is an exact tie that the two summation orders may break differently)
+    for lo in (None, max(0, len(table) - 40)):
+        qbytes = draw_quals(table, [len(r.replace("-", "")) for r in aln], len(name) + len(aln), lo=lo)
+        qnum = [np.array(table_errs(table, q)) for q in qbytes]
+        if lo is not None and last < 127 and total >= 46:
+            assert max((b - 256 if b >= 128 else b) for q in qbytes for b in q) > last
+        for cov in (0.6, 0.2, 0.9):
+            cons, lerr = oracle.create_consensus_quality(aln, cov, qbytes, table.oenc)
+            wc, we = qualfun(aln, qnum, cov)
+            assert cons == wc
+            assert np.allclose(lerr, we, rtol=1e-9, atol=1e-9)
+
+
 def test_quality_errors_and_loop(oracle, oenc):
     cons, lerr = oracle.create_consensus_quality([], 0.6, [], oenc)
     assert cons == "" and lerr.size == 0

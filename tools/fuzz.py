@@ -421,7 +421,148 @@ def case_profile(rng):
     assert err or same(g, o), "find_errors"
 
 
+# ---- the quality-aware cases under a table drawn from tests/encodings.py (Phred+33 is one of them): new functions, so
+# that the seeded draws of the cases above stay what they were ----
+def _table(rng):
+    from tests.encodings import TABLES
+    return TABLES[int(rng.integers(0, len(TABLES)))]
+
+
+def tqual(rng, table, n, bad=0.0):
+    """n quality bytes over the table's names and up to six past the last; with probability `bad` one below the first."""
+    pool = table.pool()
+    q = pool[rng.integers(0, len(pool), n)].tobytes()
+    if n and table.below() is not None and rng.random() < bad:
+        k = int(rng.integers(0, n))
+        q = q[:k] + table.below() + q[k + 1:]
+    return q
+
+
+def case_align_enc(rng):
+    t = _table(rng)
+    R = int(rng.choice([1, 2, 5, 16, 18, 22, 30, 31, 33, 64, 70, 130, 257]))
+    n = int(rng.integers(1, 40))
+    Lmax = int(rng.choice([0, 3, 30, 150, 700]))
+    adaptor = rstr(rng, R, IUPAC if rng.random() < 0.5 else "ACGT")
+    if rng.random() < 0.3:
+        adaptor = ("ACGATCAGC" + "N" * 12 + "GTCAGTCAG")   # the locator's shape
+    reads = [rstr(rng, int(rng.integers(0, Lmax + 1)), "ACGT" if rng.random() < 0.7 else "ACGTN") for _ in range(n)]
+    if rng.random() < 0.7:   # plant a noisy copy
+        k = int(rng.integers(0, n))
+        core = "".join(c if c in "ACGT" else "ACGT"[int(rng.integers(0, 4))] for c in adaptor)
+        pos = int(rng.integers(0, len(reads[k]) + 1))
+        reads[k] = reads[k][:pos] + core + reads[k][pos:]
+    quals = [tqual(rng, t, len(r), 0.002) for r in reads]
+    go, ge = [(5, 1), (20, 1), (1, 1), (2.5, 0.75), (0, 1), (2, 0.5), (7.25, 2.5), (-1, 2), (0.1, 0.7)][int(rng.integers(0, 9))]
+    R = len(adaptor)
+    nsec = int(rng.integers(0, 4))
+    ss = sorted(int(x) for x in rng.integers(0, R, nsec))
+    se = [int(rng.integers(s, R) + 1) for s in ss]
+    g, o, err = both(lambda: calls.adaptor_align(reads, quals, t.enc, go, ge, adaptor, ss, se),
+                     lambda: O.adaptor_align(reads, quals, t.oenc, go, ge, adaptor, ss, se))
+    if not err:
+        assert np.array_equal(bits(g[0]), bits(o[0])), "adaptor scores (%s)" % t.name
+        assert np.array_equal(g[1], o[1]) and np.array_equal(g[2], o[2]), "adaptor positions (%s)" % t.name
+        for a, b in zip(g[3] + g[4], o[3] + o[4]):
+            assert np.array_equal(a, b), "sections (%s)" % t.name
+    g, o, err = both(lambda: calls.barcode_align(reads, quals, t.enc, go, ge, adaptor),
+                     lambda: O.barcode_align(reads, quals, t.oenc, go, ge, adaptor))
+    if not err:
+        assert np.array_equal(bits(g), bits(o)), "barcode scores (%s)" % t.name
+    if R <= 130 and Lmax <= 150:
+        g, o, err = both(lambda: calls.general_align(reads, quals, t.enc, go, ge, adaptor, False),
+                         lambda: O.general_align(reads, quals, t.oenc, go, ge, adaptor))
+        if not err:
+            assert np.array_equal(bits(g[0]), bits(o[0])) and np.array_equal(g[1], o[1]), "general scores/edits (%s)" % t.name
+            assert g[2] == o[2] and g[3] == o[3], "general strings (%s)" % t.name
+
+
+def case_consensus_enc(rng):
+    t = _table(rng)
+    alns, quals = [], []
+    p_n = float(rng.choice([0.0, 0.0, 0.03]))
+    for _ in range(int(rng.integers(1, 10))):
+        nrows = int(rng.integers(0, int(rng.choice([30, 30, 80]))))
+        W = int(rng.integers(0, int(rng.choice([400, 400, 1200]))))
+        truth = rng.choice(list("ACGT"), W) if W else np.array([], dtype="<U1")
+        rows, qs = [], []
+        for _ in range(nrows):
+            r = truth.copy()
+            if W:
+                sub = rng.random(W) < 0.1
+                r[sub] = rng.choice(list("ACGT"), int(sub.sum()))
+                r[rng.random(W) < p_n] = "N"
+                if rng.random() < 0.02:
+                    r[int(rng.integers(0, W))] = "acgtRY"[int(rng.integers(0, 6))]
+                r[rng.random(W) < rng.choice([0.05, 0.4])] = "-"
+            row = "".join(r)
+            rows.append(row)
+            qs.append(tqual(rng, t, len(row.replace("-", "")), 0.002))
+        alns.append(rows)
+        quals.append(qs)
+    cov = float(rng.choice([0.0, 0.2, 0.5, 0.6, 0.9, 1.0]))
+    generic = int(rng.random() < 0.3)
+    calls.set_option("consensus_generic", generic)
+    try:
+        g, o, err = both(lambda: calls.create_consensus_quality_loop(alns, cov, quals, t.enc),
+                         lambda: O.create_consensus_quality_loop(alns, cov, quals, t.oenc))
+    finally:
+        calls.set_option("consensus_generic", 0)
+    if not err:
+        assert g[0] == list(o[0]) and g[1] == list(o[1]), "consensus quality (%s, generic %d)" % (t.name, generic)
+
+
+def case_mask_enc(rng):
+    t = _table(rng)
+    n = int(rng.integers(0, 50))
+    seqs = [rstr(rng, int(rng.integers(0, 80)), "ACGTN") for _ in range(n)]
+    quals = [tqual(rng, t, len(s), 0.005) for s in seqs]
+    thr = float(rng.choice([0.0, 1.0, 0.01, float(t.errors[int(rng.integers(0, len(t)))]), float(t.errors[-1])]))
+    g, o, err = both(lambda: calls.mask_bad_bases(seqs, quals, t.enc, thr), lambda: O.mask_bad_bases(seqs, quals, t.oenc, thr))
+    if not err:
+        assert g == o, "mask (%s)" % t.name
+
+
+def case_fused_enc(rng):
+    """sarlacc_msa_consensus with qualities against the oracle's quick_msa followed by its consensus."""
+    from sarlacc_amd.mock import NUC, mutate
+    from sarlacc_amd.strset import csr_from_lists
+    t = _table(rng)
+    reads, groups = [], []
+    for _ in range(int(rng.integers(1, 8))):
+        L = int(rng.choice([0, 5, 60, 300, 700]))
+        truth = NUC[rng.integers(0, 4, L)]
+        idx = []
+        for _ in range(int(rng.integers(0, 9))):
+            reads.append(mutate(truth, rng, 0.08, 0.03).tobytes().decode() if L else "")
+            idx.append(len(reads))
+        groups.append(idx)
+    if not reads:
+        reads = ["ACGT"]
+    if rng.random() < 0.3:
+        reads = ["".join("N" if rng.random() < 0.03 else c for c in r) for r in reads]
+    quals = [tqual(rng, t, len(r), 0.003) for r in reads]
+    params = [(0, -1, -5, -1), (0, -1, -1, -5), (1, -2, -2, -2)][int(rng.integers(0, 3))]
+    bw = int(rng.choice([3, 20, 100]))
+    cov = float(rng.choice([0.0, 0.5, 0.6, 1.0]))
+    spec = int(rng.choice([1, 2, 2]))
+    chars = int(rng.random() < 0.3)
+    goff, gvals = csr_from_lists(groups)
+    rows = O.quick_msa(groups, reads, *params, bw, spec=spec)
+    calls.set_msa_spec(spec)
+    calls.set_option("consensus_chars", chars)
+    try:
+        g, o, err = both(lambda: calls.msa_consensus_flat(goff, gvals, reads, *params, bw, cov, quals=quals, encoding=t.enc),
+                         lambda: O.create_consensus_quality_loop(rows, cov, [[quals[i - 1] for i in g] for g in groups], t.oenc))
+    finally:
+        calls.set_msa_spec(0)
+        calls.set_option("consensus_chars", 0)
+    if not err:
+        assert g[0].to_strings() == list(o[0]) and g[1].to_strings() == list(o[1]), "fused msa+consensus (%s, spec %d, chars %d)" % (t.name, spec, chars)
+
+
 CASES = [case_align, case_align, case_umi, case_consensus, case_msa, case_mask, case_unmask, case_fused, case_fastq, case_profile]
+ENC_CASES = [case_align_enc, case_consensus_enc, case_mask_enc, case_fused_enc]   # run on a residue of their own, see below
 
 if __name__ == "__main__":
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
@@ -435,6 +576,8 @@ if __name__ == "__main__":
         seed = seed0 * 1_000_003 + k
         rng = np.random.default_rng(seed)
         fn = case_umi_large if k % 97 == 96 else (case_align_wide if k % 41 == 40 else CASES[k % len(CASES)])
+        if fn in CASES and len(sys.argv) <= 3 and k % 7 == 6:
+            fn = ENC_CASES[(k // 7) % len(ENC_CASES)]
         try:
             fn(rng)
         except Exception:
