@@ -246,6 +246,26 @@ int sarlacc_dev_fastq_split(const uint8_t* d_text, int64_t nbytes, int64_t max_r
 int sarlacc_dev_fastq_extract(const uint8_t* d_text, uint8_t* d_seq, uint8_t* d_qual, int64_t* d_off,
                               uint8_t* d_names, int64_t* d_name_off, void* stream);
 
+/* Resident read batch -> FASTQ text in device memory: the inverse of sarlacc_dev_fastq_extract (the reference writes
+ * realizeReads' output and the consensus reads with writeXStringSet, vignettes/correction.Rmd:271-278, :352).
+ * Record i of the text is
+ *     '@' name '\n' seq '\n' '+' '\n' qual '\n'        (LF only; name_len + 2 L + 6 bytes)
+ * where seq and qual are the bytes d_off[i] .. d_off[i + 1] of d_seq and d_qual, copied as they are (no quality encoding
+ * is involved), and name the bytes d_name_off[i] .. d_name_off[i + 1] of d_names.  d_names and d_name_off are passed
+ * together or both NULL; without them record i is named READ_<first_index + i>, decimal and unpadded (first_index = 1
+ * numbers a batch from READ_1; it is not used otherwise).  A name that holds '\n' or '\r' is refused, since such a file
+ * cannot be read back: the error is "record K: read name holds a line break" for the lowest such record, K 1-based.
+ * Step 1 fills d_rec_off with the n + 1 offsets of the records in the whole text and reports its size; step 2 writes the
+ * bytes d_rec_off[first] .. d_rec_off[first + count] of the whole text to d_text[0 ..], so a caller that plans ranges
+ * of whole records needs room for one range at a time.  d_text may have any alignment.  n == 0 and count == 0 succeed
+ * without a launch.  Both calls return when the device has finished.
+ * Out of scope: gzip output, multi-line FASTQ, a repeated name on the '+' line. */
+int sarlacc_dev_fastq_format_size(const int64_t* d_off, int64_t n, const uint8_t* d_names, const int64_t* d_name_off,
+                                  int64_t first_index, int64_t* d_rec_off, int64_t* total_bytes, void* stream);
+int sarlacc_dev_fastq_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
+                             const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
+                             int64_t count, uint8_t* d_text, void* stream);
+
 /* SAM alignment records already in device memory -> ranges (sam2ranges, R/sam2ranges.R:8-95).  d_text holds
  * body lines of a SAM file (no header), LF or CRLF, blank lines skipped; first_line is the 1-based file line
  * number of its first line, used in error messages.  The caller reads the header: ref_names / ref_off (n_ref + 1

@@ -66,6 +66,12 @@ def read_fastq(path):
 
 
 def write_fastq(path, reads, append=False):
+    """Reads -> 4-line FASTQ (LF only; READ_<i> where there are no names).  A resident batch (resident.DeviceReads, e.g.
+    realizeReads(..., resident=True)) is formatted on the device and written block by block (DeviceReads.to_fastq,
+    whose byte count is returned); host Reads are not sent through the device."""
+    from .resident import DeviceReads
+    if isinstance(reads, DeviceReads):
+        return reads.to_fastq(path, append=append)
     with open(path, "ab" if append else "wb") as fh:
         for i, (s, q) in enumerate(zip(reads.seq.to_strings(), reads.qual.to_strings())):
             name = reads.names[i] if reads.names else "READ_%d" % (i + 1)

@@ -143,6 +143,85 @@ class DeviceReads:
         return (StringSet(self.seq.to_numpy(np.uint8, self.total), self.off_host.copy()),
                 StringSet(self.qual.to_numpy(np.uint8, self.total), self.off_host.copy()))
 
+    def _name_set(self):
+        """`.names` as a StringSet (None: default names): a StrList hands over its flat bytes and offsets undecoded,
+        a plain list of str is encoded once."""
+        if self.names is None or len(self.names) == 0:   # (an empty list: default names, as in generics.write_fastq)
+            return None
+        from .strset import StrList
+        ss = self.names.ss if isinstance(self.names, StrList) else StringSet.from_strings(list(self.names))
+        if len(ss) != len(self):
+            raise _lib.SarlaccError("%d read names for %d reads" % (len(ss), len(self)))
+        return ss
+
+    def _fastq_plan(self, block_bytes):
+        """The size pass of the device FASTQ writer (sarlacc_dev_fastq_format_size; refuses names with a line break) and
+        the record ranges of the blocks: the largest run of whole records whose text fits in `block_bytes` (None:
+        everything), a single record larger than that in a block of its own size."""
+        n = len(self)
+        ss = self._name_set()
+        names = noff = None
+        if ss is not None:
+            names, noff = DevBuffer.from_numpy(ss.chars), DevBuffer.from_numpy(ss.off)
+        rec_off, total = DevBuffer(8 * (n + 1)), C.c_int64(0)
+        check(_lib.lib().sarlacc_dev_fastq_format_size(self.off.ptr, C.c_int64(n), names.ptr if names else None,
+                                                       noff.ptr if noff else None, C.c_int64(1), rec_off.ptr, C.byref(total), None))
+        # the host knows every length too: it plans the ranges itself
+        if ss is not None:
+            name_len = np.diff(ss.off)
+        else:   # READ_<k>, k = 1 .. n
+            name_len = 6 + np.searchsorted(10 ** np.arange(1, 19, dtype=np.int64), np.arange(1, n + 1, dtype=np.int64), side="right")
+        ro = np.zeros(n + 1, np.int64)
+        np.cumsum(name_len + 2 * np.diff(self.off_host) + 6, out=ro[1:])
+        ranges, first = [], 0
+        while first < n:
+            last = n if block_bytes is None else max(int(np.searchsorted(ro, ro[first] + int(block_bytes), side="right")) - 1, first + 1)
+            ranges.append((first, last))
+            first = last
+        return names, noff, rec_off, ro, ranges
+
+    def _fastq_blocks(self, plan):
+        """Generator over the blocks of a _fastq_plan, formatted on the device (sarlacc_dev_fastq_format): each a uint8
+        view of ONE reused page-locked buffer, valid until the next block is asked for."""
+        names, noff, rec_off, ro, ranges = plan
+        if not ranges:
+            return
+        largest = max(int(ro[b] - ro[a]) for a, b in ranges)
+        d_text, host = DevBuffer(largest), _lib.host_array(largest, np.uint8)
+        for a, b in ranges:
+            nbytes = int(ro[b] - ro[a])
+            check(_lib.lib().sarlacc_dev_fastq_format(self.seq.ptr, self.qual.ptr, self.off.ptr, names.ptr if names else None,
+                                                      noff.ptr if noff else None, C.c_int64(1), rec_off.ptr, C.c_int64(a),
+                                                      C.c_int64(b - a), d_text.ptr, None))
+            check(_lib.lib().sarlacc_dev_download(ptr(host), d_text.ptr, C.c_int64(nbytes)))
+            yield host[:nbytes]
+
+    def fastq_text(self, block_bytes=None):
+        """The batch as 4-line FASTQ text (bytes), formatted on the device: record i is
+        b"@" + name + b"\\n" + seq + b"\\n+\\n" + qual + b"\\n" -- LF only, the bytes generics.write_fastq writes for
+        the same reads.  `.names` gives the names (the StrList from_fastq leaves, or a list of str); None selects READ_1,
+        READ_2, ...  Sequence and quality bytes are copied as they are: `encoding` plays no part.  A name that holds a
+        line break is refused ("record K: read name holds a line break").  `block_bytes` bounds the text the device
+        formats at a time (see to_fastq); the result is the same.  The whole text is held on the host more than once (the
+        download buffer, a copy per block, the joined result) and, with block_bytes=None, once on the device: this is for
+        batches whose text fits comfortably; to_fastq is the bounded route.  Not done here: gzip output, multi-line FASTQ, a
+        repeated name on the '+' line."""
+        return b"".join(blk.tobytes() for blk in self._fastq_blocks(self._fastq_plan(block_bytes)))
+
+    def to_fastq(self, path, append=False, block_bytes=256 << 20):
+        """Writes fastq_text() to `path` (after what is there with append=True) and returns the bytes written.  The
+        text is formatted on the device in blocks of whole records of at most `block_bytes` (a single larger record
+        gets a block of its own size), each downloaded into one page-locked buffer and written with one write(), so
+        neither the host nor the device ever holds more than one block of text -- the bound of stream_fastq.  The file
+        is opened only once the names have passed the check: a refused batch leaves it as it was."""
+        plan = self._fastq_plan(block_bytes)
+        written = 0
+        with open(path, "ab" if append else "wb") as fh:
+            for blk in self._fastq_blocks(plan):
+                fh.write(blk)
+                written += blk.size
+        return written
+
     def _like(self, off_host):
         total = int(off_host[-1])
         return DeviceReads(DevBuffer(total), DevBuffer(total), DevBuffer.from_numpy(off_host), off_host, self.encoding)
