@@ -66,12 +66,9 @@ def lib():
                 "(or __graft_entry__.build()); there is no CPU fallback" % LIB_PATH)
         _preload_shared_hip_runtime()
         _lib = C.CDLL(LIB_PATH)
-        _lib.sarlacc_last_error.restype = C.c_char_p
-        _lib.sarlacc_last_kernel_ms.restype = C.c_double
-        _lib.sarlacc_stage_ms.restype = C.c_double
-        _lib.sarlacc_stage_count.restype = C.c_double
-        _lib.sarlacc_release_umi_workspace.restype = C.c_int64
-        _lib.sarlacc_workspace_report.restype = C.c_int64
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return _lib
 
 
@@ -80,11 +77,97 @@ def check(rc):
         raise SarlaccError(lib().sarlacc_last_error().decode())
 
 
-def ptr(a):
-    """numpy array / None -> void*"""
-    if a is None:
-        return None
-    return a.ctypes.data_as(C.c_void_p)
+class Pointer(C.c_void_p):
+    """The type of every pointer parameter of the C ABI, `void* stream` and `void** p` included.  Takes a numpy array
+    (its data), a torch tensor (its data_ptr()), a resident.DevBuffer (through its _as_parameter_) and what c_void_p
+    takes: None, bytes, a raw integer address, a c_void_p, a byref(...) result, a ctypes buffer."""
+
+    @classmethod
+    def from_param(cls, x):
+        if isinstance(x, np.ndarray):
+            return C.c_void_p(x.ctypes.data)
+        if hasattr(x, "data_ptr"):
+            return C.c_void_p(x.data_ptr())
+        return C.c_void_p.from_param(x)
+
+
+def _prototypes():
+    """name -> (restype, [argtypes]) of every function include/sarlacc_amd.h declares, in its order
+    (tests/test_abi_table.py holds the two together)."""
+    i, i32, i64, u64, f64, s, p = C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_double, C.c_char_p, Pointer
+    reads = [p, p, p, p, i64]                 # seq, seq_off, qual, qual_off, n (umi_group: umi1, off1, umi2, off2, n)
+    enc = [p, p, i]                           # enc_errors, enc_names, enc_n
+    scored = reads + enc + [f64, f64, p, i]   # ... gapopen, gapext, reference, reference_len
+    dev_align = [i64, i32] + enc + [f64, f64, p, i, i, p, p, i, p, p, p, p, p, p]
+    msa_scores = [f64, f64, f64, f64, i]      # match, mismatch, gap_extension, gap_opening, bandwidth
+    fused_tail = msa_scores + [f64, f64] + enc + [p, p, p, i64]
+    clusters = [p, p, p]                      # nclusters, clu_off, clu
+    return {
+        "sarlacc_last_error": (s, []),
+        "sarlacc_version": (i, []),
+        "sarlacc_device_count": (i, []),
+        "sarlacc_set_device": (i, [i]),
+        "sarlacc_release_workspace": (None, []),
+        "sarlacc_release_umi_workspace": (i64, []),
+        "sarlacc_workspace_report": (i64, [p, i64]),
+        "sarlacc_stage_ms": (f64, [s]),
+        "sarlacc_stage_count": (f64, [s]),
+        "sarlacc_last_kernel_ms": (f64, []),
+        "sarlacc_adaptor_align": (i, scored + [p, p, i, p, p, p, p, p]),
+        "sarlacc_adaptor_align_score_only": (i, scored + [p]),
+        "sarlacc_barcode_align": (i, scored + [p]),
+        "sarlacc_general_align": (i, scored + [i, p, p, p, p, p, i64]),
+        "sarlacc_mask_bad_bases": (i, reads + enc + [f64, p]),
+        "sarlacc_dev_align": (i, [p, p, p] + dev_align),
+        "sarlacc_dev_pack_reads": (i, [p, i64, p, p, p]),
+        "sarlacc_dev_align_packed": (i, [p, p, p, p] + dev_align),
+        "sarlacc_dev_malloc": (i, [p, i64]),
+        "sarlacc_dev_free": (i, [p]),
+        "sarlacc_dev_pool_release": (i, []),
+        "sarlacc_dev_upload": (i, [p, p, i64]),
+        "sarlacc_dev_download": (i, [p, p, i64]),
+        "sarlacc_host_alloc": (i, [p, i64]),
+        "sarlacc_host_free": (i, [p]),
+        "sarlacc_host_release": (i, []),
+        "sarlacc_dev_windows": (i, [p, p, p, i64, p, i, p, p, p]),
+        "sarlacc_dev_choose_strand": (i, [p, p, p, p, i64, i, i, p, p, p, p]),
+        "sarlacc_dev_subseq": (i, [p, p, p, p, p, p, p, i64, p, i64, p, p]),
+        "sarlacc_dev_realize": (i, [p, p, p, p, p, p, i64, p, p, p, p]),
+        "sarlacc_dev_scramble": (i, [p, p, p, i64, u64, p, p, p]),
+        "sarlacc_unmask_alignment": (i, [p, p, i64, p, p, i64, p]),
+        "sarlacc_find_homopolymers": (i, [p, p, i64, p, p, p, p, i64, p]),
+        "sarlacc_match_homopolymers": (i, [p, p, i64, p, p, i64, p, p, p, i64, p]),
+        "sarlacc_find_errors": (i, [p, p, i64, p, p, i64, p, p, p, p, p, p, p, i64, p, p, i64, p]),
+        "sarlacc_dev_fastq_index": (i, [p, i64, p, p, p, p]),
+        "sarlacc_dev_fastq_split": (i, [p, i64, i64, p, p, p]),
+        "sarlacc_dev_fastq_extract": (i, [p, p, p, p, p, p, p]),
+        "sarlacc_dev_fastq_format_size": (i, [p, i64, p, p, i64, p, p, p]),
+        "sarlacc_dev_fastq_format": (i, [p, p, p, p, p, i64, p, i64, i64, p, p]),
+        "sarlacc_dev_sam_index": (i, [p, i64, i64, p, p, i64, p, p, p, i64, i, i64, p, p, p, p]),
+        "sarlacc_dev_sam_extract": (i, [p, p, p, p, p, p, p, p, p, p]),
+        "sarlacc_compute_lev_masked": (i, [p, p, i64, p]),
+        "sarlacc_fast_levdist_test": (i, [p, p, i64, i, p, p, i64, p]),
+        "sarlacc_cluster_umis_test": (i, [p, p, i64] + clusters),
+        "sarlacc_umi_group": (i, reads + [i, i, p, p, i64] + clusters),
+        "sarlacc_umi_pairs_shard": (i, [p, p, i64, i, i, i, p, i64, p]),
+        "sarlacc_umi_group_from_pairs": (i, [p, p, i64, i, p, i64] + clusters),
+        "sarlacc_dev_umi_pairs_shard": (i, [p, p, i64, i, i, i, p]),
+        "sarlacc_dev_umi_pairs_fetch": (i, [p, i64]),
+        "sarlacc_dev_umi_group_from_pairs": (i, [p, p, i64, i, p, i64] + clusters),
+        "sarlacc_set_msa_spec": (i, [i]),
+        "sarlacc_set_option": (i, [s, i]),
+        "sarlacc_quick_msa": (i, [p, p, i64, p, p, i64] + msa_scores + [p, p, p, i64]),
+        "sarlacc_create_consensus_basic_loop": (i, [p, p, p, i64, f64, f64, p, p, p, p]),
+        "sarlacc_create_consensus_quality_loop": (i, [p, p, p, i64, p, p, p, f64] + enc + [p, p, p, p]),
+        "sarlacc_msa_consensus": (i, [p, p, i64, p, p, p, p, i64] + fused_tail),
+        "sarlacc_dev_msa_consensus": (i, [p, p, i64, p, p, p, i64] + fused_tail),
+    }
+
+
+PROTOTYPES = _prototypes()
+
+
+ptr = Pointer.from_param   # (no call in the package needs it any more; tools/perf_sam.py names it)
 
 
 class _HostBlock:
@@ -92,14 +175,14 @@ class _HostBlock:
 
     def __init__(self, nbytes):
         p = C.c_void_p()
-        check(lib().sarlacc_host_alloc(C.byref(p), C.c_int64(nbytes)))
+        check(lib().sarlacc_host_alloc(C.byref(p), nbytes))
         self.address = p.value
         self.__array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (self.address, False), "version": 3}
 
     def __del__(self):
         try:
             if self.address:
-                lib().sarlacc_host_free(C.c_void_p(self.address))
+                lib().sarlacc_host_free(self.address)
                 self.address = 0
         except Exception:
             pass
@@ -139,7 +222,7 @@ def release_umi_workspace():
 def workspace_report(top=12):
     """sarlacc_workspace_report: (total bytes, [(name, bytes), ...] of the `top` largest cached device buffers)."""
     buf = C.create_string_buffer(1 << 16)
-    total = int(lib().sarlacc_workspace_report(buf, C.c_int64(len(buf))))
+    total = int(lib().sarlacc_workspace_report(buf, len(buf)))
     rows = [ln.rsplit(" ", 1) for ln in buf.value.decode().splitlines() if ln]
     return total, [(n, int(b)) for n, b in rows[:top]]
 

@@ -5,11 +5,12 @@ ctypes shim over the C ABI in include/sarlacc_amd.h -- the exact counterpart of 
 R glue shown in INTEGRATION.md.  All arithmetic happens in the HIP library.
 """
 import ctypes as C
+import re
 
 import numpy as np
 
 from . import _lib
-from ._lib import SarlaccError, check, ptr
+from ._lib import SarlaccError, check
 from .encoding import as_encoding
 from .strset import StringSet, csr_from_lists, lists_from_csr
 
@@ -47,6 +48,23 @@ def _seq_qual(seq, qual):
     return s, q
 
 
+def _csr_args(off, vals):
+    """CSR lists as the library takes them: int64 offsets, int32 values (one entry at least, for a valid pointer)."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    vals = np.ascontiguousarray(vals, dtype=np.int32)
+    return off, vals if vals.size else np.zeros(1, np.int32)
+
+
+def _grow(cap, need):
+    """Capacities for a call that reports its full result size in `need` (a c_int64 passed by reference) and fills its
+    arrays only when they are large enough: `cap`, then the reported size as long as it exceeds the capacity tried."""
+    while True:
+        yield cap
+        if need.value <= cap:
+            return
+        cap = need.value
+
+
 # ---------------------------------------------------------------------------
 def adaptor_align(readseq, readqual, encoding, gapopen, gapext, adaptor, sec_starts, sec_ends):
     """.Call adaptor_align (src/adaptor_align.cpp:11-77).
@@ -69,11 +87,8 @@ def adaptor_align(readseq, readqual, encoding, gapopen, gapext, adaptor, sec_sta
     if ns == 0:
         ss = np.zeros(1, np.int32)
         se = np.zeros(1, np.int32)
-    check(_lib.lib().sarlacc_adaptor_align(
-        ptr(s.chars), ptr(s.off), ptr(q.chars), ptr(q.off), C.c_int64(n),
-        ptr(enc.errors), enc.names, len(enc), C.c_double(go), C.c_double(ge),
-        ad, len(ad), ptr(ss), ptr(se), ns,
-        ptr(scores), ptr(starts), ptr(ends), ptr(so), ptr(sw)))
+    check(_lib.lib().sarlacc_adaptor_align(s.chars, s.off, q.chars, q.off, n, enc.errors, enc.names, len(enc), go, ge,
+                                           ad, len(ad), ss, se, ns, scores, starts, ends, so, sw))
     sol = [so.reshape(-1)[k * n:(k + 1) * n].copy() for k in range(ns)]
     swl = [sw.reshape(-1)[k * n:(k + 1) * n].copy() for k in range(ns)]
     return [scores, starts, ends, sol, swl]
@@ -87,9 +102,7 @@ def _scores_call(fn, seq, qual, encoding, gapopen, gapext, ref, what):
     enc = as_encoding(encoding)
     n = len(s)
     scores = np.zeros(n, np.float64)
-    check(fn(ptr(s.chars), ptr(s.off), ptr(q.chars), ptr(q.off), C.c_int64(n),
-             ptr(enc.errors), enc.names, len(enc), C.c_double(go), C.c_double(ge),
-             rf, len(rf), ptr(scores)))
+    check(fn(s.chars, s.off, q.chars, q.off, n, enc.errors, enc.names, len(enc), go, ge, rf, len(rf), scores))
     return scores
 
 
@@ -121,10 +134,8 @@ def general_align(inputseq, inputqual, encoding, gapopen, gapext, reference, edi
     ar = np.zeros(1 if only else cap, np.uint8)
     aq = np.zeros(1 if only else cap, np.uint8)
     ao = np.zeros(n + 1, np.int64)
-    check(_lib.lib().sarlacc_general_align(
-        ptr(s.chars), ptr(s.off), ptr(q.chars), ptr(q.off), C.c_int64(n),
-        ptr(enc.errors), enc.names, len(enc), C.c_double(go), C.c_double(ge),
-        rf, len(rf), int(only), ptr(scores), ptr(edits), ptr(ar), ptr(aq), ptr(ao), C.c_int64(cap)))
+    check(_lib.lib().sarlacc_general_align(s.chars, s.off, q.chars, q.off, n, enc.errors, enc.names, len(enc), go, ge,
+                                           rf, len(rf), int(only), scores, edits, ar, aq, ao, cap))
     if only:
         return [scores, edits, [], []]
     return [scores, edits, StringSet(ar, ao).to_strings(), StringSet(aq, ao).to_strings()]
@@ -142,25 +153,31 @@ def _aln_list(alignments):
     return StringSet.from_strings(rows), grp
 
 
-def _consensus(alignments, min_cov, pseudo, qualities, encoding, want_lerr):
-    s, grp = _aln_list(alignments)
-    ng = len(alignments)
-    cap = max(s.total, 1)
+def _consensus_call(rows, grp_rows, min_cov, pseudo, quals, qgrp_rows, enc, want_lerr):
+    """sarlacc_create_consensus_{basic,quality}_loop on (rows StringSet, grp_rows); `quals` None selects the basic vote.
+    Returns (cons, phred, cons_off, log errors or None)."""
+    ng = len(grp_rows) - 1
+    cap = max(rows.total, 1)
     cons = np.zeros(cap, np.uint8)
     phred = np.zeros(cap, np.uint8)
     coff = np.zeros(ng + 1, np.int64)
     lerr = np.zeros(cap, np.float64) if want_lerr else None
-    if qualities is None:
-        check(_lib.lib().sarlacc_create_consensus_basic_loop(
-            ptr(s.chars), ptr(s.off), ptr(grp), C.c_int64(ng), C.c_double(min_cov), C.c_double(pseudo),
-            ptr(cons), ptr(phred), ptr(coff), ptr(lerr)))
+    if quals is None:
+        check(_lib.lib().sarlacc_create_consensus_basic_loop(rows.chars, rows.off, grp_rows, ng, min_cov, pseudo,
+                                                             cons, phred, coff, lerr))
     else:
+        check(_lib.lib().sarlacc_create_consensus_quality_loop(rows.chars, rows.off, grp_rows, ng, quals.chars, quals.off, qgrp_rows,
+                                                               min_cov, enc.errors, enc.names, len(enc), cons, phred, coff, lerr))
+    return cons, phred, coff, lerr
+
+
+def _consensus(alignments, min_cov, pseudo, qualities, encoding, want_lerr):
+    s, grp = _aln_list(alignments)
+    q = qgrp = enc = None
+    if qualities is not None:
         q, qgrp = _aln_list(qualities)
         enc = as_encoding(encoding)
-        check(_lib.lib().sarlacc_create_consensus_quality_loop(
-            ptr(s.chars), ptr(s.off), ptr(grp), C.c_int64(ng), ptr(q.chars), ptr(q.off), ptr(qgrp),
-            C.c_double(min_cov), ptr(enc.errors), enc.names, len(enc),
-            ptr(cons), ptr(phred), ptr(coff), ptr(lerr)))
+    cons, phred, coff, lerr = _consensus_call(s, grp, min_cov, pseudo, q, qgrp, enc, want_lerr)
     cs = StringSet(cons, coff).to_strings()
     ps = StringSet(phred, coff).to_strings()
     return cs, ps, (lerr, coff)
@@ -205,9 +222,7 @@ def mask_bad_bases(sequences, qualities, encoding, threshold):
     enc = as_encoding(encoding)
     thr = _numeric(threshold, "quality threshold")
     out = np.zeros(max(s.total, 1), np.uint8)
-    check(_lib.lib().sarlacc_mask_bad_bases(
-        ptr(s.chars), ptr(s.off), ptr(q.chars), ptr(q.off), C.c_int64(len(s)),
-        ptr(enc.errors), enc.names, len(enc), C.c_double(thr), ptr(out)))
+    check(_lib.lib().sarlacc_mask_bad_bases(s.chars, s.off, q.chars, q.off, len(s), enc.errors, enc.names, len(enc), thr, out))
     return StringSet(out, s.off.copy()).to_strings()
 
 
@@ -217,8 +232,7 @@ def unmask_alignment(alignments, originals):
     a = StringSet.from_strings(alignments)
     o = StringSet.from_strings(originals)
     out = np.zeros(max(a.total, 1), np.uint8)
-    check(_lib.lib().sarlacc_unmask_alignment(ptr(a.chars), ptr(a.off), C.c_int64(len(a)), ptr(o.chars), ptr(o.off),
-                                              C.c_int64(len(o)), ptr(out)))
+    check(_lib.lib().sarlacc_unmask_alignment(a.chars, a.off, len(a), o.chars, o.off, len(o), out))
     return StringSet(out, a.off.copy()).to_strings()
 
 
@@ -227,7 +241,7 @@ def compute_lev_masked(sequences):
     s = StringSet.from_strings(sequences)
     n = len(s)
     out = np.zeros(max(n * (n - 1) // 2, 1), np.float64)
-    check(_lib.lib().sarlacc_compute_lev_masked(ptr(s.chars), ptr(s.off), C.c_int64(n), ptr(out)))
+    check(_lib.lib().sarlacc_compute_lev_masked(s.chars, s.off, n, out))
     return out[: n * (n - 1) // 2]
 
 
@@ -241,14 +255,9 @@ def fast_levdist_test(sequences, limit, sorted=True):
     n = len(s)
     off = np.zeros(n + 1, np.int64)
     need = C.c_int64(0)
-    cap = max(32 * n, 1024)
-    while True:
+    for cap in _grow(max(32 * n, 1024), need):
         nbr = np.zeros(cap, np.int32)
-        check(_lib.lib().sarlacc_fast_levdist_test(ptr(s.chars), ptr(s.off), C.c_int64(n), lim,
-                                                   ptr(off), ptr(nbr), C.c_int64(cap), C.byref(need)))
-        if need.value <= cap:
-            break
-        cap = need.value
+        check(_lib.lib().sarlacc_fast_levdist_test(s.chars, s.off, n, lim, off, nbr, cap, C.byref(need)))
     return lists_from_csr(off, nbr)
 
 
@@ -260,8 +269,20 @@ def cluster_umis_test(links):
     ncl = C.c_int64(0)
     co = np.zeros(n + 2, np.int64)
     cl = np.zeros(max(n, 1), np.int32)
-    check(_lib.lib().sarlacc_cluster_umis_test(ptr(off), ptr(vals), C.c_int64(n), C.byref(ncl), ptr(co), ptr(cl)))
+    check(_lib.lib().sarlacc_cluster_umis_test(off, vals, n, C.byref(ncl), co, cl))
     return lists_from_csr(co, cl, ncl.value)
+
+
+def _umi_group(s1, t1, s2, t2, goff, gvals):
+    """sarlacc_umi_group on checked arguments: (number of clusters, cluster offsets, members)."""
+    total = int(goff[-1])
+    ncl = C.c_int64(0)
+    co = np.zeros(total + 2, np.int64)
+    cl = np.zeros(max(total, 1), np.int32)
+    u2, o2 = (s2.chars, s2.off) if s2 is not None else (None, None)
+    check(_lib.lib().sarlacc_umi_group(s1.chars, s1.off, u2, o2, len(s1), t1, t2, goff, gvals, goff.size - 1,
+                                       C.byref(ncl), co, cl))
+    return ncl.value, co, cl
 
 
 def umi_group(umi1, thresh1, umi2, thresh2, pregroup):
@@ -275,16 +296,8 @@ def umi_group(umi1, thresh1, umi2, thresh2, pregroup):
         if len(s2) != len(s1):
             raise SarlaccError("'umi1' and 'umi2' should have the same length")
     t2 = _integer(thresh2, "threshold 2")
-    goff, gvals = csr_from_lists(pregroup)
-    total = int(goff[-1])
-    ncl = C.c_int64(0)
-    co = np.zeros(total + 2, np.int64)
-    cl = np.zeros(max(total, 1), np.int32)
-    check(_lib.lib().sarlacc_umi_group(
-        ptr(s1.chars), ptr(s1.off), ptr(s2.chars) if s2 is not None else None,
-        ptr(s2.off) if s2 is not None else None, C.c_int64(len(s1)), t1, t2,
-        ptr(goff), ptr(gvals), C.c_int64(len(pregroup)), C.byref(ncl), ptr(co), ptr(cl)))
-    return lists_from_csr(co, cl, ncl.value)
+    ncl, co, cl = _umi_group(s1, t1, s2, t2, *csr_from_lists(pregroup))
+    return lists_from_csr(co, cl, ncl)
 
 
 def umi_group_flat(umi1, thresh1, umi2, thresh2, pregroup_off, pregroup):
@@ -294,19 +307,9 @@ def umi_group_flat(umi1, thresh1, umi2, thresh2, pregroup_off, pregroup):
     s2 = StringSet.from_strings(umi2) if umi2 is not None else None
     if s2 is not None and len(s2) != len(s1):
         raise SarlaccError("'umi1' and 'umi2' should have the same length")
-    goff = np.ascontiguousarray(pregroup_off, dtype=np.int64)
-    gvals = np.ascontiguousarray(pregroup, dtype=np.int32)
-    if gvals.size == 0:
-        gvals = np.zeros(1, np.int32)
-    total = int(goff[-1])
-    ncl = C.c_int64(0)
-    co = np.zeros(total + 2, np.int64)
-    cl = np.zeros(max(total, 1), np.int32)
-    check(_lib.lib().sarlacc_umi_group(
-        ptr(s1.chars), ptr(s1.off), ptr(s2.chars) if s2 is not None else None,
-        ptr(s2.off) if s2 is not None else None, C.c_int64(len(s1)), _integer(thresh1, "threshold 1"),
-        _integer(thresh2, "threshold 2"), ptr(goff), ptr(gvals), C.c_int64(goff.size - 1), C.byref(ncl), ptr(co), ptr(cl)))
-    return co[:ncl.value + 1], cl[:int(co[ncl.value])]
+    goff, gvals = _csr_args(pregroup_off, pregroup)
+    ncl, co, cl = _umi_group(s1, _integer(thresh1, "threshold 1"), s2, _integer(thresh2, "threshold 2"), goff, gvals)
+    return co[:ncl + 1], cl[:int(co[ncl])]
 
 
 def csr_select(off, vals, keep):
@@ -327,68 +330,16 @@ def set_option(name, value):
     check(_lib.lib().sarlacc_set_option(str(name).encode(), int(value)))
 
 
-def quick_msa(groupings, sequences, match, mismatch, gapExtension, gapOpening, bandwidth):
-    """.Call quick_msa (src/quick_msa.cpp:15-80), same argument order (the R caller passes
-    -gapOpening as gapExtension and -gapExtension as gapOpening, R/multiReadAlign.R:47).
-    Returns one list of equal-width gapped strings per group."""
-    s = StringSet.from_strings(sequences)
-    ma = _numeric(match, "match score")
-    mm = _numeric(mismatch, "mismatch score")
-    gx = _numeric(gapExtension, "gap extension score")
-    go = _numeric(gapOpening, "gap opening score")
-    bw = _integer(bandwidth, "bandwidth")
-    goff, gvals = csr_from_lists(groupings)
-    ng = len(groupings)
-    width = np.zeros(max(ng, 1), np.int32)
-    ooff = np.zeros(ng + 1, np.int64)
-    args = (ptr(goff), ptr(gvals), C.c_int64(ng), ptr(s.chars), ptr(s.off), C.c_int64(len(s)),
-            C.c_double(ma), C.c_double(mm), C.c_double(gx), C.c_double(go), bw, ptr(width), ptr(ooff))
-    # generous first guess: every read padded to twice the longest member
-    sizes = np.diff(goff)
-    cap = int(s.total * 2 + 64) if ng else 1
-    for attempt in range(2):
-        out = np.zeros(max(cap, 1), np.uint8)
-        try:
-            check(_lib.lib().sarlacc_quick_msa(*args, ptr(out), C.c_int64(cap)))
-            break
-        except SarlaccError as e:
-            if attempt == 0 and "buffer too small" in str(e):
-                cap = int(ooff[ng])
-                continue
-            raise
-    res = []
-    for g in range(ng):
-        w, m = int(width[g]), int(sizes[g])
-        blk = out[ooff[g]:ooff[g + 1]].tobytes()
-        res.append([blk[r * w:(r + 1) * w].decode() for r in range(m)])
-    return res
-
-
-# ---------------------------------------------------------------------------
-# Flat variants (numpy in, numpy out) for large batches: same C ABI calls without
-# materialising Python string lists.
-
-def quick_msa_flat(grp_off, grp, seqs, match, mismatch, gapExtension, gapOpening, bandwidth):
-    """quick_msa on CSR groups.  Returns (rows StringSet, grp_rows int64[ngroups+1], width int32[ngroups]):
-    rows are the gapped strings of all groups in order, grp_rows the row range of each group."""
-    s = StringSet.from_strings(seqs)
-    goff = np.ascontiguousarray(grp_off, dtype=np.int64)
-    gvals = np.ascontiguousarray(grp, dtype=np.int32)
-    if gvals.size == 0:
-        gvals = np.zeros(1, np.int32)
+def _quick_msa(goff, gvals, s, scores, cap):
+    """sarlacc_quick_msa on CSR groups with `cap` bytes for the rows at first; the library reports the exact size
+    (out_off) when that was too small.  Returns what quick_msa_flat returns."""
     ng = goff.size - 1
     width = np.zeros(max(ng, 1), np.int32)
     ooff = np.zeros(ng + 1, np.int64)
-    args = (ptr(goff), ptr(gvals), C.c_int64(ng), ptr(s.chars), ptr(s.off), C.c_int64(len(s)),
-            C.c_double(match), C.c_double(mismatch), C.c_double(gapExtension), C.c_double(gapOpening), int(bandwidth),
-            ptr(width), ptr(ooff))
-    # one pass in the common case: rows are rarely more than 1.5x the reads they hold; the
-    # library reports the exact size (out_off) when the guess was too small
-    cap = int(1.5 * s.widths()[gvals[:int(goff[-1])].astype(np.int64) - 1].sum()) + 1024 if goff[-1] else 1
     for attempt in range(2):
         out = np.zeros(max(cap, 1), np.uint8)
         try:
-            check(_lib.lib().sarlacc_quick_msa(*args, ptr(out), C.c_int64(cap)))
+            check(_lib.lib().sarlacc_quick_msa(goff, gvals, ng, s.chars, s.off, len(s), *scores, width, ooff, out, cap))
             break
         except SarlaccError as e:
             if attempt == 0 and "buffer too small" in str(e):
@@ -404,63 +355,65 @@ def quick_msa_flat(grp_off, grp, seqs, match, mismatch, gapExtension, gapOpening
     return StringSet(out, row_off), grp_rows, width[:ng]
 
 
+def quick_msa(groupings, sequences, match, mismatch, gapExtension, gapOpening, bandwidth):
+    """.Call quick_msa (src/quick_msa.cpp:15-80), same argument order (the R caller passes
+    -gapOpening as gapExtension and -gapExtension as gapOpening, R/multiReadAlign.R:47).
+    Returns one list of equal-width gapped strings per group."""
+    s = StringSet.from_strings(sequences)
+    ma = _numeric(match, "match score")
+    mm = _numeric(mismatch, "mismatch score")
+    gx = _numeric(gapExtension, "gap extension score")
+    go = _numeric(gapOpening, "gap opening score")
+    bw = _integer(bandwidth, "bandwidth")
+    goff, gvals = csr_from_lists(groupings)
+    # generous first guess: every read padded to twice the longest member
+    rows, grp_rows, _ = _quick_msa(goff, gvals, s, (ma, mm, gx, go, bw), int(s.total * 2 + 64) if len(groupings) else 1)
+    rows = rows.to_strings()
+    return [rows[a:b] for a, b in zip(grp_rows[:-1], grp_rows[1:])]
+
+
+# ---------------------------------------------------------------------------
+# Flat variants (numpy in, numpy out) for large batches: same C ABI calls without
+# materialising Python string lists.
+
+def quick_msa_flat(grp_off, grp, seqs, match, mismatch, gapExtension, gapOpening, bandwidth):
+    """quick_msa on CSR groups.  Returns (rows StringSet, grp_rows int64[ngroups+1], width int32[ngroups]):
+    rows are the gapped strings of all groups in order, grp_rows the row range of each group."""
+    s = StringSet.from_strings(seqs)
+    goff, gvals = _csr_args(grp_off, grp)
+    # one pass in the common case: rows are rarely more than 1.5x the reads they hold
+    cap = int(1.5 * s.widths()[gvals[:int(goff[-1])].astype(np.int64) - 1].sum()) + 1024 if goff[-1] else 1
+    return _quick_msa(goff, gvals, s, (match, mismatch, gapExtension, gapOpening, int(bandwidth)), cap)
+
+
 def create_consensus_flat(rows, grp_rows, min_cov, pseudo_count=1.0, quals=None, qgrp_rows=None, encoding=None):
     """Consensus over alignments given as (rows StringSet, grp_rows).  Returns (consensus StringSet,
     phred StringSet).  With `quals` (ungapped quality strings per row) the quality-weighted vote runs."""
-    ng = len(grp_rows) - 1
     grp_rows = np.ascontiguousarray(grp_rows, dtype=np.int64)
-    cap = max(rows.total, 1)
-    cons = np.zeros(cap, np.uint8)
-    phred = np.zeros(cap, np.uint8)
-    coff = np.zeros(ng + 1, np.int64)
-    if quals is None:
-        check(_lib.lib().sarlacc_create_consensus_basic_loop(
-            ptr(rows.chars), ptr(rows.off), ptr(grp_rows), C.c_int64(ng), C.c_double(min_cov), C.c_double(pseudo_count),
-            ptr(cons), ptr(phred), ptr(coff), None))
-    else:
+    q = qg = enc = None
+    if quals is not None:
         enc = as_encoding(encoding)
         q = StringSet.from_strings(quals)
         qg = grp_rows if qgrp_rows is None else np.ascontiguousarray(qgrp_rows, dtype=np.int64)
-        check(_lib.lib().sarlacc_create_consensus_quality_loop(
-            ptr(rows.chars), ptr(rows.off), ptr(grp_rows), C.c_int64(ng), ptr(q.chars), ptr(q.off), ptr(qg),
-            C.c_double(min_cov), ptr(enc.errors), enc.names, len(enc), ptr(cons), ptr(phred), ptr(coff), None))
+    cons, phred, coff, _ = _consensus_call(rows, grp_rows, min_cov, pseudo_count, q, qg, enc, False)
     return StringSet(cons, coff.copy()), StringSet(phred, coff.copy())
 
 
-def msa_consensus_flat(grp_off, grp, seqs, match, mismatch, gapExtension, gapOpening, bandwidth, min_cov,
-                       pseudo_count=1.0, quals=None, encoding=None):
-    """quick_msa_flat followed by create_consensus_flat in one native call (sarlacc_msa_consensus):
-    the gapped rows stay in HBM and `quals` are the quality strings of ALL reads, in read order.
-    Returns (consensus StringSet, phred StringSet), one entry per group."""
-    import re
-    s = StringSet.from_strings(seqs)
-    goff = np.ascontiguousarray(grp_off, dtype=np.int64)
-    gvals = np.ascontiguousarray(grp, dtype=np.int32)
-    if gvals.size == 0:
-        gvals = np.zeros(1, np.int32)
+def _fused_consensus(fn, goff, gvals, reads, widths, scores, enc, alloc):
+    """sarlacc_msa_consensus / sarlacc_dev_msa_consensus (`fn`; `reads` are its arguments between the group lists and the
+    scores, `widths` the read lengths): results of a first-guess capacity (1.5 x the longest member per group + 1024) from
+    `alloc`, and once more of the exact size the library reports when that was too small."""
     ng = goff.size - 1
-    q = enc = None
-    if quals is not None:
-        q = StringSet.from_strings(quals)
-        if len(q) != len(s):
-            raise SarlaccError("sequence and quality vectors should have the same length")
-        enc = as_encoding(encoding)
     coff = np.zeros(ng + 1, np.int64)
-    w = s.widths()
     sizes = np.diff(goff)
-    longest = np.maximum.reduceat(w[gvals[:int(goff[-1])].astype(np.int64) - 1], goff[:-1][sizes > 0]) if goff[-1] else np.zeros(0)
+    longest = np.maximum.reduceat(widths[gvals[:int(goff[-1])].astype(np.int64) - 1], goff[:-1][sizes > 0]) if goff[-1] else np.zeros(0)
     cap = int(1.5 * longest.sum()) + 1024
+    enc_args = (enc.errors, enc.names, len(enc)) if enc is not None else (None, None, 0)
     for attempt in range(2):
-        cons = np.zeros(cap, np.uint8)
-        phred = np.zeros(cap, np.uint8)
+        cons = alloc(cap, np.uint8)
+        phred = alloc(cap, np.uint8)
         try:
-            check(_lib.lib().sarlacc_msa_consensus(
-                ptr(goff), ptr(gvals), C.c_int64(ng), ptr(s.chars), ptr(s.off),
-                ptr(q.chars) if q is not None else None, ptr(q.off) if q is not None else None, C.c_int64(len(s)),
-                C.c_double(match), C.c_double(mismatch), C.c_double(gapExtension), C.c_double(gapOpening), int(bandwidth),
-                C.c_double(min_cov), C.c_double(pseudo_count), ptr(enc.errors) if enc is not None else None,
-                enc.names if enc is not None else None, len(enc) if enc is not None else 0,
-                ptr(cons), ptr(phred), ptr(coff), C.c_int64(cap)))
+            check(fn(goff, gvals, ng, *reads, *scores, *enc_args, cons, phred, coff, cap))
             break
         except SarlaccError as e:
             m = re.search(r"buffer too small \((\d+) needed\)", str(e))
@@ -471,20 +424,35 @@ def msa_consensus_flat(grp_off, grp, seqs, match, mismatch, gapExtension, gapOpe
     return StringSet(cons, coff.copy()), StringSet(phred, coff.copy())
 
 
+def msa_consensus_flat(grp_off, grp, seqs, match, mismatch, gapExtension, gapOpening, bandwidth, min_cov,
+                       pseudo_count=1.0, quals=None, encoding=None):
+    """quick_msa_flat followed by create_consensus_flat in one native call (sarlacc_msa_consensus):
+    the gapped rows stay in HBM and `quals` are the quality strings of ALL reads, in read order.
+    Returns (consensus StringSet, phred StringSet), one entry per group."""
+    s = StringSet.from_strings(seqs)
+    goff, gvals = _csr_args(grp_off, grp)
+    q = enc = None
+    if quals is not None:
+        q = StringSet.from_strings(quals)
+        if len(q) != len(s):
+            raise SarlaccError("sequence and quality vectors should have the same length")
+        enc = as_encoding(encoding)
+    reads = (s.chars, s.off, q.chars if q is not None else None, q.off if q is not None else None, len(s))
+    return _fused_consensus(_lib.lib().sarlacc_msa_consensus, goff, gvals, reads, s.widths(),
+                            (match, mismatch, gapExtension, gapOpening, int(bandwidth), min_cov, pseudo_count), enc, np.zeros)
+
+
 def umi_pairs_shard(umi, limit, shard_index, shard_count):
     """sarlacc_umi_pairs_shard: neighbour pairs (rank_i << 32 | rank_j) found in this shard's row
     tiles of the all-pairs matrix of one pre-group (ranks = positions in the trie order)."""
     s = StringSet.from_strings(umi)
     lim = _integer(limit, "limit")
     need = C.c_int64(0)
-    cap = max(16 * len(s) // max(shard_count, 1), 1024)
-    while True:
+    for cap in _grow(max(16 * len(s) // max(int(shard_count), 1), 1024), need):
         pairs = np.zeros(cap, np.uint64)
-        check(_lib.lib().sarlacc_umi_pairs_shard(ptr(s.chars), ptr(s.off), C.c_int64(len(s)), lim, int(shard_index),
-                                                 int(shard_count), ptr(pairs), C.c_int64(cap), C.byref(need)))
-        if need.value <= cap:
-            return pairs[:need.value].copy()
-        cap = need.value
+        check(_lib.lib().sarlacc_umi_pairs_shard(s.chars, s.off, len(s), lim, int(shard_index), int(shard_count), pairs, cap,
+                                                 C.byref(need)))
+    return pairs[:need.value].copy()
 
 
 def umi_group_from_pairs(umi, limit, pairs, flat=False):
@@ -498,8 +466,7 @@ def umi_group_from_pairs(umi, limit, pairs, flat=False):
     co = np.zeros(n + 2, np.int64)
     cl = np.zeros(max(n, 1), np.int32)
     pp = pairs if pairs.size else np.zeros(1, np.uint64)
-    check(_lib.lib().sarlacc_umi_group_from_pairs(ptr(s.chars), ptr(s.off), C.c_int64(n), lim, ptr(pp), C.c_int64(pairs.size),
-                                                  C.byref(ncl), ptr(co), ptr(cl)))
+    check(_lib.lib().sarlacc_umi_group_from_pairs(s.chars, s.off, n, lim, pp, pairs.size, C.byref(ncl), co, cl))
     if flat:
         return co[:ncl.value + 1], cl[:int(co[ncl.value])]
     return lists_from_csr(co, cl, ncl.value)
@@ -510,7 +477,7 @@ def dev_umi_pairs_shard(umi, limit, shard_index, shard_count):
     their number.  dev_umi_pairs_fetch must be the next library call."""
     s = StringSet.from_strings(umi)
     need = C.c_int64(0)
-    check(_lib.lib().sarlacc_dev_umi_pairs_shard(ptr(s.chars), ptr(s.off), C.c_int64(len(s)), _integer(limit, "limit"), int(shard_index),
+    check(_lib.lib().sarlacc_dev_umi_pairs_shard(s.chars, s.off, len(s), _integer(limit, "limit"), int(shard_index),
                                                  int(shard_count), C.byref(need)))
     return int(need.value)
 
@@ -518,8 +485,7 @@ def dev_umi_pairs_shard(umi, limit, shard_index, shard_count):
 def dev_umi_pairs_fetch(d_pairs, cap):
     """sarlacc_dev_umi_pairs_fetch: copies the pairs of the shard search just run into device memory (a torch tensor of
     8-byte elements or a raw address) holding at least `cap` entries."""
-    addr = d_pairs.data_ptr() if hasattr(d_pairs, "data_ptr") else int(d_pairs)
-    check(_lib.lib().sarlacc_dev_umi_pairs_fetch(C.c_void_p(addr), C.c_int64(int(cap))))
+    check(_lib.lib().sarlacc_dev_umi_pairs_fetch(d_pairs, int(cap)))
 
 
 def dev_umi_group_from_pairs(umi, limit, d_pairs, npairs, flat=False):
@@ -529,9 +495,8 @@ def dev_umi_group_from_pairs(umi, limit, d_pairs, npairs, flat=False):
     ncl = C.c_int64(0)
     co = np.zeros(n + 2, np.int64)
     cl = np.zeros(max(n, 1), np.int32)
-    addr = d_pairs.data_ptr() if hasattr(d_pairs, "data_ptr") else int(d_pairs or 0)
-    check(_lib.lib().sarlacc_dev_umi_group_from_pairs(ptr(s.chars), ptr(s.off), C.c_int64(n), _integer(limit, "limit"), C.c_void_p(addr),
-                                                      C.c_int64(int(npairs)), C.byref(ncl), ptr(co), ptr(cl)))
+    check(_lib.lib().sarlacc_dev_umi_group_from_pairs(s.chars, s.off, n, _integer(limit, "limit"), d_pairs, int(npairs),
+                                                      C.byref(ncl), co, cl))
     if flat:
         return co[:ncl.value + 1], cl[:int(co[ncl.value])]
     return lists_from_csr(co, cl, ncl.value)
@@ -545,15 +510,10 @@ def find_homopolymers(sequences):
     s = StringSet.from_strings(sequences)
     n = len(s)
     cnt = C.c_int64(0)
-    cap = max(64, s.total // 8)
-    while True:
+    for cap in _grow(max(64, s.total // 8), cnt):
         idx, pos, size = (np.zeros(cap, np.int32) for _ in range(3))
         base = np.zeros(cap, np.uint8)
-        check(_lib.lib().sarlacc_find_homopolymers(ptr(s.chars), ptr(s.off), C.c_int64(n), ptr(idx), ptr(pos), ptr(size), ptr(base),
-                                                   C.c_int64(cap), C.byref(cnt)))
-        if cnt.value <= cap:
-            break
-        cap = cnt.value
+        check(_lib.lib().sarlacc_find_homopolymers(s.chars, s.off, n, idx, pos, size, base, cap, C.byref(cnt)))
     k = cnt.value
     return [idx[:k], pos[:k], size[:k], [chr(c) for c in base[:k]]]
 
@@ -563,14 +523,9 @@ def match_homopolymers(ref_align, read_align):
     homopolymer, longest overlapping run of the same base in the read]."""
     r, q = StringSet.from_strings(ref_align), StringSet.from_strings(read_align)
     cnt = C.c_int64(0)
-    cap = max(64, r.total // 8)
-    while True:
+    for cap in _grow(max(64, r.total // 8), cnt):
         idx, pos, rlen = (np.zeros(cap, np.int32) for _ in range(3))
-        check(_lib.lib().sarlacc_match_homopolymers(ptr(r.chars), ptr(r.off), C.c_int64(len(r)), ptr(q.chars), ptr(q.off), C.c_int64(len(q)),
-                                                    ptr(idx), ptr(pos), ptr(rlen), C.c_int64(cap), C.byref(cnt)))
-        if cnt.value <= cap:
-            break
-        cap = cnt.value
+        check(_lib.lib().sarlacc_match_homopolymers(r.chars, r.off, len(r), q.chars, q.off, len(q), idx, pos, rlen, cap, C.byref(cnt)))
     k = cnt.value
     return [idx[:k], pos[:k], rlen[:k]]
 
@@ -580,17 +535,12 @@ def find_errors(ref_align, read_align):
     positions (0-based, position of the next reference base), insertion lengths]."""
     r, q = StringSet.from_strings(ref_align), StringSet.from_strings(read_align)
     cap_b = int(r.off[1] - r.off[0]) if len(r) else 0
-    cap_i = max(64, r.total // 16)
     sl, ni = C.c_int64(0), C.c_int64(0)
-    while True:
+    for cap_i in _grow(max(64, r.total // 16), ni):
         bases = np.zeros(max(cap_b, 1), np.uint8)
         cols = [np.zeros(max(cap_b, 1), np.int32) for _ in range(5)]
         ip, il = np.zeros(cap_i, np.int32), np.zeros(cap_i, np.int32)
-        check(_lib.lib().sarlacc_find_errors(ptr(r.chars), ptr(r.off), C.c_int64(len(r)), ptr(q.chars), ptr(q.off), C.c_int64(len(q)),
-                                             C.byref(sl), ptr(bases), *[ptr(c) for c in cols], C.c_int64(cap_b), ptr(ip), ptr(il),
-                                             C.c_int64(cap_i), C.byref(ni)))
-        if ni.value <= cap_i:
-            break
-        cap_i = ni.value
+        check(_lib.lib().sarlacc_find_errors(r.chars, r.off, len(r), q.chars, q.off, len(q), C.byref(sl), bases, *cols, cap_b,
+                                             ip, il, cap_i, C.byref(ni)))
     n = sl.value
     return ["".join(chr(c) for c in bases[:n])] + [c[:n] for c in cols] + [ip[:ni.value], il[:ni.value]]

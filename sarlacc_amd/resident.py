@@ -6,17 +6,19 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import check, ptr
-from .encoding import as_encoding, phred_encoding
+from . import _lib, device
+from ._lib import check
+from .encoding import phred_encoding
 from .strset import StringSet
 
 
 class DevBuffer:
+    _as_parameter_ = property(lambda self: self.ptr)   # a buffer is passed to the library as it is
+
     def __init__(self, nbytes):
         self.nbytes = int(nbytes)
         self.ptr = C.c_void_p()
-        check(_lib.lib().sarlacc_dev_malloc(C.byref(self.ptr), C.c_int64(self.nbytes)))
+        check(_lib.lib().sarlacc_dev_malloc(C.byref(self.ptr), self.nbytes))
 
     @classmethod
     def borrow(cls, address, nbytes):
@@ -31,12 +33,12 @@ class DevBuffer:
     def from_numpy(cls, a):
         a = np.ascontiguousarray(a)
         b = cls(a.nbytes)
-        check(_lib.lib().sarlacc_dev_upload(b.ptr, ptr(a), C.c_int64(a.nbytes)))
+        check(_lib.lib().sarlacc_dev_upload(b, a, a.nbytes))
         return b
 
     def to_numpy(self, dtype, count):
         out = _lib.host_array(max(count, 1), dtype)
-        check(_lib.lib().sarlacc_dev_download(ptr(out), self.ptr, C.c_int64(count * out.itemsize)))
+        check(_lib.lib().sarlacc_dev_download(out, self, int(count) * out.itemsize))
         return out[:count]
 
     def __del__(self):
@@ -76,16 +78,16 @@ class DeviceReads:
         else:
             text = np.fromfile(source, dtype=np.uint8)
         d_text = DevBuffer.from_numpy(text if text.size else np.zeros(1, np.uint8))
-        return cls._from_device_text(d_text.ptr, text.size, encoding)
+        return cls._from_device_text(d_text, text.size, encoding)
 
     @classmethod
     def _from_device_text(cls, text_ptr, nbytes, encoding):
         nrec, tb, tn = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(_lib.lib().sarlacc_dev_fastq_index(text_ptr, C.c_int64(nbytes), C.byref(nrec), C.byref(tb), C.byref(tn), None))
+        check(_lib.lib().sarlacc_dev_fastq_index(text_ptr, int(nbytes), C.byref(nrec), C.byref(tb), C.byref(tn), None))
         n = nrec.value
         seq, qual = DevBuffer(max(tb.value, 1)), DevBuffer(max(tb.value, 1))
         off, names, noff = DevBuffer(8 * (n + 1)), DevBuffer(max(tn.value, 1)), DevBuffer(8 * (n + 1))
-        check(_lib.lib().sarlacc_dev_fastq_extract(text_ptr, seq.ptr, qual.ptr, off.ptr, names.ptr, noff.ptr, None))
+        check(_lib.lib().sarlacc_dev_fastq_extract(text_ptr, seq, qual, off, names, noff, None))
         out = cls(seq, qual, off, off.to_numpy(np.int64, n + 1), encoding)
         from .strset import StrList
         nraw = names.to_numpy(np.uint8, tn.value)
@@ -115,9 +117,8 @@ class DeviceReads:
                 pos = 0
                 while pos < text.size:
                     nrec, used = C.c_int64(0), C.c_int64(0)
-                    here = C.c_void_p(d_text.ptr.value + pos)
-                    check(_lib.lib().sarlacc_dev_fastq_split(here, C.c_int64(text.size - pos), C.c_int64(number), C.byref(nrec),
-                                                             C.byref(used), None))
+                    here = d_text.ptr.value + pos
+                    check(_lib.lib().sarlacc_dev_fastq_split(here, text.size - pos, number, C.byref(nrec), C.byref(used), None))
                     if nrec.value < number and not eof:
                         break                           # the chunk continues in the next block
                     if nrec.value < number:
@@ -130,6 +131,9 @@ class DeviceReads:
 
     def __len__(self):
         return len(self.off_host) - 1
+
+    def _encoding(self):
+        return self.encoding if self.encoding is not None else phred_encoding()
 
     @property
     def total(self):
@@ -164,8 +168,7 @@ class DeviceReads:
         if ss is not None:
             names, noff = DevBuffer.from_numpy(ss.chars), DevBuffer.from_numpy(ss.off)
         rec_off, total = DevBuffer(8 * (n + 1)), C.c_int64(0)
-        check(_lib.lib().sarlacc_dev_fastq_format_size(self.off.ptr, C.c_int64(n), names.ptr if names else None,
-                                                       noff.ptr if noff else None, C.c_int64(1), rec_off.ptr, C.byref(total), None))
+        check(_lib.lib().sarlacc_dev_fastq_format_size(self.off, n, names, noff, 1, rec_off, C.byref(total), None))
         # the host knows every length too: it plans the ranges itself
         if ss is not None:
             name_len = np.diff(ss.off)
@@ -190,10 +193,8 @@ class DeviceReads:
         d_text, host = DevBuffer(largest), _lib.host_array(largest, np.uint8)
         for a, b in ranges:
             nbytes = int(ro[b] - ro[a])
-            check(_lib.lib().sarlacc_dev_fastq_format(self.seq.ptr, self.qual.ptr, self.off.ptr, names.ptr if names else None,
-                                                      noff.ptr if noff else None, C.c_int64(1), rec_off.ptr, C.c_int64(a),
-                                                      C.c_int64(b - a), d_text.ptr, None))
-            check(_lib.lib().sarlacc_dev_download(ptr(host), d_text.ptr, C.c_int64(nbytes)))
+            check(_lib.lib().sarlacc_dev_fastq_format(self.seq, self.qual, self.off, names, noff, 1, rec_off, a, b - a, d_text, None))
+            check(_lib.lib().sarlacc_dev_download(host, d_text, nbytes))
             yield host[:nbytes]
 
     def fastq_text(self, block_bytes=None):
@@ -234,8 +235,7 @@ class DeviceReads:
         out = []
         for which in (0, 1):
             d = self._like(woff.copy())
-            check(_lib.lib().sarlacc_dev_windows(self.seq.ptr, self.qual.ptr, self.off.ptr, C.c_int64(len(self)),
-                                                 d.off.ptr, which, d.seq.ptr, d.qual.ptr, None))
+            check(_lib.lib().sarlacc_dev_windows(self.seq, self.qual, self.off, len(self), d.off, which, d.seq, d.qual, None))
             out.append(d)
         return out[0], out[1]
 
@@ -249,9 +249,8 @@ class DeviceReads:
         total = int(wd.sum(dtype=np.int64))
         chars = _lib.host_array(max(total, 1), np.uint8)
         sel = None if from_other is None else np.ascontiguousarray(from_other, dtype=np.uint8)
-        check(_lib.lib().sarlacc_dev_subseq(self.seq.ptr, self.off.ptr, other.seq.ptr if other is not None else None,
-                                            other.off.ptr if other is not None else None, ptr(sel) if sel is not None else None,
-                                            ptr(st), ptr(wd), C.c_int64(n), ptr(chars), C.c_int64(chars.size), ptr(off), None))
+        o_seq, o_off = (other.seq, other.off) if other is not None else (None, None)
+        check(_lib.lib().sarlacc_dev_subseq(self.seq, self.off, o_seq, o_off, sel, st, wd, n, chars, chars.size, off, None))
         return StringSet(chars, off)
 
     def realize(self, idx, reversed_, trim_start=None, trim_end=None):
@@ -271,15 +270,13 @@ class DeviceReads:
         d = self._like(ooff)
         if idx.size:
             d_idx, d_rev, d_ts = DevBuffer.from_numpy(idx), DevBuffer.from_numpy(rev), DevBuffer.from_numpy(ts)   # kept alive over the call
-            check(_lib.lib().sarlacc_dev_realize(self.seq.ptr, self.qual.ptr, self.off.ptr, d_idx.ptr, d_rev.ptr, d_ts.ptr,
-                                                 C.c_int64(idx.size), d.off.ptr, d.seq.ptr, d.qual.ptr, None))
+            check(_lib.lib().sarlacc_dev_realize(self.seq, self.qual, self.off, d_idx, d_rev, d_ts, idx.size, d.off, d.seq, d.qual, None))
         return d
 
     def scramble(self, seed):
         """.scramble_input (R/getAdaptorThresholds.R:68-92) on the device, deterministic in `seed`."""
         d = self._like(self.off_host.copy())
-        check(_lib.lib().sarlacc_dev_scramble(self.seq.ptr, self.qual.ptr, self.off.ptr, C.c_int64(len(self)),
-                                              C.c_uint64(int(seed)), d.seq.ptr, d.qual.ptr, None))
+        check(_lib.lib().sarlacc_dev_scramble(self.seq, self.qual, self.off, len(self), int(seed), d.seq, d.qual, None))
         return d
 
     def align_block(self, adaptor, gap_opening, gap_extension, sec_starts=(), sec_ends=()):
@@ -287,21 +284,13 @@ class DeviceReads:
         number of sections): scores | starts | ends | section starts | section widths (include/sarlacc_amd.h,
         sarlacc_dev_choose_strand) -- one allocation per call, and one download for whoever wants them on the host."""
         n = len(self)
-        ss = np.ascontiguousarray(sec_starts, dtype=np.int32).reshape(-1)
-        se = np.ascontiguousarray(sec_ends, dtype=np.int32).reshape(-1)
-        ns = ss.size
-        enc = as_encoding(self.encoding if self.encoding is not None else phred_encoding())
-        rf = adaptor.encode() if isinstance(adaptor, str) else bytes(adaptor)
+        ns = np.asarray(sec_starts).size
         nsec = max(ns, 1)
         blk = DevBuffer(16 * n + 8 * n * nsec)
         base = blk.ptr.value
-        pad = np.zeros(1, np.int32)
-        check(_lib.lib().sarlacc_dev_align(
-            self.seq.ptr, self.qual.ptr, self.off.ptr, C.c_int64(n), C.c_int32(self.max_len),
-            ptr(enc.errors), enc.names, len(enc), C.c_double(gap_opening), C.c_double(gap_extension),
-            rf, len(rf), 0, ptr(ss if ns else pad), ptr(se if ns else pad), ns,
-            C.c_void_p(base), C.c_void_p(base + 8 * n), C.c_void_p(base + 12 * n), C.c_void_p(base + 16 * n),
-            C.c_void_p(base + 16 * n + 4 * n * nsec), None))
+        device.dev_align(self.seq, self.qual, self.off, n, self.max_len, self._encoding(), gap_opening, gap_extension, adaptor,
+                         True, sec_starts, sec_ends, base, base + 8 * n, base + 12 * n, base + 16 * n, base + 16 * n + 4 * n * nsec,
+                         stream=None)
         return blk, n, ns
 
     @staticmethod
@@ -311,7 +300,7 @@ class DeviceReads:
         nsec = max(ns, 1)
         o_st, o_en, o_so, o_sw = 8 * n, 12 * n, 16 * n, 16 * n + 4 * n * nsec
         host = _lib.host_array(blk.nbytes, np.uint8)
-        check(_lib.lib().sarlacc_dev_download(ptr(host), blk.ptr, C.c_int64(blk.nbytes)))
+        check(_lib.lib().sarlacc_dev_download(host, blk, blk.nbytes))
         scores = host[:o_st].view(np.float64)
         starts, ends = host[o_st:o_en].view(np.int32), host[o_en:o_so].view(np.int32)
         so_h, sw_h = host[o_so:o_sw].view(np.int32), host[o_sw:].view(np.int32)
@@ -326,8 +315,7 @@ class DeviceReads:
         if not (ce[1] == rs[1] == re[1] == n and cs[2] == rs[2] and ce[2] == re[2]):
             raise _lib.SarlaccError("strand choice: result blocks of different shapes")
         out1, out2, rev = DevBuffer(cs[0].nbytes), DevBuffer(ce[0].nbytes), DevBuffer(max(n, 1))
-        check(_lib.lib().sarlacc_dev_choose_strand(cs[0].ptr, ce[0].ptr, rs[0].ptr, re[0].ptr, C.c_int64(n), cs[2], ce[2],
-                                                   out1.ptr, out2.ptr, rev.ptr, None))
+        check(_lib.lib().sarlacc_dev_choose_strand(cs[0], ce[0], rs[0], re[0], n, cs[2], ce[2], out1, out2, rev, None))
         return (DeviceReads.block_to_host((out1, n, cs[2])), DeviceReads.block_to_host((out2, n, ce[2])),
                 rev.to_numpy(np.uint8, n).view(np.bool_))
 
@@ -344,12 +332,7 @@ class DeviceReads:
         n = len(self)
         if n == 0:
             return np.zeros(0)
-        enc = as_encoding(self.encoding if self.encoding is not None else phred_encoding())
-        rf = adaptor.encode() if isinstance(adaptor, str) else bytes(adaptor)
         scores = DevBuffer(8 * n)
-        one = np.zeros(1, np.int32)
-        check(_lib.lib().sarlacc_dev_align(
-            self.seq.ptr, self.qual.ptr, self.off.ptr, C.c_int64(n), C.c_int32(self.max_len),
-            ptr(enc.errors), enc.names, len(enc), C.c_double(gap_opening), C.c_double(gap_extension),
-            rf, len(rf), 0 if local else 1, ptr(one), ptr(one), 0, scores.ptr, None, None, None, None, None))
+        device.dev_align(self.seq, self.qual, self.off, n, self.max_len, self._encoding(), gap_opening, gap_extension, adaptor,
+                         local, d_scores=scores, stream=None)
         return scores.to_numpy(np.float64, n)

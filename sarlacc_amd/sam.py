@@ -15,7 +15,7 @@ import re
 import numpy as np
 
 from . import _lib
-from ._lib import SarlaccError, check, ptr
+from ._lib import SarlaccError, check
 from .strset import StringSet, StrList
 
 # the `sub` patterns of :35-36; the greedy .* makes the LAST tag win
@@ -128,16 +128,15 @@ def _parse_block(d_text, nbytes, first_line, tables, use_minq, thr):
     from .resident import DevBuffer
     lib = _lib.lib()
     nlines, nk, nb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    check(lib.sarlacc_dev_sam_index(d_text.ptr, C.c_int64(nbytes), C.c_int64(first_line), ptr(tables.ref), ptr(tables.ref_off),
-                                    C.c_int64(tables.n_ref), ptr(tables.mask), ptr(tables.extra), ptr(tables.extra_off),
-                                    C.c_int64(tables.n_extra), C.c_int(1 if use_minq else 0), C.c_int64(thr), C.byref(nlines),
+    check(lib.sarlacc_dev_sam_index(d_text, nbytes, first_line, tables.ref, tables.ref_off, tables.n_ref, tables.mask,
+                                    tables.extra, tables.extra_off, tables.n_extra, 1 if use_minq else 0, thr, C.byref(nlines),
                                     C.byref(nk), C.byref(nb), None))
     n = nk.value
     cols = DevBuffer(max(21 * n, 1))            # five int32 columns, then the strand bytes
     names, noff = DevBuffer(max(nb.value, 1)), DevBuffer(8 * (n + 1))
     base = cols.ptr.value
-    check(lib.sarlacc_dev_sam_extract(d_text.ptr, *[C.c_void_p(base + 4 * n * k) for k in (0, 1, 2)], C.c_void_p(base + 20 * n),
-                                      *[C.c_void_p(base + 4 * n * k) for k in (3, 4)], names.ptr, noff.ptr, None))
+    check(lib.sarlacc_dev_sam_extract(d_text, *[base + 4 * n * k for k in (0, 1, 2)], base + 20 * n,
+                                      *[base + 4 * n * k for k in (3, 4)], names, noff, None))
     host = cols.to_numpy(np.uint8, 21 * n)
     out = [host[4 * n * k:4 * n * (k + 1)].view(np.int32) for k in range(5)] + [host[20 * n:21 * n]]
     chars = names.to_numpy(np.uint8, nb.value)

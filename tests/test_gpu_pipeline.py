@@ -251,6 +251,46 @@ def test_page_locked_result_blocks_are_pooled_and_hold_what_the_device_wrote():
     assert np.array_equal(dev.to_numpy(np.uint8, data.size), data)   # (a fresh block after the release)
 
 
+def test_dev_align_takes_buffers_tensors_and_addresses(enc):
+    """The device arguments of device.dev_align as DevBuffers, as torch tensors over the same bytes and as raw integer
+    addresses, the stream as None and as 0: every run gives the bits of calls.adaptor_align on the same reads."""
+    torch = pytest.importorskip("torch")
+    from sarlacc_amd import calls, device
+    from sarlacc_amd.resident import DevBuffer
+    from sarlacc_amd.strset import StringSet
+    reads = ["TTACGTTGCAGG", "ACGTAGCATTTTGGGACCA", "GGGGACGTTGCATTTTACGTAAAC"]
+    quals = ["IIII5IIII+II", "I#III6IIIIIIIII?III", "89:;<=>?@ABCDEFGHI#$%&'("]
+    adaptor, ss, se = "ACGTTGCA", [2], [6]
+    want = calls.adaptor_align(reads, quals, enc, 5, 1, adaptor, ss, se)
+    assert want[0].max() > 0 and (want[1] > 0).any()
+    s, q = StringSet.from_strings(reads), StringSet.from_strings(quals)
+    n, max_len = len(s), int(s.widths().max())
+    host = (s.chars, q.chars, s.off)
+    tensors = [torch.from_numpy(a).to("cuda") for a in host]
+
+    def outputs():
+        return [torch.zeros(n, dtype=torch.float64, device="cuda")] + [torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(4)]
+
+    def run(inputs, outs, as_arg, stream):
+        device.dev_align(*[as_arg(t) for t in inputs], n, max_len, enc, 5, 1, adaptor, True, ss, se, *[as_arg(t) for t in outs],
+                         stream=stream)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in outs]
+
+    got = [run(tensors, outputs(), lambda t: t, 0),
+           run(tensors, outputs(), lambda t: t.data_ptr(), 0),
+           run(tensors, outputs(), lambda t: DevBuffer.borrow(t.data_ptr(), t.numel() * t.element_size()), 0),
+           run(tensors, outputs(), lambda t: t, None)]
+    # and buffers the library allocated itself, read back through it
+    uploaded, owned = [DevBuffer.from_numpy(a) for a in host], [DevBuffer(8 * n)] + [DevBuffer(4 * n) for _ in range(4)]
+    device.dev_align(*uploaded, n, max_len, enc, 5, 1, adaptor, True, ss, se, *owned, stream=None)
+    got.append([owned[0].to_numpy(np.float64, n)] + [b.to_numpy(np.int32, n) for b in owned[1:]])
+    for sc, st, en, so, sw in got:
+        assert np.array_equal(sc.view(np.int64), want[0].view(np.int64))
+        assert np.array_equal(st, want[1]) and np.array_equal(en, want[2])
+        assert np.array_equal(so, want[3][0]) and np.array_equal(sw, want[4][0])
+
+
 def test_two_rank_pipeline_driver_matches_single_rank():
     """tools/run_pipeline.py (BASELINE config 5 in miniature) with two ranks sharing this GPU
     over gloo: read-range DP shards, tile-sharded UMI search + all-gather of neighbour pairs,

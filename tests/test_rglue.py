@@ -7,7 +7,8 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_text import ROOT, _calls, _header_decls, _split_args, _strip_comments
+
 GLUE = os.path.join(ROOT, "r-glue", "src")
 
 # routine -> number of SEXP arguments (init.cpp:9-35): all 18 registered routines
@@ -20,49 +21,6 @@ ROUTINES = {
     "quick_msa": 7,
     "find_homopolymers": 1, "match_homopolymers": 2, "find_errors": 2,
 }
-
-
-def _strip_comments(text):
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"//[^\n]*", " ", text)
-
-
-def _split_args(s):
-    """top-level comma split of an argument list"""
-    out, depth, cur = [], 0, ""
-    for ch in s:
-        if ch in "([{":
-            depth += 1
-        elif ch in ")]}":
-            depth -= 1
-        if ch == "," and depth == 0:
-            out.append(cur.strip())
-            cur = ""
-        else:
-            cur += ch
-    if cur.strip():
-        out.append(cur.strip())
-    return out
-
-
-def _calls(text, prefix):
-    """(name, [args]) for every `prefix...(` occurrence, with balanced parentheses"""
-    res = []
-    for m in re.finditer(r"\b(" + prefix + r"\w*)\s*\(", text):
-        i, depth = m.end(), 1
-        while depth:
-            depth += {"(": 1, ")": -1}.get(text[i], 0)
-            i += 1
-        res.append((m.group(1), _split_args(text[m.end():i - 1])))
-    return res
-
-
-def _header_decls():
-    text = _strip_comments(open(os.path.join(ROOT, "include", "sarlacc_amd.h")).read())
-    decls = {}
-    for name, args in _calls(text, "sarlacc_"):
-        decls[name] = 0 if args == ["void"] else len(args)
-    return decls
 
 
 def _glue_sources():
@@ -82,7 +40,7 @@ def test_every_routine_has_one_shim_with_the_registered_arity():
 
 
 def test_every_abi_call_matches_the_header():
-    decls = _header_decls()
+    decls = {name: len(params) for name, (_, params) in _header_decls().items()}
     used = set()
     for fname, text in _glue_sources().items():
         for name, args in _calls(text, "sarlacc_"):
