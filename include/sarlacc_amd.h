@@ -61,7 +61,7 @@ double sarlacc_stage_ms(const char* name);
  * cells of the pairwise alignments), "consensus_cells" (rows x width); <0 if unset. */
 double sarlacc_stage_count(const char* name);
 /* Duration in ms of the DP kernel launches recorded by the last
- * sarlacc_dev_* align call (HIP events on the launch stream); <0 if none. */
+ * sarlacc_dev_* align call (HIP events on the launch stream; a panel call: the sum over its DP launches); <0 if none. */
 double sarlacc_last_kernel_ms(void);
 
 /* ------------------------------------------------------------------ */
@@ -150,6 +150,34 @@ int sarlacc_dev_align_packed(const uint8_t* d_packed, const uint8_t* d_nmask, co
                              double* d_scores, int32_t* d_starts, int32_t* d_ends,
                              int32_t* d_sec_start_out, int32_t* d_sec_width_out,
                              void* stream);
+
+/* A whole barcode panel against one batch: the loop of barcodeAlign (R/barcodeAlign.R:20-37) around .Call barcode_align
+ * (src/barcode_align.cpp:10-44), with its reduction done on the device.  barcodes / barcode_off[nbarcodes + 1] hold the
+ * panel back to back.  For every read, over the barcodes b = 0, 1, ... in panel order with s its global-mode score:
+ *     if (s > score) { next = score; score = s; best = b + 1; } else if (s > next) next = s;
+ * from best = 0 (none: R's NA), score = next = -inf; both comparisons are strict, so the first of equal scores wins and a
+ * score equal to the best one counts as next best.  The caller's gap is score - next.  all_scores, when not NULL, receives
+ * every score as [nbarcodes][n]; each is bit for bit what sarlacc_barcode_align gives for that barcode alone.
+ * Barcodes of 1 to 32 columns run fused (k_barcode_panel: one launch per run of consecutive such barcodes, reads staged
+ * once); the others -- and all of them under option "align_panel" = -1 -- go through the DP of sarlacc_dev_align one at
+ * a time into a score row that is folded on the device.  sarlacc_stage_count "panel_fused_barcodes" /
+ * "panel_single_barcodes" / "panel_launches" (DP launches) describe the last call, sarlacc_last_kernel_ms its DP launches.
+ * n == 0 writes nothing; nbarcodes == 0 gives best 0 and -inf twice.  A call fails with the message the loop over the
+ * barcodes would have raised first (each barcode as in sarlacc_barcode_align, in panel order); the outputs are then
+ * unspecified.  The device form waits for the stream before it returns. */
+int sarlacc_dev_barcode_panel(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off,
+                              int64_t n, int32_t max_len,
+                              const double* enc_errors, const char* enc_names, int enc_n,
+                              double gapopen, double gapext,
+                              const char* barcodes, const int64_t* barcode_off, int nbarcodes,
+                              int32_t* d_best, double* d_score, double* d_next, double* d_all_scores,
+                              void* stream);
+int sarlacc_barcode_panel(const char* seq, const int64_t* seq_off,
+                          const char* qual, const int64_t* qual_off, int64_t n,
+                          const double* enc_errors, const char* enc_names, int enc_n,
+                          double gapopen, double gapext,
+                          const char* barcodes, const int64_t* barcode_off, int nbarcodes,
+                          int32_t* best, double* score, double* next, double* all_scores);
 
 /* ---- resident batches for the scrambled-control callers ----
  * tuneAlignment (R/tuneAlignment.R:30-72) and getAdaptorThresholds
@@ -368,7 +396,8 @@ int sarlacc_set_msa_spec(int spec);
  *   "msa2_budget_gb" (GB a batch of groups may take), "msa2_max_columns" (a lower ceiling of spec v2's profiles),
  *   "msa2_simple_extend" (the extended library by the one-position-per-lane kernel everywhere), "msa2_wide_extend" (largest
  *   group size of the four-positions-per-lane kernel), "align_locate" (adaptor_align: -1 the snapshot path alone, 1 every read
- *   through the locator's redo list; sarlacc_stage_count "align_redo" / "align_stalls" report the last such call).
+ *   through the locator's redo list; sarlacc_stage_count "align_redo" / "align_stalls" report the last such call),
+ *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a
  * value.  Nothing in the reference corresponds. */
 int sarlacc_set_option(const char* name, int value);

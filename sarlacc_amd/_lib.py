@@ -121,6 +121,8 @@ def _prototypes():
         "sarlacc_dev_align": (i, [p, p, p] + dev_align),
         "sarlacc_dev_pack_reads": (i, [p, i64, p, p, p]),
         "sarlacc_dev_align_packed": (i, [p, p, p, p] + dev_align),
+        "sarlacc_dev_barcode_panel": (i, [p, p, p, i64, i32] + enc + [f64, f64, p, p, i, p, p, p, p, p]),
+        "sarlacc_barcode_panel": (i, reads + enc + [f64, f64, p, p, i, p, p, p, p]),
         "sarlacc_dev_malloc": (i, [p, i64]),
         "sarlacc_dev_free": (i, [p]),
         "sarlacc_dev_pool_release": (i, []),

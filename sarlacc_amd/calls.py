@@ -118,6 +118,35 @@ def barcode_align(barcodeseq, barcodequal, encoding, gapopen, gapext, reference)
                         gapopen, gapext, reference, "barcode sequence")
 
 
+def _panel_args(barcodes):
+    """A barcode panel as the library takes it: the barcodes back to back, their offsets, their number.  Each one is checked
+    as barcode_align checks its `reference`."""
+    bcs = StringSet.from_strings([_string(b, "barcode sequence") for b in barcodes])
+    return bcs.chars if bcs.chars.size else np.zeros(1, np.uint8), bcs.off, len(bcs)
+
+
+def _panel_result(n, nb, all_scores):
+    best = _lib.host_array(n, np.int32)
+    score, nxt = _lib.host_array(n, np.float64), _lib.host_array(n, np.float64)
+    matrix = _lib.host_array(max(nb * n, 1), np.float64) if all_scores else None
+    return best, score, nxt, matrix
+
+
+def barcode_panel(seq, qual, encoding, gapopen, gapext, barcodes, all_scores=False):
+    """The loop of barcodeAlign over .Call barcode_align (R/barcodeAlign.R:20-37) in one call: (best barcode as int32, 1-based,
+    0 = none; its score; the next best score[; every score as (barcodes, reads)])."""
+    chars, boff, nb = _panel_args(barcodes)
+    go = _numeric(gapopen, "gap opening penalty")
+    ge = _numeric(gapext, "gap extension penalty")
+    s, q = _seq_qual(seq, qual)
+    enc = as_encoding(encoding)
+    n = len(s)
+    best, score, nxt, matrix = _panel_result(n, nb, all_scores)
+    check(_lib.lib().sarlacc_barcode_panel(s.chars, s.off, q.chars, q.off, n, enc.errors, enc.names, len(enc), go, ge,
+                                           chars, boff, nb, best, score, nxt, matrix))
+    return (best, score, nxt, matrix[:nb * n].reshape(nb, n)) if all_scores else (best, score, nxt)
+
+
 def general_align(inputseq, inputqual, encoding, gapopen, gapext, reference, edit_only):
     """.Call general_align (src/general_align.cpp:10-62).
     Returns [scores, edit distances, reference strings, query strings]."""

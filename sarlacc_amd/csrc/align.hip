@@ -26,7 +26,7 @@
 //
 // All arithmetic is fp64 add/sub/compare in the reference's order, compiled with
 // -ffp-contract=off, so scores are bit-identical to the CPU path.
-#include "common.hpp"
+#include "align_host.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
@@ -1721,7 +1721,7 @@ __global__ void __launch_bounds__(WIDE_MAXT) k_align_wide_q(const AlignArgs A) {
 
 // Per-column lookup info: which fp64 table a column reads, decided by the
 // reference character alone (src/reference_align.cpp:184-212, SURVEY App.B Q2).
-static int column_info(char r, uint32_t* info) {
+int column_info(char r, uint32_t* info) {
     uint32_t code = 7, tmatch, tmis;
     switch (r) {
         case 'A': code = 0; tmatch = 0; tmis = 1; break;
@@ -1739,7 +1739,7 @@ static int column_info(char r, uint32_t* info) {
 
 // (src/reference_align.cpp:21-52) -- built on the host with the host libm so the
 // device never evaluates a transcendental on the scoring path.
-static void build_tables(const double* errors, int n, std::vector<double>& tab) {
+void build_tables(const double* errors, int n, std::vector<double>& tab) {
     tab.assign(static_cast<size_t>(5) * n, 0.0);
     const double four = 4.0, ratio = four / (four - 1.0);
     auto odds = [&](double g, double e) { return std::log(g * (1 - e) * four + (1 - g) * e * ratio) / M_LN2; };
@@ -1761,8 +1761,8 @@ static void build_tables(const double* errors, int n, std::vector<double>& tab) 
 //     other code (including 4) on a mismatch row;
 //   * each ambiguity class present in the reference (2-fold, 3-fold, N) gets five identical
 //     rows: its score does not depend on the read base (src/reference_align.cpp:184-212).
-static void build_cost_rows(const std::vector<double>& tab, int n, const uint32_t* colinfo, int R,
-                            std::vector<double>& rows, std::vector<uint32_t>& colbase) {
+void build_cost_rows(const std::vector<double>& tab, int n, const uint32_t* colinfo, int R,
+                     std::vector<double>& rows, std::vector<uint32_t>& colbase) {
     rows.clear();
     auto append = [&](int t) { rows.insert(rows.end(), tab.begin() + static_cast<size_t>(t) * n, tab.begin() + static_cast<size_t>(t + 1) * n); };
     for (int r = 0; r < 8; ++r) append(r == 3 ? 0 : 1);
@@ -1931,19 +1931,6 @@ static int launch_k(int K, int rowf, int R, bool pensel, int mode, bool local, c
     return fail("sarlacc_amd: unsupported columns-per-lane %d", K);
 }
 
-struct AlignOut {
-    double* d_scores = nullptr;
-    int32_t* d_starts = nullptr;
-    int32_t* d_ends = nullptr;
-    int32_t* d_sec_so = nullptr;
-    int32_t* d_sec_wo = nullptr;
-    // mode 2
-    uint8_t* d_aln_ref = nullptr;
-    uint8_t* d_aln_qry = nullptr;
-    int32_t* d_aln_len = nullptr;
-    int32_t* d_edits = nullptr;
-};
-
 // References beyond MAX_REF columns: one workgroup per alignment (k_align_wide).  `a` is complete except for the scratch.
 static int launch_wide(AlignArgs& a, int R, int kernel_mode, int32_t max_len, long long n, hipStream_t stream) {
     Context& c = ctx();
@@ -2035,20 +2022,12 @@ static int launch_wide(AlignArgs& a, int R, int kernel_mode, int32_t max_len, lo
 
 // kernel_mode: 0 scores, 1 map, 2 strings.  Returns in *bad_qual_read the smallest
 // index of a read with a quality character below the encoding offset (or INT_MAX).
-// A host call may hand its batch over in chunks so that the upload of chunk k+1 overlaps the
-// kernel of chunk k: every chunk is one run_align on a slice of the same device arrays.
-struct ChunkOpts {
-    int64_t sec_stride = 0;   // 0: n (stand-alone launch)
-    int read_base = 0;        // index of the slice's first read in the whole batch
-    bool init_bad = true;     // reset the bad-quality flag (first chunk only)
-    bool finish = true;       // read the flag back and wait for the stream (last chunk only)
-};
-
-static int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
-                     int32_t max_len, const double* enc_errors, const char* enc_names, int enc_n,
-                     double gapopen, double gapext, const char* ref, int R, bool local, int kernel_mode,
-                     const int32_t* sec_starts, const int32_t* sec_ends, int nsec, const AlignOut& out,
-                     hipStream_t stream, int* bad_qual_read, const ChunkOpts& co = ChunkOpts()) {
+// (ChunkOpts, align_host.hpp: a host call may hand its batch over in chunks.)
+int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
+              int32_t max_len, const double* enc_errors, const char* enc_names, int enc_n,
+              double gapopen, double gapext, const char* ref, int R, bool local, int kernel_mode,
+              const int32_t* sec_starts, const int32_t* sec_ends, int nsec, const AlignOut& out,
+              hipStream_t stream, int* bad_qual_read, const ChunkOpts& co) {
     Context& c = ctx();
     if (co.init_bad) *bad_qual_read = std::numeric_limits<int>::max();
     if (n <= 0) return 0;
@@ -2201,11 +2180,16 @@ static int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t
     const size_t lds = sizeof(uint16_t) * NWAVES * (sh.rowf == 2 ? NGMAX2 * (RING + RING_MIRROR) : NGMAX * RING_SLOT) + sizeof(double) * rows.size() +
                        sizeof(int32_t) * NWAVES * sh.ngroups * (R + 1) + 16;
     if (!wide && lds > 64 * 1024) return fail("sarlacc_amd: alignment tables do not fit in LDS");
-    SL_HIP(hipEventRecord(c.ev_start, stream));
+    if (co.stage) SL_TRY(c.stage_begin(co.stage, stream));
+    else SL_HIP(hipEventRecord(c.ev_start, stream));
     if (wide) SL_TRY(launch_wide(a, R, kernel_mode == 3 ? 1 : kernel_mode, max_len, n, stream));
     else SL_TRY(launch_k(sh.K, sh.rowf, R, pensel, kernel_mode, local, a, static_cast<int>(grid), lds, stream));
-    SL_HIP(hipEventRecord(c.ev_stop, stream));
-    c.timed = true;
+    if (co.stage) {
+        SL_TRY(c.stage_end(co.stage, stream));
+    } else {
+        SL_HIP(hipEventRecord(c.ev_stop, stream));
+        c.timed = true;
+    }
 
     if (!co.finish) return 0;
     int flags[2] = {0, 0}, lstats[2] = {0, 0};
@@ -2254,19 +2238,11 @@ static int first_error(int64_t n, const int64_t* seq_off, const int64_t* qual_of
     return fail("unrecognized base in reference sequence");
 }
 
-struct HostBatch {
-    uint8_t* d_seq = nullptr;
-    uint8_t* d_qual = nullptr;
-    int64_t* d_off = nullptr;
-    int32_t max_len = 0;
-    int64_t len_bad = -1;
-};
-
 // Uploads a batch given host string sets.  Reads whose quality string has a
 // different length make the whole call fail later (first_error), so qualities
 // are copied with the sequence offsets only when every length agrees.
-static int upload_batch(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off,
-                        int64_t n, HostBatch* hb, hipStream_t s, bool defer_data = false) {
+int upload_batch(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off,
+                 int64_t n, HostBatch* hb, hipStream_t s, bool defer_data) {
     int64_t mx = 0;
     bool same = true;
     for (int64_t i = 0; i < n; ++i) {

@@ -26,7 +26,7 @@ int fail(const char* fmt, ...) {
 }
 
 static const char* const kOptNames[OPT_N] = {"msa_spec", "msa2_general_rows", "msa2_chain_hbm", "msa2_waves_per_cu", "msa2_single_wave", "msa2_batches", "align_pensel", "align_chunks",
-                                             "align_k", "align_waves_per_cu", "consensus_chars", "consensus_generic", "msa_int32", "msa_affine", "umi_full_rounds", "umi_tile_search", "msa_bitvector", "msa_bitvector_core", "msa_bitvector_tile_gb", "align_interleave", "umi_split_min", "msa2_tight_profiles", "umi_scan_single", "align_wide_barrier", "msa2_budget_gb", "msa2_max_columns", "align_wide_band", "msa2_simple_extend", "msa2_wide_extend", "align_locate"};
+                                             "align_k", "align_waves_per_cu", "consensus_chars", "consensus_generic", "msa_int32", "msa_affine", "umi_full_rounds", "umi_tile_search", "msa_bitvector", "msa_bitvector_core", "msa_bitvector_tile_gb", "align_interleave", "umi_split_min", "msa2_tight_profiles", "umi_scan_single", "align_wide_barrier", "msa2_budget_gb", "msa2_max_columns", "align_wide_band", "msa2_simple_extend", "msa2_wide_extend", "align_locate", "align_panel"};
 static int* option_values() {
     static int values[OPT_N];
     static const bool parsed = [] {
@@ -229,6 +229,7 @@ double sarlacc_stage_count(const char* name) {
 double sarlacc_last_kernel_ms(void) {
     sarlacc::Context& c = sarlacc::ctx();
     if (!c.ready || !c.timed) return -1.0;
+    if (c.timed == sarlacc::Context::TIMED_PANEL) return sarlacc_stage_ms("panel_dp");
     if (hipEventSynchronize(c.ev_stop) != hipSuccess) return -1.0;
     float ms = 0;
     if (hipEventElapsedTime(&ms, c.ev_start, c.ev_stop) != hipSuccess) return -1.0;

@@ -68,6 +68,7 @@ enum Opt {
     OPT_MSA2_SIMPLE_EXTEND,   // spec v2: the extended library by the one-position-per-lane kernel also for unit weights (A/B, tests)
     OPT_MSA2_WIDE_EXTEND,     // spec v2: largest group size that takes the four-positions-per-lane extension kernel (default 12; A/B)
     OPT_ALIGN_LOCATE,         // adaptor_align: -1 the snapshot path instead of the integer locator fill + fp64 window (A/B); 1 every read on the redo list (tests)
+    OPT_ALIGN_PANEL,          // barcode panel: -1 every barcode by run_align + the device fold instead of the fused kernel (A/B, cross-check)
     OPT_N
 };
 int option(Opt o);
@@ -86,7 +87,10 @@ struct Context {
     bool ready = false;
     int num_cu = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool timed = false;
+    // what sarlacc_last_kernel_ms reports: 0 nothing yet, 1 (true) the event pair above, TIMED_PANEL the segments of the
+    // stage timer "panel_dp" (a panel call's DP launches are not contiguous on the stream)
+    enum { TIMED_PANEL = 2 };
+    int timed = 0;
     std::map<std::string, Workspace> ws;
     // named stage timers (HIP events on the launch stream; read back by sarlacc_stage_ms)
     // A stage may run in several segments (batches); sarlacc_stage_ms adds them up.  stage_reset starts a new call.

@@ -377,28 +377,26 @@ def getBarcodeThresholds(baligned, nmads=3):
 # ---------------------------------------------------------------------------
 def barcodeAlign(sequences, barcodes, gapOpening=5, gapExtension=1):
     """barcodeAlign (R/barcodeAlign.R:4-40): best barcode, its score, and the gap to the next best.
-    The barcode reads are uploaded once and stay resident while every candidate is aligned
+    The barcode reads are uploaded once and the whole panel is aligned and reduced in one library call
     (the reference re-marshals them for each barcode, R/barcodeAlign.R:20-24)."""
     n = len(sequences)
     current = np.full(n, -np.inf)
     nextbest = np.full(n, -np.inf)
     ident = np.full(n, -1, dtype=np.int64)  # NA_integer_
-    dev = None
     if calls.__name__.endswith("sarlacc_amd.calls") and n:
+        # the whole panel in one call on the resident reads, reduced on the device (sarlacc_dev_barcode_panel)
         from .resident import DeviceReads
-        dev = DeviceReads.upload(sequences)
-    for b, bc in enumerate(barcodes):
-        if dev is not None:
-            calls._string(str(bc), "barcode sequence")
-            scores = dev.align_scores(str(bc), gapOpening, gapExtension, local=False)
-        else:
+        best, current, nextbest = DeviceReads.upload(sequences).barcode_panel([str(bc) for bc in barcodes], gapOpening, gapExtension)
+        ident = np.where(best == 0, -1, best).astype(np.int64)
+    else:
+        for b, bc in enumerate(barcodes):
             scores = calls.barcode_align(sequences.seq, sequences.qual, sequences.encoding, gapOpening, gapExtension, str(bc))
-        keep = scores > current
-        second = ~keep & (scores > nextbest)
-        ident[keep] = b + 1
-        nextbest[keep] = current[keep]
-        current[keep] = scores[keep]
-        nextbest[second] = scores[second]
+            keep = scores > current
+            second = ~keep & (scores > nextbest)
+            ident[keep] = b + 1
+            nextbest[keep] = current[keep]
+            current[keep] = scores[keep]
+            nextbest[second] = scores[second]
     return {"barcode": ident, "score": current, "gap": current - nextbest,
             "metadata": {"gapOpening": gapOpening, "gapExtension": gapExtension, "barcodes": list(barcodes)}}
 

@@ -336,3 +336,25 @@ class DeviceReads:
         device.dev_align(self.seq, self.qual, self.off, n, self.max_len, self._encoding(), gap_opening, gap_extension, adaptor,
                          local, d_scores=scores, stream=None)
         return scores.to_numpy(np.float64, n)
+
+    def barcode_panel(self, barcodes, gap_opening, gap_extension, all_scores=False):
+        """calls.barcode_panel on the resident batch: only best / score / next best (20 bytes per read, whatever the panel's
+        size) come back, and the score matrix when asked for."""
+        from .calls import _numeric, _panel_args, _panel_result
+        from .encoding import as_encoding
+        chars, boff, nb = _panel_args(barcodes)
+        go = _numeric(gap_opening, "gap opening penalty")
+        ge = _numeric(gap_extension, "gap extension penalty")
+        enc = as_encoding(self._encoding())
+        n = len(self)
+        best, score, nxt, matrix = _panel_result(n, nb, all_scores)
+        if n:
+            d_best, d_score, d_next = DevBuffer(4 * n), DevBuffer(8 * n), DevBuffer(8 * n)
+            d_all = DevBuffer(8 * n * nb) if all_scores and nb else None
+            check(_lib.lib().sarlacc_dev_barcode_panel(self.seq, self.qual, self.off, n, self.max_len, enc.errors, enc.names,
+                                                       len(enc), go, ge, chars, boff, nb, d_best, d_score, d_next, d_all, None))
+            for host, dev in ((best, d_best), (score, d_score), (nxt, d_next)):
+                check(_lib.lib().sarlacc_dev_download(host, dev, host.nbytes))
+            if d_all is not None:
+                check(_lib.lib().sarlacc_dev_download(matrix, d_all, 8 * n * nb))
+        return (best, score, nxt, matrix[:nb * n].reshape(nb, n)) if all_scores else (best, score, nxt)
