@@ -255,6 +255,44 @@ int sarlacc_find_errors(const char* ref, const int64_t* ref_off, int64_t nref, c
                         int32_t* to_t, int32_t* deletions, int64_t cap_bases, int32_t* ins_pos, int32_t* ins_len,
                         int64_t cap_ins, int64_t* nins);
 
+/* The profiling workflow on a resident batch in one call: every read aligned to `reference` as sarlacc_general_align
+ * aligns it, and the alignments reduced on the device to what sarlacc_find_errors and sarlacc_match_homopolymers give
+ * for general_align's strings (src/general_align.cpp:10-62 -> src/find_errors.cpp:9-121 + src/homopolymer.cpp:141-209;
+ * R/errorFinder.R, R/homopolymerMatcher.R) -- as histograms: no alignment string and no per-event list leaves the
+ * device (profile_reads.hip: k_profile_pairs reads the aligner's end-first strings where they lie).
+ * The call does the work, keeps the results in the library's workspace and reports their sizes: *n_ins distinct
+ * (position, length) insertion pairs, *n_hp_runs homopolymers of the reference (maximal stretches of two or more equal
+ * characters), *n_hp_obs distinct (run, observed length) pairs.  d_scores / d_edits (device, n entries, may be NULL)
+ * receive what sarlacc_general_align reports, bit for bit.  sarlacc_profile_fetch then copies out, for the last
+ * profile of the calling thread:
+ *   counts[5][R]  alignments showing A, C, G, T, a deletion at each reference position;
+ *   ins_*         per pair the 0-based position of the next reference base (R: after the last one), the length and
+ *                 the number of alignments (int64) with such an insertion, ascending by (position, length);
+ *   run_*         start and end (1-based, inclusive) and base of each homopolymer of the reference;
+ *   obs_*         per pair the run (index into run_*), the longest overlapping run of the same base in the read (0:
+ *                 none) and its multiplicity, ascending by (run, length); the multiplicities of a run add up to n.
+ * A capacity below the reported size makes the fetch fail with a message and copy nothing.
+ * The batch runs in chunks of reads so that the aligner's strings (2 x (bases + reads x R) bytes) stay within a fixed
+ * budget; option "profile_chunk_reads" forces a chunk size.  sarlacc_stage_ms "profile_align" (DP), "profile_kernel"
+ * (k_profile_pairs) and "profile_reduce" (merging the events) and sarlacc_stage_count "profile_chunks" describe the last
+ * call.  Errors are the chain's, in its order: what sarlacc_general_align raises, then "unknown character '%c' in
+ * alignment string" for the first read character other than A/C/G/T opposite a reference base.  n == 0 (where the
+ * chain has no reference to take from its first alignment) gives zero counts, the reference's runs and no pairs;
+ * reference_len == 0 gives no counts and every non-empty read as one insertion at position 0.  Limits: those of
+ * sarlacc_general_align.  The device form waits for the stream before it returns. */
+int sarlacc_dev_profile_reads(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n, int32_t max_len,
+                              const double* enc_errors, const char* enc_names, int enc_n, double gapopen, double gapext,
+                              const char* reference, int reference_len, double* d_scores, int32_t* d_edits,
+                              int64_t* n_ins, int64_t* n_hp_runs, int64_t* n_hp_obs, void* stream);
+int sarlacc_profile_fetch(int32_t* counts, int32_t* ins_pos, int32_t* ins_len, int64_t* ins_mult, int64_t cap_ins,
+                          int32_t* run_start, int32_t* run_end, char* run_base, int64_t cap_runs,
+                          int32_t* obs_run, int32_t* obs_len, int64_t* obs_mult, int64_t cap_obs);
+/* The same from host string sets (uploaded as by sarlacc_general_align); scores / edits are host arrays, may be NULL. */
+int sarlacc_profile_reads(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off, int64_t n,
+                          const double* enc_errors, const char* enc_names, int enc_n, double gapopen, double gapext,
+                          const char* reference, int reference_len, double* scores, int32_t* edits,
+                          int64_t* n_ins, int64_t* n_hp_runs, int64_t* n_hp_obs);
+
 /* FASTQ text already in device memory -> resident read batch.  Replaces the
  * host-side ShortRead::FastqStreamer + .FASTQ2QSDS conversion (R/adaptorAlign.R:26-37,:104-110;
  * R/realizeReads.R:15-26).  4-line records, LF or CRLF, trailing blank lines ignored; sequences
@@ -397,7 +435,8 @@ int sarlacc_set_msa_spec(int spec);
  *   "msa2_simple_extend" (the extended library by the one-position-per-lane kernel everywhere), "msa2_wide_extend" (largest
  *   group size of the four-positions-per-lane kernel), "align_locate" (adaptor_align: -1 the snapshot path alone, 1 every read
  *   through the locator's redo list; sarlacc_stage_count "align_redo" / "align_stalls" report the last such call),
- *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel).
+ *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel),
+ *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a
  * value.  Nothing in the reference corresponds. */
 int sarlacc_set_option(const char* name, int value);

@@ -140,6 +140,9 @@ def _prototypes():
         "sarlacc_find_homopolymers": (i, [p, p, i64, p, p, p, p, i64, p]),
         "sarlacc_match_homopolymers": (i, [p, p, i64, p, p, i64, p, p, p, i64, p]),
         "sarlacc_find_errors": (i, [p, p, i64, p, p, i64, p, p, p, p, p, p, p, i64, p, p, i64, p]),
+        "sarlacc_dev_profile_reads": (i, [p, p, p, i64, i32] + enc + [f64, f64, p, i, p, p, p, p, p, p]),
+        "sarlacc_profile_fetch": (i, [p, p, p, p, i64, p, p, p, i64, p, p, p, i64]),
+        "sarlacc_profile_reads": (i, scored + [p, p, p, p, p]),
         "sarlacc_dev_fastq_index": (i, [p, i64, p, p, p, p]),
         "sarlacc_dev_fastq_split": (i, [p, i64, i64, p, p, p]),
         "sarlacc_dev_fastq_extract": (i, [p, p, p, p, p, p, p]),

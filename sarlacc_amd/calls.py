@@ -573,3 +573,38 @@ def find_errors(ref_align, read_align):
                                              ip, il, cap_i, C.byref(ni)))
     n = sl.value
     return ["".join(chr(c) for c in bases[:n])] + [c[:n] for c in cols] + [ip[:ni.value], il[:ni.value]]
+
+
+def _profile_fetch(R, n_ins, n_runs, n_obs):
+    """sarlacc_profile_fetch into arrays of the reported sizes: the raw profile of the call just made."""
+    counts = np.zeros((5, R), np.int32)
+    ip, il, im = np.zeros(max(n_ins, 1), np.int32), np.zeros(max(n_ins, 1), np.int32), np.zeros(max(n_ins, 1), np.int64)
+    rs, re_, rb = np.zeros(max(n_runs, 1), np.int32), np.zeros(max(n_runs, 1), np.int32), np.zeros(max(n_runs, 1), np.uint8)
+    orun, olen, om = np.zeros(max(n_obs, 1), np.int32), np.zeros(max(n_obs, 1), np.int32), np.zeros(max(n_obs, 1), np.int64)
+    check(_lib.lib().sarlacc_profile_fetch(counts if R else None, ip, il, im, n_ins, rs, re_, rb, n_runs, orun, olen, om, n_obs))
+    return {"counts": counts, "ins_pos": ip[:n_ins], "ins_len": il[:n_ins], "ins_mult": im[:n_ins],
+            "run_start": rs[:n_runs], "run_end": re_[:n_runs], "run_base": rb[:n_runs].tobytes().decode("latin-1"),
+            "obs_run": orun[:n_obs], "obs_len": olen[:n_obs], "obs_mult": om[:n_obs]}
+
+
+def profile_reads(seq, qual, encoding, gapopen, gapext, reference):
+    """sarlacc_profile_reads + sarlacc_profile_fetch: general_align of every read against `reference` and the reduction
+    of the alignments to the error and homopolymer profiles on the device (no `.Call` counterpart: the chain
+    general_align -> find_errors + match_homopolymers as histograms).  Returns the raw arrays: "score", "edit" (as
+    general_align), "counts" (int32 [5][R]: A, C, G, T, deletion), "ins_pos" / "ins_len" / "ins_mult" (distinct insertion
+    (0-based position of the next reference base, length) pairs, ascending, with their number of alignments), "run_start" /
+    "run_end" (1-based, inclusive) / "run_base" (the reference's homopolymers), "obs_run" / "obs_len" / "obs_mult" (distinct
+    (run index, observed length) pairs, ascending, with multiplicities)."""
+    rf = _string(reference, "reference sequence")
+    go = _numeric(gapopen, "gap opening penalty")
+    ge = _numeric(gapext, "gap extension penalty")
+    s, q = _seq_qual(seq, qual)
+    enc = as_encoding(encoding)
+    n = len(s)
+    scores, edits = np.zeros(n, np.float64), np.zeros(n, np.int32)
+    ni, nr, no = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(_lib.lib().sarlacc_profile_reads(s.chars, s.off, q.chars, q.off, n, enc.errors, enc.names, len(enc), go, ge, rf, len(rf),
+                                           scores, edits, C.byref(ni), C.byref(nr), C.byref(no)))
+    out = _profile_fetch(len(rf), ni.value, nr.value, no.value)
+    out["score"], out["edit"] = scores, edits
+    return out

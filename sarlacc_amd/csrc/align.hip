@@ -2211,8 +2211,8 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
 // (length mismatch is tested before each alignment, src/adaptor_align.cpp:51-53;
 // inside an alignment column 1 is evaluated first: its reference character, then
 // the qualities of every row, then the remaining reference characters).
-static int first_error(int64_t n, const int64_t* seq_off, const int64_t* qual_off, const char* ref, int R,
-                       int bad_qual_read) {
+int first_error(int64_t n, const int64_t* seq_off, const int64_t* qual_off, const char* ref, int R,
+                int bad_qual_read) {
     int64_t len_bad = -1;
     if (qual_off)
         for (int64_t i = 0; i < n; ++i)

@@ -1,5 +1,5 @@
-// align_host.hpp -- the host side of align.hip that align_panel.hip builds on: the cost table layout, the batch upload
-// and run_align itself (one reference against a batch, any length).
+// align_host.hpp -- the host side of align.hip that align_panel.hip builds on: the cost table layout, the batch upload,
+// run_align itself and its error order (one reference against a batch, any length).
 #pragma once
 
 #include "common.hpp"
@@ -47,5 +47,8 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
               int32_t max_len, const double* enc_errors, const char* enc_names, int enc_n, double gapopen, double gapext,
               const char* ref, int R, bool local, int kernel_mode, const int32_t* sec_starts, const int32_t* sec_ends, int nsec,
               const AlignOut& out, hipStream_t stream, int* bad_qual_read, const ChunkOpts& co = ChunkOpts());
+// The error the reference's loop over the reads would raise first (0: none), given the host offsets of the batch
+// (qual_off NULL: lengths agree) and the bad-quality read run_align reported.
+int first_error(int64_t n, const int64_t* seq_off, const int64_t* qual_off, const char* ref, int R, int bad_qual_read);
 
 }  // namespace sarlacc

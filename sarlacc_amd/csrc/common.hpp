@@ -69,6 +69,7 @@ enum Opt {
     OPT_MSA2_WIDE_EXTEND,     // spec v2: largest group size that takes the four-positions-per-lane extension kernel (default 12; A/B)
     OPT_ALIGN_LOCATE,         // adaptor_align: -1 the snapshot path instead of the integer locator fill + fp64 window (A/B); 1 every read on the redo list (tests)
     OPT_ALIGN_PANEL,          // barcode panel: -1 every barcode by run_align + the device fold instead of the fused kernel (A/B, cross-check)
+    OPT_PROFILE_CHUNK_READS,  // profile_reads: reads per chunk of the batch (0 = by the byte budget of the aligner's scratch; tests force several chunks)
     OPT_N
 };
 int option(Opt o);

@@ -643,6 +643,93 @@ def errorFinder(ref_aligned, read_aligned):
     return {"full": full, "transition": transition}
 
 
+# The profiling workflow in one call (vignettes/profiling.Rmd: align every read to its known reference, then
+# errorFinder + homopolymerMatcher), with the per-alignment lists of those two replaced by histograms: a pair of arrays
+# (lengths ascending, multiplicities).  foldLengths / expandLengths and foldProfile / expandProfile convert between the
+# two forms on the host; they need no device.
+def foldLengths(values):
+    """A list of lengths -> (distinct lengths ascending as int32, their multiplicities as int64)."""
+    lengths, mult = np.unique(np.asarray(values, dtype=np.int32), return_counts=True)
+    return lengths.astype(np.int32), mult.astype(np.int64)
+
+
+def expandLengths(hist):
+    """(lengths, multiplicities) -> the sorted list of lengths, each as often as its multiplicity says."""
+    lengths, mult = hist
+    order = np.argsort(np.asarray(lengths), kind="stable")
+    return np.repeat(np.asarray(lengths, dtype=np.int64)[order], np.asarray(mult, dtype=np.int64)[order]).tolist()
+
+
+def _map_profile(errors, homopolymers, f):
+    full = dict(errors["full"], insertion=[f(v) for v in errors["full"]["insertion"]])
+    return dict(errors, full=full), [dict(h, observed=f(h["observed"])) for h in homopolymers]
+
+
+def foldProfile(errors, homopolymers):
+    """What errorFinder and homopolymerMatcher return -> (errors, homopolymers) with `insertion` and `observed` as
+    histograms, the form profileReads returns."""
+    return _map_profile(errors, homopolymers, foldLengths)
+
+
+def expandProfile(errors, homopolymers):
+    """The inverse of foldProfile: histograms -> the sorted lists of errorFinder / homopolymerMatcher."""
+    return _map_profile(errors, homopolymers, expandLengths)
+
+
+def _profile_result(raw, n, reference, ref, gapOpening, gapExtension, expand):
+    R = len(ref)
+    counts = raw["counts"]
+    cut = np.searchsorted(raw["ins_pos"], np.arange(R + 2))
+    insertion = []
+    for p in range(R + 1):
+        lengths, mult = raw["ins_len"][cut[p]:cut[p + 1]], raw["ins_mult"][cut[p]:cut[p + 1]]
+        none = n - int(mult.sum())
+        if none > 0:   # alignments without an insertion there count as length 0
+            lengths, mult = np.concatenate([np.zeros(1, np.int32), lengths]), np.concatenate([np.array([none], np.int64), mult])
+        insertion.append((lengths, mult))
+    full = {"base": list(ref) + [None], "insertion": insertion}
+    for k, name in enumerate(("A", "C", "G", "T", "deletion")):
+        full[name] = counts[k].tolist() + [None]
+    barr = np.frombuffer(ref.encode(), dtype=np.uint8) if R else np.zeros(0, np.uint8)
+    transition = np.array([[int(counts[y][barr == ord(x)].sum()) for y in range(4)] for x in "ACGT"], dtype=np.int64)
+    ocut = np.searchsorted(raw["obs_run"], np.arange(len(raw["run_start"]) + 1))
+    homopolymers = [{"start": int(a), "end": int(b), "base": c, "observed": (raw["obs_len"][ocut[k]:ocut[k + 1]], raw["obs_mult"][ocut[k]:ocut[k + 1]])}
+                    for k, (a, b, c) in enumerate(zip(raw["run_start"], raw["run_end"], raw["run_base"]))]
+    errors = {"full": full, "transition": transition}
+    if expand:
+        errors, homopolymers = expandProfile(errors, homopolymers)
+    return {"errors": errors, "homopolymers": homopolymers, "score": raw["score"], "edit": raw["edit"],
+            "metadata": {"gapOpening": gapOpening, "gapExtension": gapExtension, "reference": reference}}
+
+
+def profileReads(reads, reference, gapOpening=5, gapExtension=1, expand=False, assignment=None):
+    """qualityAlign followed by errorFinder and homopolymerMatcher (R/qualityAlign.R:4-27, R/errorFinder.R:9-49,
+    R/homopolymerMatcher.R:9-36) as one device call on a Reads or a resident.DeviceReads: the alignment strings never
+    leave the device.  Returns {"errors": {"full", "transition"} as errorFinder, "homopolymers" as homopolymerMatcher,
+    "score", "edit", "metadata"}, where `insertion` (per position 0 .. R) and `observed` (per homopolymer) are
+    histograms (lengths, multiplicities) -- alignments without an insertion at a position count as length 0 -- or, with
+    expand=True, the sorted lists of the two generics, value for value.  With `assignment` (per read the index of its
+    reference in the list `reference`, -1 = skip; the `seqnames` of sam2ranges) the reads of each reference are
+    gathered on the device and one result per reference is returned."""
+    from .resident import DeviceReads
+    if assignment is not None:
+        dev = reads if isinstance(reads, DeviceReads) else DeviceReads.upload(reads)
+        assignment = np.asarray(assignment, dtype=np.int64)
+        if assignment.size != len(dev):
+            raise ValueError("'assignment' should have one entry per read")
+        out = []
+        for k, ref in enumerate(reference):
+            idx = np.flatnonzero(assignment == k)
+            out.append(profileReads(dev.realize(idx, np.zeros(idx.size, np.uint8)), ref, gapOpening, gapExtension, expand))
+        return out
+    ref = str(reference).upper()
+    if isinstance(reads, DeviceReads):
+        raw = reads.profile(ref, gapOpening, gapExtension)
+    else:
+        raw = calls.profile_reads(reads.seq, reads.qual, reads.encoding, gapOpening, gapExtension, ref)
+    return _profile_result(raw, len(reads), reference, ref, gapOpening, gapExtension, expand)
+
+
 # ---------------------------------------------------------------------------
 # sam2ranges (R/sam2ranges.R)
 

@@ -358,3 +358,21 @@ class DeviceReads:
             if d_all is not None:
                 check(_lib.lib().sarlacc_dev_download(matrix, d_all, 8 * n * nb))
         return (best, score, nxt, matrix[:nb * n].reshape(nb, n)) if all_scores else (best, score, nxt)
+
+    def profile(self, reference, gap_opening, gap_extension):
+        """calls.profile_reads on the resident batch (sarlacc_dev_profile_reads + sarlacc_profile_fetch): the same raw arrays;
+        only the scores, the edit distances and the reduced profile come back."""
+        from .calls import _numeric, _profile_fetch, _string
+        from .encoding import as_encoding
+        rf = _string(reference, "reference sequence")
+        go = _numeric(gap_opening, "gap opening penalty")
+        ge = _numeric(gap_extension, "gap extension penalty")
+        enc = as_encoding(self._encoding())
+        n = len(self)
+        d_scores, d_edits = DevBuffer(8 * max(n, 1)), DevBuffer(4 * max(n, 1))
+        ni, nr, no = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(_lib.lib().sarlacc_dev_profile_reads(self.seq, self.qual, self.off, n, self.max_len, enc.errors, enc.names, len(enc), go, ge,
+                                                   rf, len(rf), d_scores, d_edits, C.byref(ni), C.byref(nr), C.byref(no), None))
+        out = _profile_fetch(len(rf), ni.value, nr.value, no.value)
+        out["score"], out["edit"] = d_scores.to_numpy(np.float64, n), d_edits.to_numpy(np.int32, n)
+        return out
