@@ -446,7 +446,20 @@ int sarlacc_set_option(const char* name, int value);
  * gap_opening, R/multiReadAlign.R:47).  Groups: CSR of 1-based read ids.
  * Output: for group g, rows_g = size(g) strings of equal width width_out[g],
  * written row-major at out + out_off[g]; out_off has ngroups+1 entries.
- * Two-call protocol: out==NULL fills width_out/out_off only. */
+ * Two-call protocol: out==NULL fills width_out/out_off only.
+ * Scoring domain (also of sarlacc_msa_consensus and sarlacc_dev_msa_consensus; DESIGN.md
+ * section 5): the four scores are truncated toward zero to integers, and with S the largest
+ * magnitude among them and L the longest read that is a member of a group of the call,
+ *     S * (2 L + 2) < 2^27
+ * must hold -- otherwise the call fails ("sarlacc_amd: MSA scores outside the scoring domain
+ * ...", NaN and infinite scores included) before anything runs.  Inside the domain every
+ * pairwise score is exact in 32 bits and far from the kernels' "outside the band" value.
+ * Under MSA spec 2 a group whose weights max(match, mismatch, 1) do not fit the 16-bit
+ * library records or the 32-bit row and chain sums (group size n, longest read L,
+ * P = floor(n/2) ceil(n/2): (n-1) W <= 65535, P (n-1) W < 2^30, P (n-1) W L < 2^32) is aligned
+ * by spec 1 instead; sarlacc_stage_count("msa_v1_fallback_weights") counts them (never with
+ * match <= 1 and mismatch <= 1).  Which pairwise kernel took the pairs of the last call:
+ * sarlacc_stage_count("msa_pairs_bitvector" | "msa_pairs_packed" | "msa_pairs_int32"). */
 int sarlacc_quick_msa(const int64_t* grp_off, const int32_t* grp, int64_t ngroups,
                       const char* seq, const int64_t* seq_off, int64_t nseq,
                       double match, double mismatch, double gap_extension, double gap_opening,

@@ -352,12 +352,49 @@ def msa2_stats(reset=True):
     return dict(zip(MSA2_STAT_NAMES, buf.tolist()))
 
 
+MSA_SCORE_RANGE = 1 << 27
+
+
+def msa_check_scores(scores, longest):
+    """The scoring domain of the MSA stage: the scores, truncated toward zero, must satisfy
+    max |score| * (2 * longest + 2) < 2^27 with `longest` the longest read of the call's groups -- every finite cell of a
+    pairwise DP is then far enough from both sides' "outside the band" values (-2^28 plus finite terms in the 32-bit kernel,
+    the constant -2^29 in msa.c) that neither clamp decides a comparison, and the conversions to int are defined.
+    Returns the truncated scores, raises OracleError outside the domain."""
+    vals = []
+    for v in scores:
+        v = float(v)
+        if not abs(v) < MSA_SCORE_RANGE:   # (NaN and infinities too)
+            raise OracleError("MSA scores outside the scoring domain: %r" % (tuple(scores),))
+        vals.append(int(v))
+    if max(abs(v) for v in vals) * (2 * int(longest) + 2) >= MSA_SCORE_RANGE:
+        raise OracleError("MSA scores outside the scoring domain: max |score| * (2 * longest read + 2) must stay below 2^27 "
+                          "(scores %r, longest read %d)" % (tuple(vals), longest))
+    return vals
+
+
+def msa2_weights_fit(n, longest, match, mismatch):
+    """Spec v2's guard for weights other than 1: with W = max(match, mismatch, 1) as truncated
+    and P = floor(n / 2) * ceil(n / 2), a group of n reads (the longest of `longest` bases) is aligned by spec v2 only if
+    (n - 1) W <= 65 535 (16-bit weights of the library records), P (n - 1) W < 2^30 (32-bit row weights, doubled by the noise
+    filter) and P (n - 1) W longest <= 2^32 - 1 (32-bit chain sums); otherwise by spec v1.  Never false for W = 1."""
+    if n < 2:
+        return True
+    W = max(int(match), int(mismatch), 1)
+    P, rec = (n // 2) * ((n + 1) // 2), (n - 1) * W
+    return rec <= 65535 and P * rec < (1 << 30) and P * rec * int(longest) <= 0xFFFFFFFF
+
+
 def quick_msa(groupings, sequences, match, mismatch, gap_extension, gap_opening, bandwidth, spec=2, tcoffee_max=64, max_columns=65535):
     """Same argument order as the reference .Call (src/quick_msa.cpp:15): note that
     the R caller passes (-gapOpening, -gapExtension) into (gap_extension, gap_opening)
     (R/multiReadAlign.R:47, SURVEY App.B Q15).  spec 2 (default): consistency-based progressive
     alignment (msa2.c) for groups of up to `tcoffee_max` reads of at most 65 471 bases whose alignment has at most 65 535
-    columns, spec 1 (centre-star, msa.c) beyond that and when spec == 1 -- the same policy as the product."""
+    columns and whose weights fit their fields (msa2_weights_fit), spec 1 (centre-star, msa.c) beyond that and when
+    spec == 1 -- the same policy as the product.  Fractional scores are truncated toward zero; a call outside the scoring
+    domain (msa_check_scores, over the longest read of all groups) raises OracleError."""
+    longest_all = max([len(sequences[i - 1]) for g in groupings for i in g], default=0)
+    match, mismatch, gap_extension, gap_opening = msa_check_scores((match, mismatch, gap_extension, gap_opening), longest_all)
     out = []
     for g in groupings:
         reads = [sequences[i - 1] for i in g]
@@ -370,7 +407,7 @@ def quick_msa(groupings, sequences, match, mismatch, gap_extension, gap_opening,
         buf = np.zeros(cap, np.uint8)
         width = C.c_int64()
         longest = int(np.diff(so).max()) if m else 0
-        v2 = spec == 2 and m <= tcoffee_max and longest + 64 <= 65535
+        v2 = spec == 2 and m <= tcoffee_max and longest + 64 <= 65535 and msa2_weights_fit(m, longest, match, mismatch)
         fn = lib().orc_msa2_group if v2 else lib().orc_msa_group
         _check(fn(_p(sb), _p(so), C.c_int64(m), int(match), int(mismatch), int(gap_opening),
                   int(gap_extension), int(bandwidth), _p(buf), C.c_int64(cap), C.byref(width)))

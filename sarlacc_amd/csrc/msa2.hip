@@ -33,6 +33,7 @@
 // A row keeps the first M2_CAP distinct partner columns (spec v2, step 5); groups whose profiles outgrow the
 // fast capacity are redone with profiles as wide as the sum of the read lengths.
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -2056,12 +2057,66 @@ __global__ void k_rows_copy(const uint8_t* src, const long long* src_off, uint8_
     for (long long k = threadIdx.x; k < n; k += blockDim.x) d[k] = s[k];
 }
 
+// Scoring domain of the MSA stage (oracle/oracle.py msa_check_scores states the same rule).  The four
+// scores are truncated toward zero to integers.  With S the largest magnitude among them and L the longest read of the call's
+// groups, the call is accepted when  S * (2 L + 2) < 2^27:
+//   * every finite cell of a pairwise DP is a sum of at most lr + lc <= 2 L scores, so |H|, |E|, |F| <= S (lr + lc);
+//   * the 32-bit kernel (msa_pairwise.hip) stands for "outside the band" by MSA_NEG = -2^28 PLUS what the recurrence adds to it
+//     (a cell beyond the band edge holds a finite value of that size, one penalty is added on the way in), i.e. at most
+//     -2^28 + S (lr + lc + 2).  That has to stay below every finite candidate, which is at least -S (lr + lc + 2):
+//     2 S (lr + lc + 2) < 2^28.  The CPU statement's "outside" is the constant INT_MIN / 4 = -2^29, never added to: the looser of
+//     the two, so the kernel's bound decides;
+//   * no 32-bit sum overflows (2^28 + 2^28 + 2^27 < 2^31), and |score| < 2^27 makes the conversion from double defined
+//     (NaN and infinities fail the comparison and are rejected with the rest).
+static int msa_check_scores(double match, double mismatch, double gap_extension, double gap_opening, int64_t longest) {
+    const double lim = 134217728.0;   // 2^27
+    long long smax = 0;
+    for (const double v : {match, mismatch, gap_extension, gap_opening}) {
+        if (!(std::fabs(v) < lim)) { smax = 1LL << 27; break; }
+        smax = std::max(smax, std::llabs(static_cast<long long>(v)));
+    }
+    if (smax * (2 * static_cast<long long>(longest) + 2) >= (1LL << 27))
+        return fail("sarlacc_amd: MSA scores outside the scoring domain: max |score| * (2 * longest read + 2) must stay below 2^27 "
+                    "(scores %g %g %g %g, longest read %lld)", match, mismatch, gap_extension, gap_opening, static_cast<long long>(longest));
+    return 0;
+}
+
+// Spec v2 with weights other than 1: does a group of n reads, the longest of `longest` bases, under
+// the largest primary weight W = max(match, mismatch, 1) fit the fields its weights are kept in?  With P = floor(n/2) ceil(n/2),
+// the most member pairs (a, b) a join of two profiles can have:
+//   * a library record of (a, p, b) sums the direct weight and one triplet per third read, (n - 1) W at most, into the 16 bits
+//     of its slot (k_m2_extend: w0 | others << 16, wk | qk << 16):                               (n - 1) W <= 65 535;
+//   * a row entry sums one slot of the record of every member pair, P (n - 1) W at most, in a 32-bit int that the noise
+//     filter doubles (2 w >= heaviest):                                                          P (n - 1) W < 2^30
+//     (implied by the first bound, 1 024 * 65 535 < 2^30; stated because the field is a different one);
+//   * a chain sums row entries in 32 unsigned bits ((f << 32) | ~id).  Every position p of a member a lies in ONE column of the
+//     first child, hence in at most one match of a chain, where the pair (a, b) adds one slot of its record:
+//                                                                                         P (n - 1) W longest <= 2^32 - 1.
+// With W = 1 all three hold for every group spec v2 takes (n <= 64, longest <= 65 471: 1 024 * 63 * 65 471 < 2^32), so the
+// unit-weight path never sees the guard act.
+static bool m2_weights_fit(long long n, long long longest, long long W) {
+    if (n < 2) return true;
+    const long long P = (n / 2) * ((n + 1) / 2), rec = (n - 1) * W;
+    if (rec > 65535) return false;
+    return P * rec < (1LL << 30) && P * rec * longest <= 0xFFFFFFFFLL;
+}
+
 // The MSA stage of quick_msa: spec v2 for groups of up to M2_MAXN reads whose profiles fit 65535 columns,
 // spec v1 (msa.hip) for the rest and when spec 1 is selected (sarlacc_set_msa_spec / SARLACC_MSA_SPEC=1).
 int msa_run(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const char* seq, const int64_t* seq_off,
             int64_t nseq, double match, double mismatch, double gap_extension, double gap_opening, int bandwidth,
             bool want_rows, int64_t out_cap, MsaResult* res, const std::function<int()>* overlap,
             const uint8_t* d_seq_resident) {
+    {   // the scoring domain, on every route into the stage (both specs, rows or fused, host or resident reads)
+        int64_t longest = 0;
+        for (int64_t k = grp_off[0]; k < grp_off[ngroups]; ++k)
+            if (grp[k] >= 1 && grp[k] <= nseq) longest = std::max<int64_t>(longest, seq_off[grp[k]] - seq_off[grp[k] - 1]);
+        SL_TRY(msa_check_scores(match, mismatch, gap_extension, gap_opening, longest));
+        Context& c0 = ctx();
+        for (const char* nm : {"msa_pairs_bitvector", "msa_pairs_packed", "msa_pairs_packed_linear", "msa_pairs_int32", "msa_pairs_packed_c4", "msa_pairs_packed_c8",
+                               "msa_pairs_packed_c16", "msa_pairs_int32_c4", "msa_pairs_int32_c8", "msa_pairs_int32_c16", "msa_v1_fallback_weights"})
+            c0.counts[nm] = 0;
+    }
     if (msa_spec() == 1)
         return msa1_run(grp_off, grp, ngroups, seq, seq_off, nseq, match, mismatch, gap_extension, gap_opening, bandwidth, want_rows,
                         out_cap, res, overlap, d_seq_resident);
@@ -2080,6 +2135,8 @@ int msa_run(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const c
     for (int64_t i = 0; i <= nseq; ++i) rel[i] = (nseq ? seq_off[i] : 0) - (nseq ? seq_off[0] : 0);
     // which groups does spec v2 take
     std::vector<int64_t> v2, v1;
+    const long long wmax = std::max(1LL, std::max(static_cast<long long>(match), static_cast<long long>(mismatch)));   // as truncated
+    double diverted_weights = 0;
     for (int64_t g = 0; g < ngroups; ++g) {
         const int64_t n = grp_off[g + 1] - grp_off[g];
         int64_t mx = 0;
@@ -2087,8 +2144,13 @@ int msa_run(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const c
         if (mx > 60000) return fail("sarlacc_amd: reads longer than 60000 bases are not supported by the MSA stage");
         // spec v2: up to M2_MAXN reads, each short enough for 16-bit positions (a profile that outgrows 65 535 COLUMNS sends its group
         // to spec v1 afterwards: msa2_core's gave_up)
-        if (n <= M2_MAXN && mx + 64 <= 65535) v2.push_back(g); else v1.push_back(g);
+        // ... and with weights that fit the fields of the library records, the rows and the chain (m2_weights_fit)
+        const bool v2_shape = n <= M2_MAXN && mx + 64 <= 65535;
+        const bool fit = !v2_shape || m2_weights_fit(n, mx, wmax);
+        if (!fit) diverted_weights += 1;
+        if (v2_shape && fit) v2.push_back(g); else v1.push_back(g);
     }
+    ctx().counts["msa_v1_fallback_weights"] = diverted_weights;
     SL_TRY(ensure_device());
     Context& c = ctx();
     hipStream_t s = nullptr;

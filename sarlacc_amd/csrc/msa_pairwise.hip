@@ -1333,6 +1333,16 @@ int msa_pairwise_launch(const MsaJob* jobs, size_t njobs, const MsaJob* d_jobs, 
         if (!one_class) SL_TRY(upload(ord_name[cls], order[cls].data(), order[cls].size(), &d_order, s));
         a.order = d_order; a.njobs = static_cast<int>(cls_n[cls]);
         a.tb = d_tb; a.tb_per_wave = per_wave;
+        // which kernel took the pairs of this class (msa_run resets the counters): the totals, the packed kernel's
+        // linear-gap variant (launch_pk) and one counter per kernel and cells-per-lane instantiation
+        {
+            const double np = static_cast<double>(cls_n[cls]);
+            static const char* const by_c[2][3] = {{"msa_pairs_int32_c4", "msa_pairs_int32_c8", "msa_pairs_int32_c16"},
+                                                   {"msa_pairs_packed_c4", "msa_pairs_packed_c8", "msa_pairs_packed_c16"}};
+            c.counts[packed ? "msa_pairs_packed" : "msa_pairs_int32"] += np;
+            c.counts[by_c[packed ? 1 : 0][cls]] += np;
+            if (packed && a.go <= a.ge && !option(OPT_MSA_AFFINE)) c.counts["msa_pairs_packed_linear"] += np;
+        }
         if (out_mode == 0) SL_TRY(launch_class<0>(packed, C, a, static_cast<int>(grid), lds, s));
         else SL_TRY(launch_class<1>(packed, C, a, static_cast<int>(grid), lds, s));
     }

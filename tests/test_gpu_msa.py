@@ -531,9 +531,8 @@ def test_pairwise_bitvector_spec_v1_outputs(oracle):
     try:
         for bw in (100, 10):
             params = (0, -1, -5, -1, bw)
-            before = _lib.stage_count("msa_pairs_bitvector")
             got = calls.quick_msa(groups, reads, *params)
-            assert _lib.stage_count("msa_pairs_bitvector") > before
+            assert _lib.stage_count("msa_pairs_bitvector") > 0   # (of this call: msa_run resets the counter under either spec)
             assert got == oracle.quick_msa(groups, reads, *params, spec=1), bw
             calls.set_option("msa_bitvector", -1)
             try:

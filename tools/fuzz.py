@@ -200,6 +200,11 @@ def case_consensus(rng):
         assert g[0] == list(o[0]) and g[1] == list(o[1]), "consensus basic"
 
 
+# scorings beyond the unit-like ones (tests/test_gpu_msa_scores.py): the packed kernel with doubled costs and near its spread
+# bound, the 32-bit kernel for scores outside the cost domain, a call that mixes the two over its band classes
+MSA_OTHER_SCORES = [(5, -4, -6, -8), (0, -4, -6, -8), (0, -20, -20, -20), (1, 2, -3, -3), (0, -5000, -5000, -5000)]
+
+
 def case_msa(rng):
     from sarlacc_amd.mock import NUC, mutate
     reads, groups = [], []
@@ -231,10 +236,11 @@ def case_msa(rng):
     if rng.random() < 0.15 and groups and groups[0]:     # a length outlier and a huge bandwidth: the band cap of the spec
         k = groups[0][0] - 1
         reads[k] = reads[k] + mutate(NUC[rng.integers(0, 4, int(rng.choice([300, 1100, 1500])))], rng, 0.0, 0.0).tobytes().decode()
-    params = [(0, -1, -5, -1), (0, -1, -1, -5), (1, -2, -2, -2), (2, -3, -1, -4), (0, -1, -1, -1)][int(rng.integers(0, 5))]
+    params = [(0, -1, -5, -1), (0, -1, -1, -5), (1, -2, -2, -2), (2, -3, -1, -4), (0, -1, -1, -1)] + MSA_OTHER_SCORES
+    params = params[int(rng.integers(0, len(params)))]
     bw = int(rng.choice([0, 3, 20, 100, 180, 600, 5000]))
     spec = int(rng.choice([1, 2, 2, 2]))
-    opts = [o for o in ("msa2_general_rows", "msa2_chain_hbm", "msa2_single_wave", "msa2_batches", "msa2_simple_extend", "msa2_wide_extend") if rng.random() < 0.15]   # the other code paths of spec v2
+    opts = [o for o in ("msa2_general_rows", "msa2_chain_hbm", "msa2_single_wave", "msa2_batches", "msa2_simple_extend", "msa2_wide_extend", "msa_int32") if rng.random() < 0.15]   # the other code paths of spec v2
     calls.set_msa_spec(spec)
     for o_ in opts:
         calls.set_option(o_, 3 if o_ == "msa2_batches" else (64 if o_ == "msa2_wide_extend" else 1))   # (msa2_wide_extend = 64: the four-positions kernel for every group size)
@@ -342,7 +348,8 @@ def case_fused(rng):
     quals = [rqual(rng, len(r), 40, 90) for r in reads]
     if rng.random() < 0.05 and quals[0]:   # a quality below the encoding: the reference's error
         quals[0] = " " + quals[0][1:]
-    params = [(0, -1, -5, -1), (0, -1, -1, -5), (1, -2, -2, -2)][int(rng.integers(0, 3))]
+    params = [(0, -1, -5, -1), (0, -1, -1, -5), (1, -2, -2, -2)] + MSA_OTHER_SCORES
+    params = params[int(rng.integers(0, len(params)))]
     bw = int(rng.choice([3, 20, 100]))
     cov = float(rng.choice([0.0, 0.5, 0.6, 1.0]))
     goff, gvals = csr_from_lists(groups)
@@ -542,7 +549,8 @@ def case_fused_enc(rng):
     if rng.random() < 0.3:
         reads = ["".join("N" if rng.random() < 0.03 else c for c in r) for r in reads]
     quals = [tqual(rng, t, len(r), 0.003) for r in reads]
-    params = [(0, -1, -5, -1), (0, -1, -1, -5), (1, -2, -2, -2)][int(rng.integers(0, 3))]
+    params = [(0, -1, -5, -1), (0, -1, -1, -5), (1, -2, -2, -2)] + MSA_OTHER_SCORES
+    params = params[int(rng.integers(0, len(params)))]
     bw = int(rng.choice([3, 20, 100]))
     cov = float(rng.choice([0.0, 0.5, 0.6, 1.0]))
     spec = int(rng.choice([1, 2, 2]))
