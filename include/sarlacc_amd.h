@@ -434,7 +434,9 @@ int sarlacc_set_msa_spec(int spec);
  *   "msa2_budget_gb" (GB a batch of groups may take), "msa2_max_columns" (a lower ceiling of spec v2's profiles),
  *   "msa2_simple_extend" (the extended library by the one-position-per-lane kernel everywhere), "msa2_wide_extend" (largest
  *   group size of the four-positions-per-lane kernel), "align_locate" (adaptor_align: -1 the snapshot path alone, 1 every read
- *   through the locator's redo list; sarlacc_stage_count "align_redo" / "align_stalls" report the last such call),
+ *   through the locator's redo list, 2 the locator outside its extension-free frame, 3 the same at the frame's scale;
+ *   sarlacc_stage_count "align_redo" / "align_stalls" / "align_locate_k" (the locator's scale 2^k, negative outside the
+ *   frame, 0 without a locator) report the last such call),
  *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel),
  *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a

@@ -88,7 +88,8 @@ struct AlignArgs {
     // MODE 4 (integer locator fill + fp64 window, see LOC_NEG) and its redo launch
     const int* loc_tab;                // integer cost table: the rows of `tables` scaled by 2^k and rounded, int32 (addressed by colbase / 2)
     const int* loc_rz;                 // [R+1] integer row 0
-    int loc_GO, loc_GE, loc_D;         // penalties in integer units; candidate margin D
+    int loc_GO, loc_GE, loc_D;         // penalties in integer units (framed: loc_GO is the opening GO - GE); candidate margin D
+    int loc_framed;                    // the locator runs in the extension-free frame (MODE 6 instead of MODE 5)
     int loc_force;                     // testing: every read goes on the redo list
     double loc_unit, loc_slack, loc_top;  // 2^-k; Delta_int + eps_fp; sum+ smax + max(0, row 0) + 1 (window certificate)
     int* loc_redo;                     // [0] reads on the redo list, [2 ...] their indices (reset per launch)
@@ -208,15 +209,30 @@ static inline int snap_win(int R, int W) { return (SNAP_P + snap_head(R) + W + 7
 //     hit) or whose walk stalls goes on a device-side list, which the MODE 3 kernel then aligns (read_list).
 // Pass 1 runs as a kernel of its own (MODE 5: int32 state only, no walk, a third of the LDS) and hands {I_max, lo, hi} per
 // read to the window kernel (MODE 4) through HBM (12 B per read).
+// MODE 6 is MODE 5 in the frame I'(i, c) = I(i, c) + GE (i + c) (row 0, column 0 and the jump scores shifted alike), where
+// both gap extensions cost 0, an opening costs GO - GE (in column R of local mode every vertical step "costs" -GE) and the
+// diagonal move gains 2 GE, folded into the table by the host.  The map is a bijection per cell, so every comparison
+// between candidates of one cell comes out as in MODE 5 and the two modes compute the same cells.  Column R's tests
+// compare values of different rows of one block: the difference of their frames is a constant folded into D.  The
+// frame grows by GE 2^k per row, so the host picks k from the longest read as well (plan_locate) and falls back to MODE 5
+// where no k >= LOC_FRAME_KMIN fits.
 constexpr int LOC_NEG = -(1 << 29);   // -inf of the integer DP (and of its table entries); cells stay above -2^27
-// resident wavefronts per SIMD of the locator kernel: at 4 it takes 110 VGPRs and spills nothing (at 6 and 8 its steady
-// state reloads spilled registers from scratch)
+// -inf of a framed table entry.  Framed cells and intermediates lie in (-2^27, 2^30] (plan_locate), so diag' + LOC_NEG_FRAMED
+// neither leaves int32 nor passes a real cell: cell (i, c) is at least the horizontal path from column 0,
+// H' >= -GO - GE (c - 1) - (R + 1) / 2 + GE (i + c), and diag' <= bpos + (R + 1) / 2 + GE (i + c - 2), so
+// diag' + LOC_NEG_FRAMED < H' follows from bpos + GO + GE (c - 3) + (R + 1) < 2^30, which the range rule guarantees (all in
+// units of 2^-k).
+constexpr int LOC_NEG_FRAMED = -(1 << 30);
+constexpr int LOC_FRAME_KMIN = 8;
+// resident wavefronts per SIMD of the locator kernel: at 4 it takes 113 VGPRs (114 in the frame) and spills nothing (at 6
+// and 8 its steady state reloads spilled registers from scratch)
 constexpr int LOC_WAVES = 4;
 
 // MODE 0: scores only.  MODE 1: scores + reference->read map (adaptor_align), codes streamed.
 // MODE 2: scores + gapped strings + edit distance (general_align).
 // MODE 3: as MODE 1 by snapshots + windowed recompute (LOCAL, !PENSEL only; see SNAP_P).
 // MODE 4: as MODE 3 by an integer locator fill + one fp64 window (ROWF 2 only; see LOC_NEG).
+// MODE 5 / 6: the locator fill of MODE 4 as a kernel of its own, plain / in the extension-free frame.
 // LOCAL: free leading read bases + free vertical gaps in the last column (adaptor mode).
 // ROWF: 0 alignments of any width, wave-wide shifts; 1 alignments are 16 lanes wide and start on DPP row
 // boundaries; 2 alignments are 8 lanes wide, two interleaved per DPP row (see lane_shr1).
@@ -236,7 +252,7 @@ constexpr int LOC_WAVES = 4;
 template <int K, int MODE, bool LOCAL, int ROWF, int KLAST, bool PENSEL>
 // (six wavefronts per SIMD for the snapshot mode; five with eight alignments per wavefront: four columns per lane need the registers --
 // at six the recompute code spilled -- 2 182 -> 2 213 GCUPS on the same box)
-__global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 3 && ROWF != 2) ? 6 : 5) k_align(const AlignArgs A) {
+__global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 3 && ROWF != 2) ? 6 : 5) k_align(const AlignArgs A) {
     constexpr bool ROW16 = ROWF != 0;                      // leaders keep their column-0 inputs through the DPP fill operand
     constexpr int NG = ROWF == 2 ? NGMAX2 : NGMAX;         // alignments per wavefront at most
     // uint16 entries per alignment's ring slot: 512 B slots let a ring address be base | offset; with eight
@@ -273,9 +289,10 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
     static_assert(MODE < 4 || (ROWF == 2 && LOCAL && !PENSEL), "the locator runs the interleaved local shape only");
     // the redo launch after a locator pass with an empty list: nothing to stage
     if (A.read_list && A.read_list[0] == 0) return;
-    // MODE 5: the integer table (4-byte entries, rows half as long) in place of the fp64 one
+    // MODE 5 / 6: the integer table (4-byte entries, rows half as long) in place of the fp64 one
+    constexpr bool LOCATOR = MODE >= 5, FRAMED = MODE == 6;
     int* const s_tabi = reinterpret_cast<int*>(smem + RING_BYTES);
-    if (MODE == 5)
+    if (LOCATOR)
         for (int x = threadIdx.x; x < A.tab_doubles; x += 64 * NWAVES) s_tabi[x] = A.loc_tab[x];
     else
         for (int x = threadIdx.x; x < A.tab_doubles; x += 64 * NWAVES) s_tab[x] = A.tables[x];
@@ -297,10 +314,13 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
         vgo[k] = last ? 0.0 : GO;
         vge[k] = last ? 0.0 : GE;
         rz[k] = A.rowzero[cc];
-        if (MODE == 5) {
+        if (LOCATOR) {
             colbi[k] = lds0 + RING_BYTES + static_cast<int>(A.colbase[cc] >> 1);
-            vgoi[k] = last ? 0 : A.loc_GO;
-            vgei[k] = last ? 0 : A.loc_GE;
+            // framed: loc_GO is the opening GO - GE and an extension is free; the free vertical step of column R gains GE.
+            // Column R's jump score is the running maximum of the rows above, never more than the cell just above, so its
+            // "extension" may cost anything that keeps it there: 0, the constant of the other columns
+            vgoi[k] = last ? (FRAMED ? -A.loc_GE : 0) : A.loc_GO;
+            vgei[k] = FRAMED ? 0 : last ? 0 : A.loc_GE;
             rzi[k] = A.loc_rz[cc];
         }
     }
@@ -412,7 +432,10 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
                 bad = bad || (r + e < slen && qi < 0);
                 qi = qi < 0 ? 0 : (qi >= A.navail ? A.navail - 1 : qi);
                 const uint32_t code = ((v.b >> (8 + e)) & 1u) ? 4u : ((v.b >> (2 * e)) & 3u);
-                ent[e] = (r + e < slen) ? code * static_cast<uint32_t>(A.row_bytes) + static_cast<uint32_t>(qi << 3) : 0u;
+                // the locator's ring is its own: it stages offsets into the int32 rows, half of an fp64 row offset
+                const uint32_t at = LOCATOR ? code * static_cast<uint32_t>(A.row_bytes >> 1) + static_cast<uint32_t>(qi << 2)
+                                            : code * static_cast<uint32_t>(A.row_bytes) + static_cast<uint32_t>(qi << 3);
+                ent[e] = (r + e < slen) ? at : 0u;
             }
             if (bad && !A.read_list) atomicMin(A.badqual, A.read_base + static_cast<int>(item * A.ngroups + sg));
             const uint2 w = make_uint2(ent[0] | (ent[1] << 16), ent[2] | (ent[3] << 16));
@@ -631,14 +654,19 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
                 loc_lo = A.loc_out[3 * read + 1];
                 loc_hi = A.loc_out[3 * read + 2];
             }
-        } else if constexpr (MODE == 5) {
-            int Si[K], UJi[K];
+        } else if constexpr (LOCATOR) {
+            // Sg: Si less the column's vertical opening, carried beside it across blocks (Si itself is the next diagonal)
+            int Si[K], Sg[K], UJi[K];
 #pragma unroll
-            for (int k = 0; k < K; ++k) { Si[k] = rzi[k]; UJi[k] = LOC_NEG; }
+            for (int k = 0; k < K; ++k) { Si[k] = rzi[k]; Sg[k] = rzi[k] - vgoi[k]; UJi[k] = LOC_NEG; }
             int si_in = 0, lji_in = LOC_NEG, di_prev = A.loc_rz[c0 - 1 <= R ? c0 - 1 : R];
             const int GOi = A.loc_GO, GEi = A.loc_GE, D = A.loc_D;
+            // framed: a block's last row lies UNR - 1 rows, that many GE, above its first in the frame
+            const int D_lo = FRAMED ? D + (UNR - 1) * GEi : D;
             auto run_loc = [&](auto guard_tag, int t_begin, int t_end) {
                 constexpr bool GUARD = decltype(guard_tag)::value;
+                constexpr int NO_ROW = -0x7fffffff - 1;
+                int hi_blk = NO_ROW;   // steady state: first row of the last block that sets loc_hi (the row loc_lo takes too)
                 for (int t0 = t_begin; t0 < t_end; t0 += UNR) {
                     if ((t0 & 63) == 0) {
                         int t0s = t0;
@@ -651,6 +679,12 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
                     }
                     int s_before = 0, xacc = LOC_NEG;   // column R before the block; max of X over the block
                     const uint32_t ring_blk = static_cast<uint32_t>(ring_g + (x2 & 0xff));
+                    // staged entries are byte offsets into the int32 rows; the steady state reads a block's entries up front
+                    int rdv[UNR];
+                    if (!GUARD) {
+#pragma unroll
+                        for (int u = 0; u < UNR; ++u) rdv[u] = static_cast<int>(*reinterpret_cast<lds_cu16*>(ring_blk + 2u * u));
+                    }
 #pragma unroll
                     for (int u = 0; u < UNR; ++u) {
                         int left = si_in, lj = lji_in;
@@ -658,15 +692,15 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
                         bool act = true;
                         if (GUARD) act = x2 >= 0 && x2 <= x2max;
                         if (act) {
-                            // staged entries are byte offsets into the fp64 rows: half of one addresses the int32 rows
-                            const int rd = static_cast<int>(*reinterpret_cast<lds_cu16*>(ring_blk + 2u * u)) >> 1;
+                            const int rd = GUARD ? static_cast<int>(*reinterpret_cast<lds_cu16*>(ring_blk + 2u * u)) : rdv[u];
                             int diag = di_prev;
                             di_prev = si_in;
+                            int lg = si_in - GOi;   // the cell to the left less the opening
 #pragma unroll
                             for (int k = 0; k < K; ++k) {
-                                const int H = max(lj - GEi, left - GOi);
+                                const int H = max(FRAMED ? lj : lj - GEi, lg);
                                 lj = H;
-                                const int V = max(UJi[k] - vgei[k], Si[k] - vgoi[k]);
+                                const int V = max(UJi[k] - vgei[k], Sg[k]);
                                 UJi[k] = V;
                                 const int M = diag + *reinterpret_cast<lds_cint*>(static_cast<uint32_t>(colbi[k] + rd));
                                 diag = Si[k];
@@ -674,6 +708,9 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
                                 const int best = max(X, V);
                                 Si[k] = best;
                                 left = best;
+                                // one subtraction serves the next column of this row and this column of the next row
+                                lg = best - GOi;
+                                Sg[k] = (KLAST >= 0 && k != KLAST) ? lg : best - vgoi[k];
                                 const bool is_last = KLAST >= 0 ? (k == KLAST) : (k == klast);
                                 if (is_last) {
                                     // V is column R's running maximum before this row (free vertical gaps)
@@ -682,20 +719,24 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
                                         if (X + D >= best) loc_hi = x2;
                                     } else {
                                         if (u == 0) s_before = V;
-                                        xacc = max(xacc, X);
+                                        xacc = u == 0 ? X : max(xacc, FRAMED ? X - u * GEi : X);   // in the frame of the block's first row
                                         if (u == UNR - 1) {
-                                            loc_lo = sel32(loc_lo, x2 - 2 * (UNR - 1), __builtin_amdgcn_ballot_w64(best - D > s_before));
-                                            loc_hi = sel32(loc_hi, x2, __builtin_amdgcn_ballot_w64(xacc + D >= best));
+                                            const int bd = best - D_lo, xb = x2 - 2 * (UNR - 1);
+                                            loc_lo = sel32(loc_lo, xb, __builtin_amdgcn_ballot_w64(bd > s_before));
+                                            hi_blk = sel32(hi_blk, xb, __builtin_amdgcn_ballot_w64(xacc >= bd));
                                         }
                                     }
                                 }
                             }
                         }
-                        si_in = GUARD ? lane_shr1<ROWF>(left, si_in) : lane_shr1<ROWF>(left, s_two_back);
+                        // framed: column 0, which the leaders keep, is GE i; the register of two steps back holds GE (i - 1)
+                        if (FRAMED) si_in = GUARD ? lane_shr1<ROWF>(left, GEi * ((x2 >> 1) + 2)) : lane_shr1<ROWF>(left, s_two_back + 2 * GEi);
+                        else si_in = GUARD ? lane_shr1<ROWF>(left, si_in) : lane_shr1<ROWF>(left, s_two_back);
                         lji_in = lane_shr1<ROWF>(lj, lji_in);
                         x2 += 2;
                     }
                 }
+                if (!GUARD && hi_blk != NO_ROW) loc_hi = hi_blk + 2 * (UNR - 1);
             };
             run_loc(Flag<true>{}, 0, t_a);
             run_loc(Flag<false>{}, t_a, t_b);
@@ -703,6 +744,7 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE == 5 ? LOC_WAVES : (MODE == 
             loc_max = Si[0];
 #pragma unroll
             for (int k = 1; k < K; ++k) loc_max = (k == klast) ? Si[k] : loc_max;
+            if (FRAMED) loc_max -= GEi * (L + R);   // out of the frame: column R's last row is the read's last
             if (valid && j == jlast) {
                 A.loc_out[3 * read] = loc_max;
                 A.loc_out[3 * read + 1] = loc_lo;
@@ -1787,9 +1829,10 @@ struct LocPlan {
     std::vector<int> tab, rz;
     int k = 0, GO = 0, GE = 0, D = 0;
     double unit = 0, slack = 0, top = 0;
+    bool framed = false;   // tab, rz and GO are those of the extension-free frame (MODE 6)
 };
 static bool plan_locate(const std::vector<double>& rows, const std::vector<uint32_t>& colbase, int n, int R, double GO,
-                        double GE, const std::vector<double>& rowzero, int64_t max_len, LocPlan& p) {
+                        double GE, const std::vector<double>& rowzero, int64_t max_len, int frame, LocPlan& p) {
     if (!(GE > 0) || !(GO >= GE) || !std::isfinite(GO) || R < 1) return false;
     double splus = 0, wmax = 0;   // sum over columns of max(0, largest entry); largest finite |entry|
     for (double v : rows) {
@@ -1818,8 +1861,22 @@ static bool plan_locate(const std::vector<double>& rows, const std::vector<uint3
     int k = 24;
     while (k > 0 && (bmag + GE) * std::ldexp(1.0, k) + 2.0 * (R + 4) > std::ldexp(1.0, 27)) --k;
     if ((bmag + GE) * std::ldexp(1.0, k) + 2.0 * (R + 4) > std::ldexp(1.0, 27)) return false;
-    const double go = std::ldexp(GO, k), ge = std::ldexp(GE, k);
+    double go = std::ldexp(GO, k), ge = std::ldexp(GE, k);
     if (go != std::floor(go) || ge != std::floor(ge)) return false;   // not dyadic at this k: nor at any smaller one
+    // The extension-free frame (MODE 6) adds GE 2^k (i + c) to cell (i, c): the largest k <= the one above whose framed
+    // values and intermediates stay within 2^30, (bmag + GE (max_len + R + 2)) 2^k + 2 (R + 4) <= 2^30.  Un-framed values
+    // stay above -2^27 as before (k only shrinks) and the frame adds nothing negative, so LOC_NEG keeps its place below
+    // them.  The penalties must stay integers at that k; below LOC_FRAME_KMIN the un-framed locator runs at the k above.
+    // frame: 1 as above, 0 never, 2 the un-framed locator at the frame's k (A/B of the frame alone)
+    if (frame) {
+        int kf = k;
+        while (kf >= LOC_FRAME_KMIN && (bmag + GE * lenx) * std::ldexp(1.0, kf) + 2.0 * (R + 4) > std::ldexp(1.0, 30)) --kf;
+        const double gof = std::ldexp(GO, kf), gef = std::ldexp(GE, kf);
+        if (kf >= LOC_FRAME_KMIN && gof == std::floor(gof) && gef == std::floor(gef)) {
+            p.framed = frame == 1;
+            k = kf; go = gof; ge = gef;
+        }
+    }
     p.k = k;
     p.GO = static_cast<int>(go);
     p.GE = static_cast<int>(ge);
@@ -1828,6 +1885,11 @@ static bool plan_locate(const std::vector<double>& rows, const std::vector<uint3
         p.tab[x] = std::isfinite(rows[x]) ? static_cast<int>(std::nearbyint(std::ldexp(rows[x], k))) : LOC_NEG;
     p.rz.resize(rowzero.size());
     for (size_t x = 0; x < rowzero.size(); ++x) p.rz[x] = static_cast<int>(std::nearbyint(std::ldexp(rowzero[x], k)));
+    if (p.framed) {   // a diagonal move crosses two anti-diagonals of the frame, an opening pays GO - GE, row 0 is GE c up
+        for (int& v : p.tab) v = v == LOC_NEG ? LOC_NEG_FRAMED : v + 2 * p.GE;
+        for (size_t x = 0; x < p.rz.size(); ++x) p.rz[x] += p.GE * static_cast<int>(x);
+        p.GO -= p.GE;
+    }
     p.D = (R + 1) + static_cast<int>(std::ceil(2.0 * eps * std::ldexp(1.0, k))) + 1;
     p.unit = std::ldexp(1.0, -k);
     p.slack = (R + 1) * std::ldexp(1.0, -(k + 1)) + eps;
@@ -1889,7 +1951,8 @@ static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStre
         // the locator (its LDS: rings + the integer table), the windows, then the snapshot kernel on the reads the windows
         // put on their list (count read on the device)
         const size_t lds5 = sizeof(uint16_t) * NWAVES * NGMAX2 * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
-        hipLaunchKernelGGL((k_align<K, 5, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
+        if (a.loc_framed) hipLaunchKernelGGL((k_align<K, 6, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
+        else hipLaunchKernelGGL((k_align<K, 5, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
         hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
         AlignArgs r = a;
         r.read_list = a.loc_redo;
@@ -2121,10 +2184,12 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
                          nsnap * (2 * sh.K + 3) * 64 * (sizeof(double) / word_bytes);
     }
     // ... and, where eligible, by the integer locator + one fp64 window, the snapshot kernel redoing the reads it
-    // cannot certify (same tiles).  align_locate = -1: the snapshot path alone (A/B)
+    // cannot certify (same tiles).  align_locate = -1: the snapshot path alone (A/B); 2: the un-framed locator, 3: the same
+    // at the frame's k (A/B)
     LocPlan lp;
+    const int loc_frame = option(OPT_ALIGN_LOCATE) == 2 ? 0 : option(OPT_ALIGN_LOCATE) == 3 ? 2 : 1;
     if (kernel_mode == 3 && sh.rowf == 2 && option(OPT_ALIGN_LOCATE) >= 0 &&
-        plan_locate(rows, colbase, enc_n, R, GO, GE, rowzero, max_len, lp))
+        plan_locate(rows, colbase, enc_n, R, GO, GE, rowzero, max_len, loc_frame, lp))
         kernel_mode = 4;
     // Far more workgroups than fit at once: each wave then owns only a few work items and the
     // hardware hands out workgroups as CUs free up, which balances the load much better than an
@@ -2174,6 +2239,7 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
         SL_HIP(hipMemsetAsync(d_redo, 0, 2 * sizeof(int), stream));
         a.loc_tab = d_ltab; a.loc_rz = d_lrz; a.loc_redo = d_redo; a.loc_stats = d_stats;
         a.loc_GO = lp.GO; a.loc_GE = lp.GE; a.loc_D = lp.D; a.loc_force = option(OPT_ALIGN_LOCATE) == 1 ? 1 : 0;
+        a.loc_framed = lp.framed ? 1 : 0;
         a.loc_unit = lp.unit; a.loc_slack = lp.slack; a.loc_top = lp.top;
     }
 
@@ -2202,6 +2268,8 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     if (kernel_mode == 3 || kernel_mode == 4) {
         c.counts["align_redo"] = d_stats ? lstats[0] : -1.0;
         c.counts["align_stalls"] = d_stats ? lstats[1] : -1.0;
+        // the locator's scale 2^k, negative where it ran un-framed (0: no locator)
+        c.counts["align_locate_k"] = d_stats ? (lp.framed ? lp.k : -lp.k) : 0.0;
     }
     if (flags[1]) return fail("sarlacc_amd: internal error: an alignment traceback exceeded its bound");
     return 0;

@@ -67,7 +67,7 @@ enum Opt {
     OPT_ALIGN_WIDE_BAND,      // k_align_wide_q with traceback: rows either side of the main diagonal that carry codes in the first launch (default 96; -1: every cell)
     OPT_MSA2_SIMPLE_EXTEND,   // spec v2: the extended library by the one-position-per-lane kernel also for unit weights (A/B, tests)
     OPT_MSA2_WIDE_EXTEND,     // spec v2: largest group size that takes the four-positions-per-lane extension kernel (default 12; A/B)
-    OPT_ALIGN_LOCATE,         // adaptor_align: -1 the snapshot path instead of the integer locator fill + fp64 window (A/B); 1 every read on the redo list (tests)
+    OPT_ALIGN_LOCATE,         // adaptor_align: -1 the snapshot path instead of the integer locator fill + fp64 window (A/B); 1 every read on the redo list (tests); 2 the locator outside its extension-free frame, 3 the same at the frame's scale (A/B)
     OPT_ALIGN_PANEL,          // barcode panel: -1 every barcode by run_align + the device fold instead of the fused kernel (A/B, cross-check)
     OPT_PROFILE_CHUNK_READS,  // profile_reads: reads per chunk of the batch (0 = by the byte budget of the aligner's scratch; tests force several chunks)
     OPT_N
