@@ -436,7 +436,12 @@ int sarlacc_set_msa_spec(int spec);
  *   group size of the four-positions-per-lane kernel), "align_locate" (adaptor_align: -1 the snapshot path alone, 1 every read
  *   through the locator's redo list, 2 the locator outside its extension-free frame, 3 the same at the frame's scale;
  *   sarlacc_stage_count "align_redo" / "align_stalls" / "align_locate_k" (the locator's scale 2^k, negative outside the
- *   frame, 0 without a locator) report the last such call),
+ *   frame, 0 without a locator) report the last such call, and so do "align_oversize" (the reads of align_redo that the
+ *   locator itself listed, their window being taller than the code tile), "align_window_steps" (steps summed over the window
+ *   kernel's work items, each the tallest of its eight windows) and "align_window_class_<c>" (reads whose window takes
+ *   8 c steps at most, c = 1 .. 31, of the call's last launch)),
+ *   "align_window_classes" (adaptor_align by the locator: -1 the windows in index order, one redo list filled by the window
+ *   kernel and its launch on the caller's stream instead of the locator's classes, its oversize list and the side stream),
  *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel),
  *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a

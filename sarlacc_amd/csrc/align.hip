@@ -93,9 +93,17 @@ struct AlignArgs {
     int loc_force;                     // testing: every read goes on the redo list
     double loc_unit, loc_slack, loc_top;  // 2^-k; Delta_int + eps_fp; sum+ smax + max(0, row 0) + 1 (window certificate)
     int* loc_redo;                     // [0] reads on the redo list, [2 ...] their indices (reset per launch)
-    int* loc_stats;                    // [0] reads redone, [1] walks that stalled at the window top (summed over a call)
+    int* loc_stats;                    // summed over a call: [0] reads redone, [1] walks that stalled at the window top, [2] reads the locator
+                                       // put on its oversize list, [4 .. 5] one 64-bit count of window steps (see LOC_STATS)
     int* loc_out;                      // [3 n] per read: I_max, lo, hi (x2 units) from MODE 5 for MODE 4
-    const int* read_list;              // the MODE 3 redo launch: loc_redo of the MODE 4 launch ([0] count, reads from [2]); null: reads 0 .. n - 1
+    // window classes (null: off, MODE 4 takes the reads in index order and lists the oversize ones itself)
+    uint8_t* loc_cls;                  // [n] per read: ceil(window steps / 8), 0 for a read on the oversize list
+    int* loc_ccount;                   // [LOC_NCLS] reads per class, then [LOC_NCLS] the cursors of k_loc_order (reset per launch)
+    int* loc_over;                     // the locator's oversize list, laid out like loc_redo (reset per launch)
+    const int* read_list;              // the reads of this launch ([0] count, reads from [2]): a redo list for MODE 3, the window order for
+                                       // MODE 4; null: reads 0 .. n - 1
+    int bad_done;                      // the locator of this call has seen every quality: this launch reports no bad one (its
+                                       // slots are not read indices where it runs from a list)
 };
 
 // Traceback code of one cell, 4 bits -- the raw outcomes of the cell's four comparisons:
@@ -224,9 +232,53 @@ constexpr int LOC_NEG = -(1 << 29);   // -inf of the integer DP (and of its tabl
 // units of 2^-k).
 constexpr int LOC_NEG_FRAMED = -(1 << 30);
 constexpr int LOC_FRAME_KMIN = 8;
-// resident wavefronts per SIMD of the locator kernel: at 4 it takes 113 VGPRs (114 in the frame) and spills nothing (at 6
+// resident wavefronts per SIMD of the locator kernel: at 4 it takes 114 VGPRs (115 in the frame) and spills nothing (at 6
 // and 8 its steady state reloads spilled registers from scratch)
 constexpr int LOC_WAVES = 4;
+constexpr int LOC_STATS = 6;   // ints of AlignArgs::loc_stats
+// Window classes.  A window wave runs the steps of the tallest of its eight windows, so the locator, which ends with
+// every input of a read's window plan, files the read under ceil(steps / 8) and k_loc_order turns the class bytes into
+// the order MODE 4 takes its reads in: tallest class first, a class contiguous, any order inside it (outputs go by read
+// index).  Reads whose window exceeds the code tile go on a list of their own instead, which the snapshot kernel aligns
+// on a second stream beside the windows.
+constexpr int LOC_NCLS = 32;   // classes 1 .. LOC_NCLS - 1 (snap_win / 8 is 15 at most for the shapes the locator serves)
+
+// The window plan of one read from what the locator reports (lo, hi in x2 units): the window's first row (0: the true
+// row 0), the lowest row it must hold and its steps.  The locator and MODE 4 both call this and nothing else.
+struct WinPlan { int ts, want, need; };
+__device__ __forceinline__ WinPlan window_plan(const AlignArgs& A, int imax, int lo_x2, int hi_x2) {
+    const int lo = (lo_x2 >> 1) + 1, hi = (hi_x2 >> 1) + 1;
+    // the window certificate: U + GO + 1 < F_low, U = top - 1 - GO - GE (Wc - R)
+    const double f_low = static_cast<double>(imax) * A.loc_unit - A.loc_slack;
+    const double over = floor((A.loc_top - f_low) / A.GE) + 1.0;
+    const int wc = A.R + (over > 0.0 ? static_cast<int>(fmin(over, 1.0e6)) : 0);
+    const int r0 = lo - wc;
+    const int ts = r0 < 8 ? 0 : (r0 & ~7);
+    return {ts, hi, hi + A.W + 1 - ts};
+}
+
+// The window order from the class bytes: perm[0] the number of reads in it, perm[2 ...] the reads, tallest class first.
+// A block ranks its 256 reads per class in LDS and reserves one range per class with one atomic on the class cursor.
+__global__ void __launch_bounds__(256) k_loc_order(const uint8_t* cls, long long n, int* ctl, int* perm) {
+    __shared__ int s_cnt[LOC_NCLS], s_base[LOC_NCLS];
+    const int t = threadIdx.x;
+    if (t < LOC_NCLS) s_cnt[t] = 0;
+    __syncthreads();
+    const long long read = static_cast<long long>(blockIdx.x) * 256 + t;
+    const int c = read < n ? min(static_cast<int>(cls[read]), LOC_NCLS - 1) : 0;
+    int rank = 0;
+    if (c) rank = atomicAdd(&s_cnt[c], 1);
+    __syncthreads();
+    if (t < LOC_NCLS) {
+        int taller = 0;
+        for (int x = t + 1; x < LOC_NCLS; ++x) taller += ctl[x];
+        const int mine = t ? s_cnt[t] : 0;
+        s_base[t] = taller + (mine ? atomicAdd(&ctl[LOC_NCLS + t], mine) : 0);
+        if (blockIdx.x == 0 && t == 0) perm[0] = taller;   // every class is taller than class 0, which holds no read
+    }
+    __syncthreads();
+    if (c) perm[2 + s_base[c] + rank] = static_cast<int>(read);
+}
 
 // MODE 0: scores only.  MODE 1: scores + reference->read map (adaptor_align), codes streamed.
 // MODE 2: scores + gapped strings + edit distance (general_align).
@@ -337,6 +389,7 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
 
     const long long nreads = A.read_list ? static_cast<long long>(A.read_list[0]) : A.n;   // redo launch: the list's length
     const long long nitems = (nreads + A.ngroups - 1) / A.ngroups;
+    int wsteps = 0;   // MODE 4: window steps of this wave's items (wave-uniform; a wave owns a few items of 120 steps at most)
     for (long long item = gwave; item < nitems; item += nwaves) {
         const long long slot_r = item * A.ngroups + g;
         const bool valid = lane_on && slot_r < nreads;
@@ -437,7 +490,7 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                                             : code * static_cast<uint32_t>(A.row_bytes) + static_cast<uint32_t>(qi << 3);
                 ent[e] = (r + e < slen) ? at : 0u;
             }
-            if (bad && !A.read_list) atomicMin(A.badqual, A.read_base + static_cast<int>(item * A.ngroups + sg));
+            if (bad && !A.bad_done) atomicMin(A.badqual, A.read_base + static_cast<int>(item * A.ngroups + sg));
             const uint2 w = make_uint2(ent[0] | (ent[1] << 16), ent[2] | (ent[3] << 16));
             uint16_t* const slot = s_ring + sg * SLOT + (r & (RING - 1));   // r is a multiple of 4: 8-byte aligned
             *reinterpret_cast<uint2*>(slot) = w;
@@ -749,6 +802,20 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                 A.loc_out[3 * read] = loc_max;
                 A.loc_out[3 * read + 1] = loc_lo;
                 A.loc_out[3 * read + 2] = loc_hi;
+                if (A.loc_cls) {
+                    const WinPlan wp = window_plan(A, loc_max, loc_lo, loc_hi);
+                    int cls = 0;
+                    if (wp.need > A.snap_win || A.loc_force) {
+                        const int at = atomicAdd(A.loc_over, 1);
+                        A.loc_over[2 + at] = static_cast<int>(read);
+                        atomicAdd(A.loc_stats, 1);
+                        atomicAdd(A.loc_stats + 2, 1);
+                    } else {
+                        cls = min(max((wp.need + 7) >> 3, 1), LOC_NCLS - 1);
+                        atomicAdd(A.loc_ccount + cls, 1);
+                    }
+                    A.loc_cls[read] = static_cast<uint8_t>(cls);
+                }
             }
             continue;
         } else {
@@ -786,16 +853,11 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
             };
             if (MODE == 4) {
                 const int lane_r = lane_of(g, jlast);
-                const int imax = __shfl(loc_max, lane_r);
-                const int lo = (__shfl(loc_lo, lane_r) >> 1) + 1, hi = (__shfl(loc_hi, lane_r) >> 1) + 1;
-                // the window certificate: U + GO + 1 < F_low, U = top - 1 - GO - GE (Wc - R)
-                const double f_low = static_cast<double>(imax) * A.loc_unit - A.loc_slack;
-                const double over = floor((A.loc_top - f_low) / GE) + 1.0;
-                const int wc = R + (over > 0.0 ? static_cast<int>(fmin(over, 1.0e6)) : 0);
-                const int r0 = lo - wc;
-                ts4 = r0 < 8 ? 0 : (r0 & ~7);
-                want = hi;
-                if (valid && (want + W + 1 - ts4 > A.snap_win || A.loc_force)) {
+                const WinPlan wp = window_plan(A, __shfl(loc_max, lane_r), __shfl(loc_lo, lane_r), __shfl(loc_hi, lane_r));
+                ts4 = wp.ts;
+                want = wp.want;
+                // (with window classes the locator has listed these reads already and the order holds none of them)
+                if (valid && (wp.need > A.snap_win || A.loc_force)) {
                     if (leader) push_redo();
                     pending = 0;
                 }
@@ -823,6 +885,7 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                     }
                 }
                 nwin = min(((nwin + UNR - 1) / UNR) * UNR, A.snap_win);
+                if (MODE == 4) wsteps += nwin;
                 t_wa = min(((t_wa + UNR - 1) / UNR) * UNR, nwin);
                 t_wb = min(max((t_wb / UNR) * UNR, t_wa), nwin);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1067,6 +1130,7 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
             }
         }
     }
+    if (MODE == 4 && lane == 0 && wsteps) atomicAdd(reinterpret_cast<unsigned long long*>(A.loc_stats + 4), static_cast<unsigned long long>(wsteps));
 }
 
 // Empty reference: the DP has only column 0 (src/reference_align.cpp:63-78,:104).
@@ -1945,18 +2009,51 @@ static int launch_pen(bool pensel, int mode, bool local, const AlignArgs& a, int
                   : launch_mode<K, ROW16, KLAST, false>(mode, local, a, grid, lds, s);
 }
 
+// What a MODE 4 call with window classes launches beside `a` (whose tiles then hold window codes only): the window order
+// and the tiles, with snapshots, of the two small snapshot launches.
+struct LocLaunch {
+    int* order = nullptr;                  // [n + 2] k_loc_order's output
+    void* redo_dirs = nullptr;
+    unsigned long long redo_per_wave = 0;
+    int redo_grid = 0;
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+};
+
 template <int K, int KLAST>
-static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStream_t s) {
+static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStream_t s, const LocLaunch* ll) {
     if (mode == 4) {
         // the locator (its LDS: rings + the integer table), the windows, then the snapshot kernel on the reads the windows
         // put on their list (count read on the device)
         const size_t lds5 = sizeof(uint16_t) * NWAVES * NGMAX2 * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
         if (a.loc_framed) hipLaunchKernelGGL((k_align<K, 6, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
         else hipLaunchKernelGGL((k_align<K, 5, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
-        hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
         AlignArgs r = a;
-        r.read_list = a.loc_redo;
-        hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, r);
+        r.bad_done = 1;
+        if (!ll) {
+            hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
+            r.read_list = a.loc_redo;
+            hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, r);
+        } else {
+            // The locator has listed the oversize reads: the snapshot kernel aligns them on the side stream while this one
+            // orders and runs the windows.  Both snapshot launches are small (their item loop strides) and share tiles: the
+            // second, on the reads whose walk stalled, starts after the join.
+            r.dirs = ll->redo_dirs;
+            r.dirs_per_wave = ll->redo_per_wave;
+            SL_HIP(hipEventRecord(ll->fork, s));
+            SL_HIP(hipStreamWaitEvent(ll->side, ll->fork, 0));
+            r.read_list = a.loc_over;
+            hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(ll->redo_grid), dim3(64 * NWAVES), lds, ll->side, r);
+            SL_HIP(hipEventRecord(ll->join, ll->side));
+            hipLaunchKernelGGL(k_loc_order, dim3(static_cast<unsigned>((a.n + 255) / 256)), dim3(256), 0, s, a.loc_cls, a.n, a.loc_ccount, ll->order);
+            AlignArgs w = a;
+            w.read_list = ll->order;
+            w.bad_done = 1;
+            hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, w);
+            SL_HIP(hipStreamWaitEvent(s, ll->join, 0));
+            r.read_list = a.loc_redo;
+            hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(ll->redo_grid), dim3(64 * NWAVES), lds, s, r);
+        }
     } else if (mode == 3) hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
     else hipLaunchKernelGGL((k_align<K, 0, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
     SL_HIP(hipGetLastError());
@@ -1964,19 +2061,19 @@ static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStre
 }
 
 static int launch_k(int K, int rowf, int R, bool pensel, int mode, bool local, const AlignArgs& a, int grid, size_t lds,
-                    hipStream_t s) {
+                    hipStream_t s, const LocLaunch* ll = nullptr) {
     const int klast = (R - 1) % K;
     if (rowf == 2) {
         // interleaved alignments: local mode without penalty selects only (adaptor_align by snapshots, score-only)
         if (!local || pensel || !(mode == 3 || mode == 4 || mode == 0)) return fail("sarlacc_amd: interleaved alignments serve local modes 0 and 3 only");
         const int key = K * 4 + klast;
         switch (key) {
-            case 2 * 4 + 0: return launch_il<2, 0>(mode, a, grid, lds, s);
-            case 2 * 4 + 1: return launch_il<2, 1>(mode, a, grid, lds, s);
-            case 4 * 4 + 0: return launch_il<4, 0>(mode, a, grid, lds, s);
-            case 4 * 4 + 1: return launch_il<4, 1>(mode, a, grid, lds, s);
-            case 4 * 4 + 2: return launch_il<4, 2>(mode, a, grid, lds, s);
-            case 4 * 4 + 3: return launch_il<4, 3>(mode, a, grid, lds, s);
+            case 2 * 4 + 0: return launch_il<2, 0>(mode, a, grid, lds, s, ll);
+            case 2 * 4 + 1: return launch_il<2, 1>(mode, a, grid, lds, s, ll);
+            case 4 * 4 + 0: return launch_il<4, 0>(mode, a, grid, lds, s, ll);
+            case 4 * 4 + 1: return launch_il<4, 1>(mode, a, grid, lds, s, ll);
+            case 4 * 4 + 2: return launch_il<4, 2>(mode, a, grid, lds, s, ll);
+            case 4 * 4 + 3: return launch_il<4, 3>(mode, a, grid, lds, s, ll);
         }
         return fail("sarlacc_amd: unsupported columns-per-lane %d for interleaved alignments", K);
     }
@@ -2191,6 +2288,13 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     if (kernel_mode == 3 && sh.rowf == 2 && option(OPT_ALIGN_LOCATE) >= 0 &&
         plan_locate(rows, colbase, enc_n, R, GO, GE, rowzero, max_len, loc_frame, lp))
         kernel_mode = 4;
+    // MODE 4 with window classes (align_window_classes = -1: without, A/B): its own tiles hold the codes of one window and
+    // the two small snapshot launches get tiles of their own
+    const bool classes = kernel_mode == 4 && option(OPT_ALIGN_WINDOW_CLASSES) >= 0;
+    // (the locator serves eight-lane alignments only: R <= 32, W = 8, a tile of 120 steps at most)
+    if (classes && snap_win(R, sh.W) / 8 >= LOC_NCLS) return fail("sarlacc_amd: internal error: window tile of %d steps exceeds the window classes", snap_win(R, sh.W));
+    const size_t redo_per_wave = per_wave_elems;
+    if (classes) per_wave_elems = static_cast<size_t>(snap_win(R, sh.W) / tb_steps) * 64;
     // Far more workgroups than fit at once: each wave then owns only a few work items and the
     // hardware hands out workgroups as CUs free up, which balances the load much better than an
     // exactly resident grid with a static stride (1.74 -> 2.07 TCUPS at 1M x 2kb; flat from 128 to
@@ -2221,18 +2325,20 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     a.snap_head = snap_head(R); a.snap_win = snap_win(R, sh.W);
     a.aln_ref = out.d_aln_ref; a.aln_qry = out.d_aln_qry; a.aln_len = out.d_aln_len; a.edits = out.d_edits;
     int* d_stats = nullptr;
+    int* d_ccount = nullptr;
+    LocLaunch ll;
     if (kernel_mode == 4) {
         int *d_ltab, *d_lrz, *d_redo;
         if (co.init_bad) {
             SL_TRY(upload("align.ltab", lp.tab.data(), lp.tab.size(), &d_ltab, stream));
             SL_TRY(upload("align.lrz", lp.rz.data(), lp.rz.size(), &d_lrz, stream));
-            const int zero[2] = {0, 0};
-            SL_TRY(upload("align.lstats", zero, 2, &d_stats, stream));
+            const int zero[LOC_STATS] = {};
+            SL_TRY(upload("align.lstats", zero, LOC_STATS, &d_stats, stream));
             if (!co.finish) SL_HIP(hipStreamSynchronize(stream));
         } else {
             SL_TRY(scratch("align.ltab", lp.tab.size(), &d_ltab));
             SL_TRY(scratch("align.lrz", lp.rz.size(), &d_lrz));
-            SL_TRY(scratch("align.lstats", 2, &d_stats));
+            SL_TRY(scratch("align.lstats", LOC_STATS, &d_stats));
         }
         SL_TRY(scratch("align.lredo", static_cast<size_t>(n) + 2, &d_redo));
         SL_TRY(scratch("align.lout", static_cast<size_t>(n) * 3, &a.loc_out));
@@ -2241,6 +2347,21 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
         a.loc_GO = lp.GO; a.loc_GE = lp.GE; a.loc_D = lp.D; a.loc_force = option(OPT_ALIGN_LOCATE) == 1 ? 1 : 0;
         a.loc_framed = lp.framed ? 1 : 0;
         a.loc_unit = lp.unit; a.loc_slack = lp.slack; a.loc_top = lp.top;
+        if (classes) {
+            SL_TRY(scratch("align.lcls", static_cast<size_t>(n), &a.loc_cls));
+            SL_TRY(scratch("align.lccount", static_cast<size_t>(2 * LOC_NCLS), &d_ccount));
+            SL_TRY(scratch("align.lover", static_cast<size_t>(n) + 2, &a.loc_over));
+            SL_TRY(scratch("align.lorder", static_cast<size_t>(n) + 2, &ll.order));
+            SL_HIP(hipMemsetAsync(d_ccount, 0, 2 * LOC_NCLS * sizeof(int), stream));
+            SL_HIP(hipMemsetAsync(a.loc_over, 0, 2 * sizeof(int), stream));
+            a.loc_ccount = d_ccount;
+            // about one workgroup per four CUs, each wavefront with a whole tile (codes of a window + snapshots)
+            const size_t wg_bytes = std::max<size_t>(1, redo_per_wave * word_bytes * NWAVES);
+            ll.redo_grid = static_cast<int>(std::max<size_t>(1, std::min<size_t>((c.num_cu + 3) / 4, (static_cast<size_t>(6) << 30) / wg_bytes)));
+            ll.redo_per_wave = redo_per_wave;
+            SL_TRY(c.buffer("align.rdirs", static_cast<size_t>(ll.redo_grid) * wg_bytes, &ll.redo_dirs));
+            SL_TRY(c.side_stream(&ll.side, &ll.fork, &ll.join));
+        }
     }
 
     const size_t lds = sizeof(uint16_t) * NWAVES * (sh.rowf == 2 ? NGMAX2 * (RING + RING_MIRROR) : NGMAX * RING_SLOT) + sizeof(double) * rows.size() +
@@ -2249,7 +2370,7 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     if (co.stage) SL_TRY(c.stage_begin(co.stage, stream));
     else SL_HIP(hipEventRecord(c.ev_start, stream));
     if (wide) SL_TRY(launch_wide(a, R, kernel_mode == 3 ? 1 : kernel_mode, max_len, n, stream));
-    else SL_TRY(launch_k(sh.K, sh.rowf, R, pensel, kernel_mode, local, a, static_cast<int>(grid), lds, stream));
+    else SL_TRY(launch_k(sh.K, sh.rowf, R, pensel, kernel_mode, local, a, static_cast<int>(grid), lds, stream, classes ? &ll : nullptr));
     if (co.stage) {
         SL_TRY(c.stage_end(co.stage, stream));
     } else {
@@ -2258,9 +2379,10 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     }
 
     if (!co.finish) return 0;
-    int flags[2] = {0, 0}, lstats[2] = {0, 0};
+    int flags[2] = {0, 0}, lstats[LOC_STATS] = {}, ccount[LOC_NCLS] = {};
     SL_HIP(hipMemcpyAsync(flags, d_bad, sizeof flags, hipMemcpyDeviceToHost, stream));
     if (d_stats) SL_HIP(hipMemcpyAsync(lstats, d_stats, sizeof lstats, hipMemcpyDeviceToHost, stream));
+    if (d_ccount) SL_HIP(hipMemcpyAsync(ccount, d_ccount, sizeof ccount, hipMemcpyDeviceToHost, stream));
     SL_HIP(hipStreamSynchronize(stream));
     *bad_qual_read = flags[0];
     // adaptor_align calls: reads the locator handed to the snapshot kernel, and walks of its window that stalled (-1: the
@@ -2268,6 +2390,20 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     if (kernel_mode == 3 || kernel_mode == 4) {
         c.counts["align_redo"] = d_stats ? lstats[0] : -1.0;
         c.counts["align_stalls"] = d_stats ? lstats[1] : -1.0;
+        // reads the locator itself listed as oversize (part of align_redo; 0 without window classes), and the steps the
+        // window kernel's work items ran (each the tallest of its eight windows)
+        c.counts["align_oversize"] = d_stats ? lstats[2] : -1.0;
+        unsigned long long wsteps = 0;
+        std::memcpy(&wsteps, lstats + 4, sizeof wsteps);
+        c.counts["align_window_steps"] = d_stats ? static_cast<double>(wsteps) : -1.0;
+        // reads per window class (a class is 8 steps) of the call's last launch, "align_window_class_<c>": diagnostic, for
+        // the tests and the perf records
+        static const std::vector<std::string> class_keys = [] {
+            std::vector<std::string> v;
+            for (int x = 0; x < LOC_NCLS; ++x) v.push_back("align_window_class_" + std::to_string(x));
+            return v;
+        }();
+        for (int x = 1; x < LOC_NCLS; ++x) c.counts[class_keys[x]] = d_ccount ? ccount[x] : -1.0;
         // the locator's scale 2^k, negative where it ran un-framed (0: no locator)
         c.counts["align_locate_k"] = d_stats ? (lp.framed ? lp.k : -lp.k) : 0.0;
     }

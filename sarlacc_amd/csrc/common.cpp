@@ -26,7 +26,7 @@ int fail(const char* fmt, ...) {
 }
 
 static const char* const kOptNames[OPT_N] = {"msa_spec", "msa2_general_rows", "msa2_chain_hbm", "msa2_waves_per_cu", "msa2_single_wave", "msa2_batches", "align_pensel", "align_chunks",
-                                             "align_k", "align_waves_per_cu", "consensus_chars", "consensus_generic", "msa_int32", "msa_affine", "umi_full_rounds", "umi_tile_search", "msa_bitvector", "msa_bitvector_core", "msa_bitvector_tile_gb", "align_interleave", "umi_split_min", "msa2_tight_profiles", "umi_scan_single", "align_wide_barrier", "msa2_budget_gb", "msa2_max_columns", "align_wide_band", "msa2_simple_extend", "msa2_wide_extend", "align_locate", "align_panel", "profile_chunk_reads"};
+                                             "align_k", "align_waves_per_cu", "consensus_chars", "consensus_generic", "msa_int32", "msa_affine", "umi_full_rounds", "umi_tile_search", "msa_bitvector", "msa_bitvector_core", "msa_bitvector_tile_gb", "align_interleave", "umi_split_min", "msa2_tight_profiles", "umi_scan_single", "align_wide_barrier", "msa2_budget_gb", "msa2_max_columns", "align_wide_band", "msa2_simple_extend", "msa2_wide_extend", "align_locate", "align_panel", "profile_chunk_reads", "align_window_classes"};
 static int* option_values() {
     static int values[OPT_N];
     static const bool parsed = [] {
@@ -94,6 +94,27 @@ int Context::buffer(const char* name, size_t bytes, void** out) {
     }
     *out = w.ptr;
     return 0;
+}
+
+int Context::side_stream(hipStream_t* s, hipEvent_t* fork, hipEvent_t* join) {
+    if (!side) {
+        SL_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+        SL_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+        SL_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    }
+    *s = side; *fork = ev_fork; *join = ev_join;
+    return 0;
+}
+
+void Context::side_release() {
+    if (side) {
+        (void)hipStreamSynchronize(side);
+        (void)hipStreamDestroy(side);
+        (void)hipEventDestroy(ev_fork);
+        (void)hipEventDestroy(ev_join);
+    }
+    side = nullptr;
+    ev_fork = ev_join = nullptr;
 }
 
 void Context::stage_reset(const char* name) {
@@ -175,6 +196,7 @@ int sarlacc_set_device(int device) {
                 (void)hipEventDestroy(seg.second);
             }
         c.stages.clear();
+        c.side_release();
         c.ready = false;
     }
     c.device = device;

@@ -70,6 +70,7 @@ enum Opt {
     OPT_ALIGN_LOCATE,         // adaptor_align: -1 the snapshot path instead of the integer locator fill + fp64 window (A/B); 1 every read on the redo list (tests); 2 the locator outside its extension-free frame, 3 the same at the frame's scale (A/B)
     OPT_ALIGN_PANEL,          // barcode panel: -1 every barcode by run_align + the device fold instead of the fused kernel (A/B, cross-check)
     OPT_PROFILE_CHUNK_READS,  // profile_reads: reads per chunk of the batch (0 = by the byte budget of the aligner's scratch; tests force several chunks)
+    OPT_ALIGN_WINDOW_CLASSES, // adaptor_align by the locator: -1 the windows in index order, one redo list filled by the window kernel and its launch on the caller's stream (A/B, tests)
     OPT_N
 };
 int option(Opt o);
@@ -98,6 +99,13 @@ struct Context {
     struct StageTimer { std::vector<std::pair<hipEvent_t, hipEvent_t>> segs; size_t used = 0; bool open = false; };
     std::map<std::string, StageTimer> stages;
     std::map<std::string, double> counts;   // work counters of the last call (cells, jobs ...), sarlacc_stage_count
+    // A stream of the library's own beside the caller's (non-blocking, created on first use) and the event pair that
+    // forks work onto it and joins it back: adaptor_align's oversize reads run there beside the window kernel.  They belong
+    // to the device they were created on (sarlacc_set_device drops them with the buffers).
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int side_stream(hipStream_t* s, hipEvent_t* fork, hipEvent_t* join);
+    void side_release();
     void stage_reset(const char* name);
     int stage_begin(const char* name, hipStream_t s);
     int stage_end(const char* name, hipStream_t s);
