@@ -915,8 +915,8 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
     const int max_rows = a.max_rows;
 
     uint8_t* d_cons; uint8_t* d_phred; double* d_lerr = nullptr; int32_t* d_len; int8_t* d_status;
-    unsigned long long* d_badchar; int* d_fixn; long long* d_fixpos; double* d_fixval;
-    const int fix_cap = 4096;
+    unsigned long long* d_badchar; int* d_fixn; long long* d_fixpos = nullptr; double* d_fixval = nullptr;
+    int fix_cap = 4096;
     SL_TRY(scratch("cons.out", static_cast<size_t>(total), &d_cons));
     SL_TRY(scratch("cons.phred", static_cast<size_t>(total), &d_phred));
     if (lerr) SL_TRY(scratch("cons.lerr", static_cast<size_t>(total), &d_lerr));
@@ -924,30 +924,31 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
     SL_TRY(scratch("cons.status", static_cast<size_t>(std::max<int64_t>(rows_eval, 1)), &d_status));
     SL_TRY(scratch("cons.badchar", 1, &d_badchar));
     SL_TRY(scratch("cons.fixn", 1, &d_fixn));
-    SL_TRY(scratch("cons.fixpos", fix_cap, &d_fixpos));
-    SL_TRY(scratch("cons.fixval", 4 * fix_cap, &d_fixval));
     SL_HIP(hipMemsetAsync(d_status, 0, static_cast<size_t>(std::max<int64_t>(rows_eval, 1)), s));
     SL_HIP(hipMemsetAsync(d_badchar, 0xff, sizeof(unsigned long long), s));
-    SL_HIP(hipMemsetAsync(d_fixn, 0, sizeof(int), s));
     a.cons = d_cons; a.phred = d_phred; a.lerr = d_lerr; a.cons_len = d_len; a.row_status = d_status;
-    a.first_bad_char = d_badchar; a.fix_count = d_fixn; a.fix_cap = fix_cap; a.fix_pos = d_fixpos; a.fix_val = d_fixval;
-    int* d_fixgrp; int* d_gflag;
-    SL_TRY(scratch("cons.fixgrp", fix_cap, &d_fixgrp));
+    a.first_bad_char = d_badchar; a.fix_count = d_fixn;
+    int* d_fixgrp = nullptr; int* d_gflag;
     SL_TRY(scratch("cons.gflag", static_cast<size_t>(std::max<int64_t>(ngroups, 1)), &d_gflag));
-    SL_HIP(hipMemsetAsync(d_fixgrp, 0xff, sizeof(int) * fix_cap, s));
-    a.fix_grp = d_fixgrp; a.gflag = d_gflag; a.only_flagged = 0;
-
-    if (ng_eval > 0) {
-        const size_t lds = (quality ? 2 * sizeof(double) * enc_n : 0) + (2 * sizeof(long long) + 3 * sizeof(int)) * static_cast<size_t>(max_rows) + 16;
-        if (lds > 160 * 1024) return fail("sarlacc_amd: alignment with %d rows does not fit the consensus kernel", max_rows);
-        const int grid = static_cast<int>(std::min<int64_t>(ng_eval, static_cast<int64_t>(c.num_cu) * 32));
-        // quality vote without the per-column log errors: 4 columns per lane, 4 alignments per workgroup
-        const size_t lds4 = sizeof(double) * 4 * (5 * static_cast<size_t>(enc_n) + 1) + 4 * (2 * sizeof(long long) + 3 * sizeof(int)) * static_cast<size_t>(max_rows) + 16;
-        const bool q4 = quality && !lerr && lds4 <= 48 * 1024;
-        SL_HIP(hipEventRecord(c.ev_start, s));
-        c.counts["consensus_cells"] = static_cast<double>(total);
-        c.stage_reset("consensus");
-        SL_TRY(c.stage_begin("consensus", s));
+    a.gflag = d_gflag; a.only_flagged = 0;
+    // the boundary list: fix_cap empty entries (no group recorded)
+    const auto fix_list = [&]() -> int {
+        SL_TRY(scratch("cons.fixpos", static_cast<size_t>(fix_cap), &d_fixpos));
+        SL_TRY(scratch("cons.fixval", 4 * static_cast<size_t>(fix_cap), &d_fixval));
+        SL_TRY(scratch("cons.fixgrp", static_cast<size_t>(fix_cap), &d_fixgrp));
+        SL_HIP(hipMemsetAsync(d_fixn, 0, sizeof(int), s));
+        SL_HIP(hipMemsetAsync(d_fixgrp, 0xff, sizeof(int) * static_cast<size_t>(fix_cap), s));
+        a.fix_cap = fix_cap; a.fix_pos = d_fixpos; a.fix_val = d_fixval; a.fix_grp = d_fixgrp;
+        return 0;
+    };
+    SL_TRY(fix_list());
+    const size_t lds = (quality ? 2 * sizeof(double) * enc_n : 0) + (2 * sizeof(long long) + 3 * sizeof(int)) * static_cast<size_t>(max_rows) + 16;
+    const int grid = static_cast<int>(std::min<int64_t>(ng_eval, static_cast<int64_t>(c.num_cu) * 32));
+    // quality vote without the per-column log errors: 4 columns per lane, 4 alignments per workgroup
+    const size_t lds4 = sizeof(double) * 4 * (5 * static_cast<size_t>(enc_n) + 1) + 4 * (2 * sizeof(long long) + 3 * sizeof(int)) * static_cast<size_t>(max_rows) + 16;
+    const bool q4 = quality && !lerr && lds4 <= 48 * 1024;
+    // the vote's launches: run again when the boundary list was too short
+    const auto vote = [&]() -> int {
         if (a.codes) {
             // rows written as vote codes by the MSA stage: nothing to decode
             const size_t ldsc = static_cast<size_t>(enc_n + 1) * QC_ROWB;
@@ -978,6 +979,16 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
             else hipLaunchKernelGGL(k_consensus<false>, dim3(grid), dim3(64), lds, s, a);
         }
         SL_HIP(hipGetLastError());
+        return 0;
+    };
+
+    if (ng_eval > 0) {
+        if (lds > 160 * 1024) return fail("sarlacc_amd: alignment with %d rows does not fit the consensus kernel", max_rows);
+        SL_HIP(hipEventRecord(c.ev_start, s));
+        c.counts["consensus_cells"] = static_cast<double>(total);
+        c.stage_reset("consensus");
+        SL_TRY(c.stage_begin("consensus", s));
+        SL_TRY(vote());
         SL_HIP(hipEventRecord(c.ev_stop, s));
         SL_TRY(c.stage_end("consensus", s));
         c.timed = true;
@@ -1016,7 +1027,14 @@ static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_
         }
     if (struct_err_kind == 1) return fail("alignment strings should have the same length");
     if (struct_err_kind == 2) return fail("alignments and qualities have different numbers of entries");
-    if (fixn > fix_cap) return fail("sarlacc_amd: too many Phred values on a rounding boundary (%d)", fixn);
+    // More boundary columns than the list holds (every column of an alignment of equal rows can sit on one): the count
+    // is exact and the kernels are deterministic, so the vote runs once more with a list of that size.
+    while (fixn > fix_cap) {
+        fix_cap = fixn;
+        SL_TRY(fix_list());
+        SL_TRY(vote());
+        SL_HIP(hipMemcpy(&fixn, d_fixn, sizeof fixn, hipMemcpyDeviceToHost));
+    }
 
     // compact the kept columns on the device, then copy only those back
     std::vector<long long> dst(static_cast<size_t>(ngroups) + 1, 0);
