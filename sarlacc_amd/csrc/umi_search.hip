@@ -1222,6 +1222,10 @@ int pair_edges(const std::string& p, const SortedUmis& S, int limit, int tile_lo
         SL_HIP(hipStreamSynchronize(s));
         d_list = d_l;
     }
+    // what the tile filter kept: upper-triangle tile pairs of this launch, and how many of them are searched (0: no list)
+    const long long below_diagonal = static_cast<long long>(tile_lo + tile_hi - 1) * (tile_hi - tile_lo) / 2;   // sum of the row tiles' indices
+    c.counts["umi_tile_pairs_total"] = static_cast<double>(ntp - below_diagonal);
+    c.counts["umi_tile_pairs_listed"] = d_list ? static_cast<double>(nlisted) : 0;
     const uint32_t row_lo = static_cast<uint32_t>(std::min<long long>(static_cast<long long>(tile_lo) * TILE, n));
     const uint32_t row_hi = static_cast<uint32_t>(std::min<long long>(static_cast<long long>(tile_hi) * TILE, n));
     // every search kernel of one pass over the set; `stride` > 1: a sample (every stride-th tile pair / work item)

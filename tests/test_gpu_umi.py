@@ -219,6 +219,7 @@ def test_candidate_rounds_cut_off_list_falls_back_to_a_full_round(oracle):
         want = oracle.umi_group(umis, t, None, t, g, fast=True)
         same_lists(calls.umi_group(umis, t, None, t, g), want)
         assert _lib.stage_count("umi_links") >= 24 * len(umis)
+        assert _lib.stage_count("umi_pair_attempts") == 2   # 3 123 750 pairs: past the first pair buffer, a second search
         assert _lib.stage_count("umi_cluster_full_rounds") >= 1 and _lib.stage_count("umi_cluster_candidate_rounds") >= 1
 
 

@@ -1,0 +1,173 @@
+"""The neighbour search of the UMI stage at every threshold class and through every filter (umi_search.hip).
+
+Exact integer work, compared without tolerance against two CPU references of different build: the content of every
+neighbour list comes from dense full-table distances (d2 <= 2 * limit; no trie, no band, no filter), the order inside the
+lists and the groups from the oracle's trie walk.  The inputs (tests/umi_cases.py; tests/test_umi_cases.py shows that they
+hold what they claim) put pairs exactly at and just past each threshold, make the tile filter discard tile pairs that lie
+next to tiles with true neighbours, and push the pair count past the first buffer.
+
+Thresholds and the instantiation each one reaches:
+  k_umi_pairs<K>, strings of up to 32 bases (8, 12, 31, 32):   0 1 2 3 4 5 -> K = limit;  6 7 8 -> 8;  9 15 16 -> 16;
+                                                                17 31 32 33 40 -> 32 (33 and 40: above every string length)
+  k_umi_pairs_long<K, false>, 33 to 128 bases (33, 64, 65, 128): 4 -> 5;  6 7 8 -> 8;  10 15 16 -> 16;  17 19 40 -> full DP
+  k_umi_pairs_long<K, true>, beyond 128 bases (129, 300):       4 -> 5;  7 8 -> 8;  16 -> 16;  17 -> full DP
+  k_tile_info, k_tile_pairs<L>, prefix_dist<L> in the tile and the 64-column filter: L = 1 .. 5 on 6 400 anchored strings,
+  the per-row prefix test at L = 1 .. 3."""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import umi_cases as K
+
+pytestmark = pytest.mark.gpu
+
+
+def same_lists(got, want):
+    assert len(got) == len(want), (len(got), len(want))
+    for k, (x, y) in enumerate(zip(got, want)):
+        if not np.array_equal(x, y):
+            raise AssertionError((k, list(x)[:40], list(y)[:40], len(x), len(y)))
+
+
+def same_groups_or_same_error(oracle, seqs, limit, groups):
+    from sarlacc_amd import SarlaccError, calls
+    try:
+        want = oracle.umi_group(seqs, limit, None, limit, groups, fast=True)
+    except oracle.OracleError as e:   # a string with more N than 2 * limit is not its own neighbour
+        with pytest.raises(SarlaccError, match=str(e)):
+            calls.umi_group(seqs, limit, None, limit, groups)
+        return
+    same_lists(calls.umi_group(seqs, limit, None, limit, groups), want)
+
+
+# ---------------------------------------------------------------------------
+# 1. every threshold class, pairs exactly at and just past the limit
+
+def at_limit_case(oracle, length, limit):
+    from sarlacc_amd import _lib, calls
+    rng = np.random.default_rng(K.case_seed(length, limit))
+    seqs = K.at_limit_families(rng, length, limit, K.case_alphabet(length), K.case_molecules(length))
+    d2 = K.dense_d2(seqs, oracle)
+    census = K.limit_census(d2, limit)
+    print("length %d limit %d: n %d, pairs at the limit %d, just past %d, odd %d" % (length, limit, len(seqs), census["at"], census["past"], census["odd"]))
+    got = calls.fast_levdist_test(seqs, limit, True)
+    assert _lib.stage_count("umi_split_search") == 0 and _lib.stage_count("umi_tile_pairs_listed") == 0
+    same_lists(got, K.neighbours_from_d2(seqs, d2, limit))       # content (and order) from the dense distances
+    same_lists(got, oracle.fast_levdist_test(seqs, limit))       # order from the trie walk
+    same_groups_or_same_error(oracle, seqs, limit, [list(range(1, len(seqs) + 1))])
+    same_groups_or_same_error(oracle, seqs, limit, K.three_groups(rng, len(seqs)))
+
+
+@pytest.mark.parametrize("limit", K.ONE_WORD_LIMITS)
+@pytest.mark.parametrize("length", K.ONE_WORD_LENGTHS)
+def test_one_word_path_at_the_limit(oracle, length, limit):
+    # 32 bases: the la >= 32 edge of shd_reject's masks; 33 and 40: beyond every string, every pair of a pre-group is a neighbour
+    at_limit_case(oracle, length, limit)
+
+
+@pytest.mark.parametrize("limit", K.FOUR_WORD_LIMITS)
+@pytest.mark.parametrize("length", K.FOUR_WORD_LENGTHS)
+def test_four_word_path_at_the_limit(oracle, length, limit):
+    at_limit_case(oracle, length, limit)
+
+
+@pytest.mark.parametrize("limit", K.XL_LIMITS)
+@pytest.mark.parametrize("length", K.XL_LENGTHS)
+def test_xl_path_at_the_limit(oracle, length, limit):
+    at_limit_case(oracle, length, limit)
+
+
+# ---------------------------------------------------------------------------
+# 2. the prefix filters, engaged
+
+@functools.lru_cache(maxsize=None)
+def anchored(L, variant):
+    rng = np.random.default_rng(40 + L)
+    seqs = K.anchored_set(rng, L)
+    return tuple(K.with_some_n(rng, seqs) if variant == "masked" else seqs)
+
+
+@pytest.mark.parametrize("L", [1, 2, 3, 4, 5])
+def test_tile_filter_discards_tile_pairs_and_keeps_every_neighbour(oracle, L):
+    from sarlacc_amd import _lib, calls
+    seqs = list(anchored(L, "plain"))
+    got = calls.fast_levdist_test(seqs, L, True)
+    listed, total = _lib.stage_count("umi_tile_pairs_listed"), _lib.stage_count("umi_tile_pairs_total")
+    print("L=%d: umi_tile_pairs_listed %d of umi_tile_pairs_total %d, %d links" % (L, listed, total, sum(len(x) for x in got)))
+    assert _lib.stage_count("umi_split_search") == 0
+    assert total == 325 and 0 < listed < total
+    assert _lib.stage_count("umi_pair_attempts") == 1   # under the first buffer: independent of the overflow tests
+    same_lists(got, oracle.fast_levdist_test(seqs, L))
+
+
+@pytest.mark.parametrize("L", [1, 2, 3, 4, 5])
+def test_tile_filter_groups(oracle, L):
+    seqs = list(anchored(L, "plain"))
+    same_groups_or_same_error(oracle, seqs, L, [list(range(1, len(seqs) + 1))])
+
+
+@pytest.mark.parametrize("L", [1, 2, 3, 4, 5])
+def test_tile_filter_under_three_pre_groups(oracle, L):
+    # tiles that span two pre-groups carry no prefix
+    from sarlacc_amd import _lib
+    seqs = list(anchored(L, "plain"))
+    same_groups_or_same_error(oracle, seqs, L, K.three_groups(np.random.default_rng(L), len(seqs)))
+    assert _lib.stage_count("umi_tile_pairs_total") == 325 and 0 < _lib.stage_count("umi_tile_pairs_listed")
+
+
+@pytest.mark.parametrize("what", ["lists", "groups"])
+@pytest.mark.parametrize("L", [1, 2, 3, 4, 5])
+def test_tile_filter_with_masked_bases(oracle, L, what):
+    # a tile with an N carries no prefix and is never discarded
+    from sarlacc_amd import _lib, calls
+    seqs = list(anchored(L, "masked"))
+    assert sum("N" in s for s in seqs) == 64
+    if what == "lists":
+        got = calls.fast_levdist_test(seqs, L, True)
+        print("L=%d masked: umi_tile_pairs_listed %d" % (L, _lib.stage_count("umi_tile_pairs_listed")))
+        same_lists(got, oracle.fast_levdist_test(seqs, L))
+    else:
+        same_groups_or_same_error(oracle, seqs, L, [list(range(1, len(seqs) + 1))])
+    assert _lib.stage_count("umi_tile_pairs_total") == 325 and 0 < _lib.stage_count("umi_tile_pairs_listed")
+
+
+# ---------------------------------------------------------------------------
+# 3. more pairs than the first buffer holds
+
+def test_pair_buffer_overflow_runs_a_second_search(oracle):
+    from sarlacc_amd import _lib, calls
+    umis = K.overflow_clump(np.random.default_rng(9))
+    g = [list(range(1, len(umis) + 1))]
+    want = oracle.fast_levdist_test(umis, 1)
+    assert K.undirected_pairs(want) > K.PAIR_BUFFER
+    same_lists(calls.fast_levdist_test(umis, 1, True), want)
+    assert _lib.stage_count("umi_pair_attempts") == 2 and _lib.stage_count("umi_tile_pairs_listed") == 0
+    same_lists(calls.umi_group(umis, 1, None, 1, g), oracle.umi_group(umis, 1, None, 1, g, fast=True))
+    assert _lib.stage_count("umi_pair_attempts") == 2
+
+
+def test_sampled_estimate_sizes_the_buffer_or_the_second_search_does(oracle):
+    # the tile list is in the order of its atomicAdd: the sample (every 32nd listed tile pair) may see the clump or miss it.
+    # Either way the lists are the oracle's, and the number of attempts is the one the estimate implies.
+    from sarlacc_amd import _lib, calls
+    umis = K.overflow_sampled(np.random.default_rng(10))
+    g = [list(range(1, len(umis) + 1))]
+    want = oracle.fast_levdist_test(umis, 1)
+    pairs = K.undirected_pairs(want)
+    first = max(K.PAIR_BUFFER, 32 * len(umis))
+    assert pairs > first
+
+    def check_counters():
+        listed, est, attempts = (_lib.stage_count(x) for x in ("umi_tile_pairs_listed", "umi_pairs_estimated", "umi_pair_attempts"))
+        print("listed %d, estimated %d of %d pairs, attempts %d" % (listed, est, pairs, attempts))
+        assert _lib.stage_count("umi_split_search") == 0 and 2048 <= listed <= 85 * 86 // 2
+        # about 1 000 pairs among the random strings alone: a sample of this call has seen some of them
+        assert est > 0 and est % 32 == 0 and est <= 32 * pairs
+        assert attempts in (1, 2)
+        assert attempts == (1 if max(first, int(est * 1.25) + K.PAIR_BUFFER) >= pairs else 2)   # the estimate is this call's
+
+    same_lists(calls.fast_levdist_test(umis, 1, True), want)
+    check_counters()
+    same_lists(calls.umi_group(umis, 1, None, 1, g), oracle.umi_group(umis, 1, None, 1, g, fast=True))
+    check_counters()
