@@ -442,6 +442,10 @@ int sarlacc_set_msa_spec(int spec);
  *   8 c steps at most, c = 1 .. 31, of the call's last launch)),
  *   "align_window_classes" (adaptor_align by the locator: -1 the windows in index order, one redo list filled by the window
  *   kernel and its launch on the caller's stream instead of the locator's classes, its oversize list and the side stream),
+ *   "align_window_lds" (adaptor_align by the locator: -1 the window's traceback codes in the global tile alone, the kernel
+ *   at five wavefronts per SIMD; >= 2 that many blocks in the per-wave LDS code ring instead of the default; the counters
+ *   "align_walk_global" (code words walks read from the global tile) and "align_walk_left_ring" (walks that read any)
+ *   report the last call, -1 without the ring),
  *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel),
  *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a

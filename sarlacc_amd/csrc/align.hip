@@ -94,7 +94,8 @@ struct AlignArgs {
     double loc_unit, loc_slack, loc_top;  // 2^-k; Delta_int + eps_fp; sum+ smax + max(0, row 0) + 1 (window certificate)
     int* loc_redo;                     // [0] reads on the redo list, [2 ...] their indices (reset per launch)
     int* loc_stats;                    // summed over a call: [0] reads redone, [1] walks that stalled at the window top, [2] reads the locator
-                                       // put on its oversize list, [4 .. 5] one 64-bit count of window steps (see LOC_STATS)
+                                       // put on its oversize list, [3] walks that left the LDS code ring, [4 .. 5] one 64-bit count of
+                                       // window steps, [6 .. 7] one of the code words such walks read from the global tile (see LOC_STATS)
     int* loc_out;                      // [3 n] per read: I_max, lo, hi (x2 units) from MODE 5 for MODE 4
     // window classes (null: off, MODE 4 takes the reads in index order and lists the oversize ones itself)
     uint8_t* loc_cls;                  // [n] per read: ceil(window steps / 8), 0 for a read on the oversize list
@@ -104,6 +105,7 @@ struct AlignArgs {
                                        // MODE 4; null: reads 0 .. n - 1
     int bad_done;                      // the locator of this call has seen every quality: this launch reports no bad one (its
                                        // slots are not read indices where it runs from a list)
+    int win_nb;                        // MODE 4 with the codes in LDS (WLDS): blocks of the per-wave code ring (see WIN_LDS_WAVES)
 };
 
 // Traceback code of one cell, 4 bits -- the raw outcomes of the cell's four comparisons:
@@ -235,7 +237,15 @@ constexpr int LOC_FRAME_KMIN = 8;
 // resident wavefronts per SIMD of the locator kernel: at 4 it takes 114 VGPRs (115 in the frame) and spills nothing (at 6
 // and 8 its steady state reloads spilled registers from scratch)
 constexpr int LOC_WAVES = 4;
-constexpr int LOC_STATS = 6;   // ints of AlignArgs::loc_stats
+constexpr int LOC_STATS = 8;   // ints of AlignArgs::loc_stats
+// The codes of a MODE 4 window in LDS (WLDS).  A walk reads one code word per cell it visits, each load depending on the one
+// before, and from the global tile every one of them is an L2 round trip behind an L1 invalidate.  The window's last
+// win_nb blocks of code words therefore also stay in a per-wave LDS ring (block b in slot b % win_nb), which holds the
+// rows a walk from the window's last row normally visits (snap_head + W steps); a walk that climbs past them reads the
+// global tile, the backing store, after the fence the tile needs.  With the ring a workgroup takes about 48 KB of LDS at
+// 30 columns, three fit a CU, and the kernel is compiled for three wavefronts per SIMD.
+constexpr int WIN_LDS_WAVES = 3;
+static inline int win_ring_blocks(int R, int W, int unr) { return (snap_head(R) + W + unr - 1) / unr + 1; }
 // Window classes.  A window wave runs the steps of the tallest of its eight windows, so the locator, which ends with
 // every input of a read's window plan, files the read under ceil(steps / 8) and k_loc_order turns the class bytes into
 // the order MODE 4 takes its reads in: tallest class first, a class contiguous, any order inside it (outputs go by read
@@ -301,10 +311,11 @@ __global__ void __launch_bounds__(256) k_loc_order(const uint8_t* cls, long long
 // subtracts the opening penalty and selects nothing.  Only the "jump continued" flag differs
 // (true instead of false), and the true flag is raw && !(previous cell's move is the same gap
 // kind) -- the traceback applies that from the neighbour's code, which it reads anyway.
-template <int K, int MODE, bool LOCAL, int ROWF, int KLAST, bool PENSEL>
+template <int K, int MODE, bool LOCAL, int ROWF, int KLAST, bool PENSEL, bool WLDS = false>
 // (six wavefronts per SIMD for the snapshot mode; five with eight alignments per wavefront: four columns per lane need the registers --
 // at six the recompute code spilled -- 2 182 -> 2 213 GCUPS on the same box)
-__global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 3 && ROWF != 2) ? 6 : 5) k_align(const AlignArgs A) {
+// (WLDS: the MODE 4 window with its codes in an LDS ring and the walk by whole lane groups, three wavefronts per SIMD, see WIN_LDS_WAVES)
+__global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 ? LOC_WAVES : (MODE == 3 && ROWF != 2) ? 6 : 5) k_align(const AlignArgs A) {
     constexpr bool ROW16 = ROWF != 0;                      // leaders keep their column-0 inputs through the DPP fill operand
     constexpr int NG = ROWF == 2 ? NGMAX2 : NGMAX;         // alignments per wavefront at most
     // uint16 entries per alignment's ring slot: 512 B slots let a ring address be base | offset; with eight
@@ -339,6 +350,7 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
     const int GOhi = hi32(GO), GOlo = lo32(GO), GEhi = hi32(GE), GElo = lo32(GE);
 
     static_assert(MODE < 4 || (ROWF == 2 && LOCAL && !PENSEL), "the locator runs the interleaved local shape only");
+    static_assert(!WLDS || MODE == 4, "the LDS code ring belongs to the MODE 4 window");
     // the redo launch after a locator pass with an empty list: nothing to stage
     if (A.read_list && A.read_list[0] == 0) return;
     // MODE 5 / 6: the integer table (4-byte entries, rows half as long) in place of the fp64 one
@@ -350,6 +362,12 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
         for (int x = threadIdx.x; x < A.tab_doubles; x += 64 * NWAVES) s_tab[x] = A.tables[x];
     uint16_t* const s_ring = reinterpret_cast<uint16_t*>(smem) + wave * NG * SLOT;
     int32_t* const s_map = reinterpret_cast<int32_t*>(s_tab + A.tab_doubles) + wave * A.ngroups * (R + 1);
+    // WLDS: the wave's code ring behind the maps, win_nb blocks of 64 words; this lane's word of slot 0
+    const int code_ring_bytes = WLDS ? A.win_nb * 64 * static_cast<int>(sizeof(Word)) : 0;
+    unsigned char* const s_code = reinterpret_cast<unsigned char*>(reinterpret_cast<int32_t*>(s_tab + A.tab_doubles) + NWAVES * A.ngroups * (R + 1)) +
+                                  wave * code_ring_bytes;
+    int code_ofs = 0;              // byte offset of the ring slot the next block's codes go to (wave-uniform)
+    int walk_glob = 0, walks_out = 0;   // WLDS: code words this lane read from the global tile; leaders: walks that read any
 
     double vgo[K], vge[K], rz[K];
     int colbase[K];  // LDS byte address of the table rows this column reads (see build_tables)
@@ -689,6 +707,11 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                 }
                 if (TR == 1) __builtin_nontemporal_store(pk, scr + static_cast<size_t>(t0 / UNR) * 64 + lane);
                 if (TR == 3 || TR == 5) scr[static_cast<size_t>(t0 / UNR) * 64 + lane] = pk;
+                if (TR == 5 && WLDS) {
+                    *reinterpret_cast<Word*>(s_code + code_ofs + lane * static_cast<int>(sizeof(Word))) = pk;
+                    code_ofs += 64 * static_cast<int>(sizeof(Word));
+                    if (code_ofs == code_ring_bytes) code_ofs = 0;
+                }
             }
             if (!GUARD) vnl = sel32(0, 1, m_vnl);
         };
@@ -888,8 +911,12 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                 if (MODE == 4) wsteps += nwin;
                 t_wa = min(((t_wa + UNR - 1) / UNR) * UNR, nwin);
                 t_wb = min(max((t_wb / UNR) * UNR, t_wa), nwin);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                // (MODE 3 reads snapshots next; the MODE 4 window reads nothing this wave wrote to global memory)
+                if (!WLDS) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                }
+                code_ofs = 0;
                 if (MODE == 3) {
                     const double* sp = snap + static_cast<size_t>(ts / SNAP_P) * (NSV * 64) + lane;
 #pragma unroll
@@ -922,8 +949,18 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                 run(Flag<true>{}, Int<TR_WIN>{}, 0, t_wa);
                 run(Flag<false>{}, Int<TR_WIN>{}, t_wa, t_wb);
                 run(Flag<true>{}, Int<TR_WIN>{}, t_wb, nwin);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                // WLDS: the walk reads the ring its own wave wrote, in LDS order; the tile's fences wait for the first word
+                // a walk takes from it (tile_word)
+                if (WLDS) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                } else {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                }
+                // WLDS: the window's last block and its ring slot; block b <= last_blk sits (last_blk - b) slots before it
+                const int last_blk = nwin / UNR - 1;
+                const int last_ofs = (code_ofs ? code_ofs : code_ring_bytes) - 64 * static_cast<int>(sizeof(Word));
+                bool tile_fenced = false;
                 // rows above this one hold no cell of the full DP (MODE 4 with a fresh boundary)
                 const int rtop = (MODE == 4 && ts > 0) ? ts : 0;
                 if (MODE == 4) {
@@ -938,13 +975,38 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                 }
 
                 // ---- leaders walk (src/reference_align.cpp:231-278) until done or out of window ----
-                if (pending && leader) {
+                // WLDS: the eight lanes of an alignment walk together.  Every lane carries the leader's state and runs the
+                // leader's code, so the group stays in step; in a run of diagonal moves, most of the path, lane m looks at
+                // the cell m steps up the diagonal and a ballot gives the length of the run: one LDS round trip for up to
+                // eight cells.  Only the leader writes outputs and lists.
+                constexpr bool GWALK = WLDS;
+                if (pending && (GWALK || leader)) {
+                    // the code word of lane `ln` at step tt >= 0 of the window: from the ring while the block is one of its
+                    // last win_nb, else from the global tile (`counted`: the read goes into align_walk_global)
+                    auto tile_word = [&](int tt, int ln, bool counted) -> Word {
+                        const unsigned b = static_cast<unsigned>(tt) / UNR;
+                        if (WLDS) {
+                            const unsigned back = static_cast<unsigned>(last_blk) - b;
+                            if (back < static_cast<unsigned>(A.win_nb)) {
+                                int o = last_ofs - static_cast<int>(back) * 64 * static_cast<int>(sizeof(Word));
+                                o += o < 0 ? code_ring_bytes : 0;
+                                return *reinterpret_cast<const Word*>(s_code + o + ln * static_cast<int>(sizeof(Word)));
+                            }
+                            if (!tile_fenced) {   // this wave's tile stores, past its L1
+                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                                tile_fenced = true;
+                            }
+                            walk_glob += counted ? 1 : 0;
+                        }
+                        return wtile[b * 64u + static_cast<unsigned>(ln)];
+                    };
                     // raw compare bits of cell (rr, cc), see nibble() below; false: above the window
                     auto code_at = [&](int cc, int rr, unsigned& out) -> bool {
                         const int jj = (cc - 1) / K, kk = (cc - 1) % K;
                         const int tt = rr + jj - ts;
                         if (tt < 0 || rr < rtop) return false;
-                        const Word w = wtile[static_cast<size_t>(tt / UNR) * 64 + lane_of(g, jj)];
+                        const Word w = tile_word(tt, lane_of(g, jj), leader);
                         out = static_cast<unsigned>(w >> (4 * (CELLS - 1 - ((tt % UNR) * K + kk)))) & 15u;
                         return true;
                     };
@@ -952,14 +1014,38 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                     while (c > 0 && !stalled) {
                         if (phase == 0) {
                             // runs of diagonal moves (most of the path) in a loop of their own
-                            while (c > 0 && row > 0) {
+                            while (!GWALK && c > 0 && row > 0) {
                                 const int jj = (c - 1) / K, kk = (c - 1) % K;
                                 const int tt = row + jj - ts;
                                 if (tt < 0 || row < rtop) break;
-                                const Word w = wtile[static_cast<unsigned>(tt / UNR) * 64u + static_cast<unsigned>(lane_of(g, jj))];
+                                const Word w = tile_word(tt, lane_of(g, jj), true);
                                 if (!((w >> (4 * (CELLS - 1 - ((tt % UNR) * K + kk)))) & 2u)) break;
                                 map[c] = row * 2 + 1;
                                 --row; --c;
+                            }
+                            while (GWALK && c > 0 && row > 0) {
+                                // lane m of the alignment: is cell (row - m, c - m) inside the window and a diagonal move?
+                                const int rr = row - j, cc = c - j;
+                                bool on = false;
+                                if (cc > 0 && rr > 0) {
+                                    const int jj = (cc - 1) / K, kk = (cc - 1) % K;
+                                    const int tt = rr + jj - ts;
+                                    if (tt >= 0 && rr >= rtop) {
+                                        const Word w = tile_word(tt, lane_of(g, jj), true);
+                                        on = ((w >> (4 * (CELLS - 1 - ((tt % UNR) * K + kk)))) & 2u) != 0;
+                                    }
+                                }
+                                // the alignment's eight lanes (every second lane of its DPP row) are all here; its bits of
+                                // the ballot, packed: bit m = lane m's cell ends the run
+                                const mask_t off_m = __builtin_amdgcn_ballot_w64(!on);
+                                unsigned x = static_cast<unsigned>(off_m >> lane_of(g, 0)) & 0x5555u;
+                                x = (x | (x >> 1)) & 0x3333u;
+                                x = (x | (x >> 2)) & 0x0f0fu;
+                                x = (x | (x >> 4)) & 0xffu;
+                                const int len = __builtin_ctz(x | 0x100u);   // diagonal moves from (row, c) on, 8 at most
+                                if (j < len) map[cc] = rr * 2 + 1;
+                                row -= len; c -= len;
+                                if (len < 8) break;
                             }
                             if (c <= 0) break;
                             if (row <= 0) { map[c] = (row + 1) * 2; --c; continue; }  // D[c][0] = 1
@@ -993,13 +1079,19 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
                             phase = 0;
                         }
                     }
+                    if (GWALK) {   // a walk any of whose lanes read the tile left the ring
+                        const mask_t out_m = __builtin_amdgcn_ballot_w64(tile_fenced);
+                        if (leader && ((out_m >> lane_of(g, 0)) & 0x5555u)) ++walks_out;
+                    }
                     if (MODE == 4 && stalled) {
-                        atomicAdd(A.loc_stats + 1, 1);
-                        push_redo();
+                        if (leader) {
+                            atomicAdd(A.loc_stats + 1, 1);
+                            push_redo();
+                        }
                         pending = 0;
                     }
-                    if (!stalled) {
-                        pending = 0;
+                    if (!stalled) pending = 0;
+                    if (!stalled && leader) {
                         // (src/reference_align.cpp:307-351), size_t wrap kept via unsigned
                         auto interval = [&](int a, int b, bool gaps, unsigned& s, unsigned& e) {
                             if (!gaps) {
@@ -1131,6 +1223,8 @@ __global__ void __launch_bounds__(64 * NWAVES, MODE >= 5 ? LOC_WAVES : (MODE == 
         }
     }
     if (MODE == 4 && lane == 0 && wsteps) atomicAdd(reinterpret_cast<unsigned long long*>(A.loc_stats + 4), static_cast<unsigned long long>(wsteps));
+    if (WLDS && walks_out) atomicAdd(A.loc_stats + 3, walks_out);
+    if (WLDS && walk_glob) atomicAdd(reinterpret_cast<unsigned long long*>(A.loc_stats + 6), static_cast<unsigned long long>(walk_glob));
 }
 
 // Empty reference: the DP has only column 0 (src/reference_align.cpp:63-78,:104).
@@ -2030,8 +2124,24 @@ static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStre
         else hipLaunchKernelGGL((k_align<K, 5, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
         AlignArgs r = a;
         r.bad_done = 1;
+        // the windows: with the code ring in LDS behind the maps (three wavefronts per SIMD), or the tile alone
+        const size_t lds4 = lds + static_cast<size_t>(NWAVES) * a.win_nb * 64 * sizeof(uint32_t);
+        auto windows = [&](const AlignArgs& w) -> int {
+            if (!a.win_nb) {
+                hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, w);
+                return 0;
+            }
+            static thread_local size_t lds_set = 0;   // (per instantiation: the attribute is raised once, not at every launch)
+            if (lds4 > 48 * 1024 && lds4 > lds_set) {
+                SL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_align<K, 4, true, 2, KLAST, false, true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds4)));
+                lds_set = lds4;
+            }
+            hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false, true>), dim3(grid), dim3(64 * NWAVES), lds4, s, w);
+            return 0;
+        };
         if (!ll) {
-            hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
+            SL_TRY(windows(a));
             r.read_list = a.loc_redo;
             hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, r);
         } else {
@@ -2049,7 +2159,7 @@ static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStre
             AlignArgs w = a;
             w.read_list = ll->order;
             w.bad_done = 1;
-            hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, w);
+            SL_TRY(windows(w));
             SL_HIP(hipStreamWaitEvent(s, ll->join, 0));
             r.read_list = a.loc_redo;
             hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(ll->redo_grid), dim3(64 * NWAVES), lds, s, r);
@@ -2367,6 +2477,19 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     const size_t lds = sizeof(uint16_t) * NWAVES * (sh.rowf == 2 ? NGMAX2 * (RING + RING_MIRROR) : NGMAX * RING_SLOT) + sizeof(double) * rows.size() +
                        sizeof(int32_t) * NWAVES * sh.ngroups * (R + 1) + 16;
     if (!wide && lds > 64 * 1024) return fail("sarlacc_amd: alignment tables do not fit in LDS");
+    // MODE 4: the window's codes also in an LDS ring of win_nb blocks per wavefront behind the maps (WIN_LDS_WAVES), as many
+    // blocks as the 64 KB leave at most.  align_window_lds = -1: the global tile alone (A/B, tests); >= 2: that many blocks
+    // (tests: a small ring wraps often and sends most walks to the tile)
+    int win_nb = 0;
+    if (kernel_mode == 4 && option(OPT_ALIGN_WINDOW_LDS) >= 0) {
+        const int tile_blocks = snap_win(R, sh.W) / tb_steps;
+        win_nb = option(OPT_ALIGN_WINDOW_LDS) >= 2 ? option(OPT_ALIGN_WINDOW_LDS) : win_ring_blocks(R, sh.W, tb_steps);
+        win_nb = std::min(win_nb, tile_blocks);
+        const size_t block_bytes = static_cast<size_t>(NWAVES) * 64 * sizeof(uint32_t);
+        win_nb = static_cast<int>(std::min<size_t>(win_nb, (64 * 1024 - lds) / block_bytes));
+        if (win_nb < 2) win_nb = 0;
+    }
+    a.win_nb = win_nb;
     if (co.stage) SL_TRY(c.stage_begin(co.stage, stream));
     else SL_HIP(hipEventRecord(c.ev_start, stream));
     if (wide) SL_TRY(launch_wide(a, R, kernel_mode == 3 ? 1 : kernel_mode, max_len, n, stream));
@@ -2396,6 +2519,12 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
         unsigned long long wsteps = 0;
         std::memcpy(&wsteps, lstats + 4, sizeof wsteps);
         c.counts["align_window_steps"] = d_stats ? static_cast<double>(wsteps) : -1.0;
+        // the code words walks read from the global tile and the walks that read any, the others having stayed in the LDS
+        // ring (-1: the call ran without the ring)
+        unsigned long long wglob = 0;
+        std::memcpy(&wglob, lstats + 6, sizeof wglob);
+        c.counts["align_walk_global"] = d_stats && win_nb ? static_cast<double>(wglob) : -1.0;
+        c.counts["align_walk_left_ring"] = d_stats && win_nb ? lstats[3] : -1.0;
         // reads per window class (a class is 8 steps) of the call's last launch, "align_window_class_<c>": diagnostic, for
         // the tests and the perf records
         static const std::vector<std::string> class_keys = [] {

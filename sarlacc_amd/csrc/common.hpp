@@ -71,6 +71,7 @@ enum Opt {
     OPT_ALIGN_PANEL,          // barcode panel: -1 every barcode by run_align + the device fold instead of the fused kernel (A/B, cross-check)
     OPT_PROFILE_CHUNK_READS,  // profile_reads: reads per chunk of the batch (0 = by the byte budget of the aligner's scratch; tests force several chunks)
     OPT_ALIGN_WINDOW_CLASSES, // adaptor_align by the locator: -1 the windows in index order, one redo list filled by the window kernel and its launch on the caller's stream (A/B, tests)
+    OPT_ALIGN_WINDOW_LDS,     // adaptor_align by the locator: -1 the window's codes in the global tile alone, five wavefronts per SIMD (A/B, tests); >= 2 that many blocks in the LDS code ring (tests)
     OPT_N
 };
 int option(Opt o);
