@@ -352,6 +352,37 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
                             uint8_t* d_strand, int32_t* d_lclip, int32_t* d_rclip, uint8_t* d_names,
                             int64_t* d_name_off, void* stream);
 
+/* BGZF input (blocked gzip: SAM specification section 4.1, RFC 1951 / RFC 1952): compressed FASTQ and SAM files are
+ * inflated on the device, so that the compressed bytes cross the bus and the text never visits the host.
+ * sarlacc_bgzf_scan needs no device.  buf holds nbytes of a file from the start of a block on and may end inside a
+ * block.  It walks the gzip member headers (ID 1f 8b, CM 8, FLG with FEXTRA, a 'BC' subfield of length 2 holding
+ * BSIZE, found among any other subfields) of at most max_blocks blocks and fills comp_off (block k is the bytes
+ * comp_off[k] .. comp_off[k + 1] of buf) and text_off (the running sum of the ISIZE fields), max_blocks + 1 entries
+ * each; *n_blocks is the number of complete blocks, *used_bytes what they occupy, *last_is_eof whether the last of
+ * them is the 28-byte empty end-of-file block (a file without one is not an error).  Errors, K the 1-based block
+ * number counted from first_block: "BGZF block K: not a gzip member", "... no BC subfield" (how a plain gzip file is
+ * recognised), "... block size field is inconsistent" (BSIZE + 1 below header + trailer), "... uncompressed size
+ * exceeds 65536".  Bytes left over at the end of a file are the caller's error ("file ends inside BGZF block K").
+ * sarlacc_dev_bgzf_inflate inflates block k of d_comp, header and trailer as in the file, into
+ * d_text[d_text_off[k] .. d_text_off[k + 1]); d_text and every block's output may have any alignment.  All of
+ * RFC 1951 is read: stored, fixed and dynamic blocks, any number per BGZF block.  With check_crc the trailer's
+ * ISIZE and CRC-32 are held against the output.  The lowest failing block is the error, "BGZF block K: <reason>" with
+ * K counted from first_block and reason one of: invalid stored block, invalid code lengths, invalid symbol,
+ * distance beyond the start of the block, output exceeds the size field, compressed data ends early, length
+ * mismatch, CRC32 mismatch.  Nothing is written outside a block's own range of d_text, whatever the input.
+ * n_blocks == 0 succeeds without a launch.  The call returns when the device has finished.
+ * sarlacc_dev_copy copies bytes within device memory (ranges that do not overlap, any alignment): the tail of one
+ * text buffer to the front of the next.  sarlacc_dev_rfind_byte reports the position of the last byte of d_text equal
+ * to value (-1: none): where a block of lines ends.  Both return when the device has finished.
+ * Out of scope: compressed output, BAM records, random access via .gzi, device inflate of gzip that is not BGZF
+ * (the Python layer inflates that on the host). */
+int sarlacc_bgzf_scan(const uint8_t* buf, int64_t nbytes, int64_t max_blocks, int64_t first_block, int64_t* comp_off,
+                      int64_t* text_off, int64_t* n_blocks, int64_t* used_bytes, int* last_is_eof);
+int sarlacc_dev_bgzf_inflate(const uint8_t* d_comp, const int64_t* d_comp_off, const int64_t* d_text_off, int64_t n_blocks,
+                             int64_t first_block, uint8_t* d_text, int check_crc, void* stream);
+int sarlacc_dev_copy(void* d_dst, const void* d_src, int64_t bytes, void* stream);
+int sarlacc_dev_rfind_byte(const uint8_t* d_text, int64_t nbytes, int value, int64_t* pos, void* stream);
+
 /* ------------------------------------------------------------------ */
 /* masked Levenshtein, neighbour search, clustering                      */
 

@@ -47,9 +47,11 @@ class Reads:
 
 def read_fastq(path):
     """4-line FASTQ -> Reads (the reference streams with ShortRead::FastqStreamer,
-    R/adaptorAlign.R:26-37).  Host reader; resident.DeviceReads.from_fastq parses on the device."""
+    R/adaptorAlign.R:26-37).  Host reader; resident.DeviceReads.from_fastq parses on the device.  A gzip or BGZF file
+    is read through Python's gzip module."""
+    from .bgzf import open_text
     names, seqs, quals = [], [], []
-    with open(path, "rb") as fh:
+    with open_text(path) as fh:
         while True:
             h = fh.readline()
             if not h:
@@ -232,7 +234,9 @@ def adaptorAlign(adaptor1, adaptor2, reads, tolerance=250, gapOpening=5, gapExte
     the resident windows (no host pass over the bases); `qual_type` ("phred", "solexa" or "illumina",
     match.arg semantics) names the quality class the file is read with (.qual2class, :97-99) and hence
     the encoding vector of every alignment.  A Reads object is accepted as well (one chunk; it carries
-    its own encoding, so `qual_type` only lands in the metadata)."""
+    its own encoding, so `qual_type` only lands in the metadata).  The file may be plain text, BGZF or plain gzip, as the
+    reference's FastqStreamer reads `.fastq.gz`: BGZF blocks are inflated on the device, plain gzip by zlib on the host
+    (bgzf.py); `metadata["filepath"]` keeps the path as given, and realizeReads reads the same file again."""
     adaptor1, adaptor2 = str(adaptor1).upper(), str(adaptor2).upper()
     qual_type, enc = encoding_for_qual_type(qual_type)
     filepath = None
@@ -740,6 +744,7 @@ def sam2ranges(sam, minq=10, restricted=None, block_bytes=256 << 20):
     place of the GRanges: "seqnames" (int32 codes into seqinfo["seqnames"], a factor), "start", "end", "width",
     "left.clip", "right.clip" (int32), "strand" ('+' / '-'), "names" (the QNAMEs) and "seqinfo" ({"seqnames": the @SQ
     names then '*', "seqlengths": int64, 0 for '*'}).  A header-only or empty file returns the empty result without a
-    device.  Departures from the reference: DESIGN.md §8, "Known deviations"."""
+    device.  A BGZF file (`.sam.gz` by bgzip) has its header inflated on the host and its body on the device; plain gzip is
+    inflated on the host (slow).  Departures from the reference: DESIGN.md §8, "Known deviations"."""
     from .sam import sam2ranges as _sam2ranges
     return _sam2ranges(sam, minq=minq, restricted=restricted, block_bytes=block_bytes)

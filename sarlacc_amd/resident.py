@@ -70,13 +70,24 @@ class DeviceReads:
     def from_fastq(cls, source, encoding=None):
         """FASTQ text (path, bytes or uint8 array) -> resident batch, parsed on the device
         (sarlacc_dev_fastq_index / _extract; replaces FastqStreamer + .FASTQ2QSDS,
-        R/adaptorAlign.R:26-37,:104-110).  Read names are kept on the host in `.names`."""
+        R/adaptorAlign.R:26-37,:104-110).  Read names are kept on the host in `.names`.  A path may name a plain, gzip or
+        BGZF file (bgzf.sniff): BGZF is inflated on the device, plain gzip by zlib on the host (slow, for correctness only)."""
         if isinstance(source, (bytes, bytearray)):
             text = np.frombuffer(bytes(source), dtype=np.uint8)
         elif isinstance(source, np.ndarray):
             text = np.ascontiguousarray(source, dtype=np.uint8)
         else:
-            text = np.fromfile(source, dtype=np.uint8)
+            from . import bgzf
+            kind = bgzf.sniff(source)
+            if kind == bgzf.BGZF:    # inflated on the device: the text never visits the host
+                with open(source, "rb") as fh:
+                    d_text, nbytes, _ = bgzf.DeviceTextStream(fh, None).next()
+                return cls._from_device_text(d_text if d_text is not None else DevBuffer(1), nbytes, encoding)
+            if kind == bgzf.GZIP:    # the slow path: one zlib thread on the host
+                with open(source, "rb") as fh:
+                    text = np.frombuffer(bgzf.GzipReader(fh).read(), dtype=np.uint8)
+            else:
+                text = np.fromfile(source, dtype=np.uint8)
         d_text = DevBuffer.from_numpy(text if text.size else np.zeros(1, np.uint8))
         return cls._from_device_text(d_text, text.size, encoding)
 
@@ -100,12 +111,22 @@ class DeviceReads:
         FastqStreamer(filepath, n=number) + yield() loop of R/adaptorAlign.R:26-37.  The file is read in
         blocks of `block_bytes`; where a block ends inside a record the device reports the end of the
         last complete one (sarlacc_dev_fastq_split) and the rest is carried over to the next block, so
-        neither the host nor the device ever holds more than one block plus one chunk."""
+        neither the host nor the device ever holds more than one block plus one chunk.  A BGZF file is inflated on the
+        device, whole BGZF blocks worth `block_bytes` of text at a time, and the carry-over stays there (_stream_bgzf); a
+        plain gzip file is inflated by zlib on the host into the text route (slow, for correctness only).  The chunks
+        and the error messages are those of the text."""
         number = int(number)
         if number < 1:
             raise ValueError("'number' must be a positive integer")
+        from . import bgzf
+        kind = bgzf.sniff(path)
         carry = np.zeros(0, np.uint8)
         with open(path, "rb") as fh:
+            if kind == bgzf.BGZF:
+                yield from cls._stream_bgzf(fh, number, encoding, block_bytes)
+                return
+            if kind == bgzf.GZIP:
+                fh = bgzf.GzipReader(fh)     # the slow path: inflated by zlib on the host, then as text
             eof = False
             while not eof:
                 fresh = np.frombuffer(fh.read(int(block_bytes)), dtype=np.uint8)
@@ -128,6 +149,31 @@ class DeviceReads:
                     if len(chunk):
                         yield chunk
                 carry = text[pos:].copy()
+
+    @classmethod
+    def _stream_bgzf(cls, fh, number, encoding, block_bytes):
+        """stream_fastq over a BGZF file: whole blocks worth about `block_bytes` of text are inflated on the device behind
+        the unused tail of the buffer before, which is copied on the device; the chunks are those of the text route."""
+        from . import bgzf
+        stream, carry, eof = bgzf.DeviceTextStream(fh, block_bytes), None, False
+        while not eof:
+            d_text, nbytes, eof = stream.next(carry)
+            if d_text is None or nbytes == 0:
+                break
+            pos = 0
+            while pos < nbytes:
+                nrec, used = C.c_int64(0), C.c_int64(0)
+                here = d_text.ptr.value + pos
+                check(_lib.lib().sarlacc_dev_fastq_split(here, nbytes - pos, number, C.byref(nrec), C.byref(used), None))
+                if nrec.value < number and not eof:
+                    break                           # the chunk continues in the next blocks
+                if nrec.value < number:
+                    used.value = nbytes - pos
+                chunk = cls._from_device_text(here, used.value, encoding)
+                pos += used.value
+                if len(chunk):
+                    yield chunk
+            carry = (d_text, pos, nbytes - pos) if pos < nbytes else None
 
     def __len__(self):
         return len(self.off_host) - 1

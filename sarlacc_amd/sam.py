@@ -166,27 +166,94 @@ def blocks(fh, block_bytes):
         yield text[:cut] if carry else text
 
 
-def sam2ranges(sam, minq=10, restricted=None, block_bytes=256 << 20):
-    """sam2ranges (R/sam2ranges.R:8-95).  See generics.sam2ranges."""
+def _text_parts(fh, block_bytes, restricted, use_minq, thr):
+    """(seqinfo names, lengths, parsed blocks) of a file of SAM text opened in binary mode; no blocks: an empty result."""
     from .resident import DevBuffer
+    names, lengths, nhead, ended = read_header(fh)
+    if ended:
+        return names, lengths, []          # :42-46, before any data is read
+    first = fh.read(1 << 16)
+    if len(first) < 1 << 16 and not first.lstrip(b"\r\n"):
+        return names, lengths, []          # a body of blank lines only
+    fh.seek(-len(first), 1)
+    tables = _Tables(names, restricted)
+    parts, line = [], nhead + 1
+    for text in blocks(fh, block_bytes):
+        d_text = DevBuffer.from_numpy(np.frombuffer(text, np.uint8))
+        nlines, cols = _parse_block(d_text, len(text), line, tables, use_minq, thr)
+        line += nlines
+        parts.append(cols)
+    return names, lengths, parts
+
+
+def _bgzf_header(fh):
+    """The header of a BGZF SAM file, inflated on the host with zlib, leading blocks only, up to the first body line:
+    (header lines, (file offset, number) of the block that holds the first body byte and that byte's offset in the
+    block's text -- None when the file ends inside the header)."""
+    from . import bgzf
+    lines, pending, origin = [], b"", None
+    for offset, number, text in bgzf.host_blocks(fh):
+        p = 0
+        if not pending:
+            origin = (offset, number, 0)
+        while pending or p < len(text):
+            if (pending[:1] or text[p:p + 1]) != b"@":
+                return lines, origin
+            nl = text.find(b"\n", p)
+            if nl < 0:
+                pending += text[p:]
+                break
+            lines.append(_strip_eol(pending + text[p:nl + 1]))
+            pending, p = b"", nl + 1
+            origin = (offset, number, p)
+    if pending:
+        lines.append(_strip_eol(pending))
+    return lines, None
+
+
+def _bgzf_parts(path, block_bytes, restricted, use_minq, thr):
+    """_text_parts for a BGZF file: the body is inflated on the device from the block that holds its first byte; a parse
+    block ends at the last newline of the device text (sarlacc_dev_rfind_byte) and the rest is carried over on the device."""
+    from . import bgzf
+    with open(path, "rb") as fh:
+        lines, origin = _bgzf_header(fh)
+        names, lengths = parse_header(lines)
+        if origin is None:
+            return names, lengths, []
+        fh.seek(origin[0])
+        stream = bgzf.DeviceTextStream(fh, block_bytes, first_block=origin[1], skip=origin[2])
+        tables = _Tables(names, restricted)
+        parts, line, carry, eof, first = [], len(lines) + 1, None, False, True
+        while not eof:
+            d_text, nbytes, eof = stream.next(carry)
+            if d_text is None or nbytes == 0:
+                break
+            if first and eof and nbytes < 1 << 16:     # a body of blank lines only (a small file: the only host look at body text)
+                from .resident import DevBuffer
+                if not DevBuffer.borrow(d_text.ptr.value, nbytes).to_numpy(np.uint8, nbytes).tobytes().lstrip(b"\r\n"):
+                    return names, lengths, []
+            first = False
+            cut = nbytes if eof else bgzf.rfind_newline(d_text, 0, nbytes)
+            if cut:
+                nlines, cols = _parse_block(d_text, cut, line, tables, use_minq, thr)
+                line += nlines
+                parts.append(cols)
+            carry = (d_text, cut, nbytes - cut) if cut < nbytes else None    # (no line ends in this block yet: it grows)
+    return names, lengths, parts
+
+
+def sam2ranges(sam, minq=10, restricted=None, block_bytes=256 << 20):
+    """sam2ranges (R/sam2ranges.R:8-95).  See generics.sam2ranges.  `sam` may be plain text, BGZF (the body is inflated on
+    the device, bgzf.py) or plain gzip (inflated by Python's gzip module on the host: slow, for correctness only)."""
+    from . import bgzf
     use_minq, thr, restricted = check_args(minq, restricted)
     if int(block_bytes) < 1:
         raise ValueError("'block_bytes' must be a positive integer")
-    with open(sam, "rb") as fh:
-        names, lengths, nhead, ended = read_header(fh)
-        if ended:
-            return _empty(names, lengths)      # :42-46, before any data is read
-        first = fh.read(1 << 16)
-        if len(first) < 1 << 16 and not first.lstrip(b"\r\n"):
-            return _empty(names, lengths)      # a body of blank lines only
-        fh.seek(-len(first), 1)
-        tables = _Tables(names, restricted)
-        parts, line = [], nhead + 1
-        for text in blocks(fh, block_bytes):
-            d_text = DevBuffer.from_numpy(np.frombuffer(text, np.uint8))
-            nlines, cols = _parse_block(d_text, len(text), line, tables, use_minq, thr)
-            line += nlines
-            parts.append(cols)
+    if bgzf.sniff(sam) == bgzf.BGZF:
+        names, lengths, parts = _bgzf_parts(sam, block_bytes, restricted, use_minq, thr)
+    else:
+        with bgzf.open_text(sam) as fh:
+            names, lengths, parts = _text_parts(fh, block_bytes, restricted, use_minq, thr)
     if not parts:
         return _empty(names, lengths)
     ref, start, width, lclip, rclip, strand = (np.concatenate([p[k] for p in parts]) for k in range(6))
