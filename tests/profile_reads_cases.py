@@ -104,6 +104,87 @@ def cases():
     return {k: (ref, *make_reads(np.random.default_rng(len(ref) + n), ref, n)) for k, (ref, n) in out.items()}
 
 
+TILE = 2048      # reference positions per workgroup of k_profile_pairs (PR_TILE)
+DENSE = 64       # event lengths from here on go to the list (PR_DENSE)
+EDGE = (DENSE - 1, DENSE, DENSE + 1)
+
+
+def phred_quals(rng, reads):
+    return ["".join(chr(c) for c in rng.integers(33 + 2, 33 + 41, len(r))) for r in reads]
+
+
+def reference_runs(ref):
+    """(start, end) of the maximal stretches of two or more equal bases, 0-based, end exclusive"""
+    runs, a = [], 0
+    while a < len(ref):
+        b = a + 1
+        while b < len(ref) and ref[b] == ref[a]:
+            b += 1
+        if b - a > 1:
+            runs.append((a, b))
+        a = b
+    return runs
+
+
+def _insertion(rng, ref, p, k):
+    """k random bases to go in front of position p: they end in neither neighbour, so that they stay where they are put"""
+    around = (ref[p - 1] if p else "") + (ref[p] if p < len(ref) else "")
+    s = list(rand_seq(rng, k))
+    s[0] = next(c for c in "ACGT" if c not in around)
+    s[-1] = next(c for c in "TGCA" if c not in around)
+    return "".join(s)
+
+
+def tile_reads(rng, ref):
+    """Reads around the edge of the first tile: the reference, an empty read, insertions of 63, 64 and 65 bases in front of
+    position 0, near 1 000, at 2 048 and behind the last base, four runs (the first, one near 1 000, the first from 2 048
+    on or else the last but one, the last) lengthened to 63, 64 and 65 bases, a deletion of 100 bases across 2 000-2 100,
+    four noisy reads and the two halves of a fifth."""
+    R = len(ref)
+    reads = [ref, ""]
+    for p in sorted({0, min(1000, R), min(TILE, R), R}):
+        reads += [ref[:p] + _insertion(rng, ref, p, k) + ref[p:] for k in EDGE]
+    runs = reference_runs(ref)
+    beyond = [k for k, (a, _) in enumerate(runs) if a >= TILE]
+    picked = sorted({0, min(range(len(runs)), key=lambda k: abs(runs[k][0] - 1000)), beyond[0] if beyond else len(runs) - 2, len(runs) - 1})
+    for k in picked:
+        a, b = runs[k]
+        reads += [ref[:a] + ref[a] * w + ref[b:] for w in EDGE]
+    reads.append(ref[:2000] + ref[min(2100, R):])
+    reads += [noisy(rng, ref, 0.05) for _ in range(4)]
+    half = noisy(rng, ref, 0.05)
+    reads += [half[:len(half) // 2], half[len(half) // 2:]]
+    return reads
+
+
+# name -> (reference, reads, qualities) at the boundaries of k_profile_pairs beyond one tile: references of one tile less
+# a base, one tile, one tile and a base and three tiles; the last two with a run of G across the edge (positions 2 044-2 051,
+# as far as the reference goes)
+def long_cases():
+    out = {}
+    for R in (TILE - 1, TILE, TILE + 1, 4100):
+        rng = np.random.default_rng(R)
+        ref = rich_reference(rng, R)
+        if R > TILE:
+            ref = (ref[:TILE - 4] + "G" * 8 + ref[TILE + 4:])[:R]
+        reads = tile_reads(rng, ref)
+        out["r%d" % R] = (ref, reads, phred_quals(rng, reads))
+    return out
+
+
+def stride_case(n, seed=40):
+    """(reference of 40 bases, n reads, qualities): drawn with replacement from 300 noisy reads, an empty read and one read
+    with an insertion of 70 bases (twice at least), one quality string per distinct read -- more alignments than one sweep of
+    the persistent grid walks, and a list event with a multiplicity"""
+    rng = np.random.default_rng(seed)
+    ref = rich_reference(rng, 40)
+    pool = [noisy(rng, ref) for _ in range(300)] + ["", ref[:20] + _insertion(rng, ref, 20, 70) + ref[20:]]
+    quals = phred_quals(rng, pool)
+    pick = rng.integers(0, len(pool), n)
+    pick[[n // 3, n - 1]] = len(pool) - 1
+    return ref, [pool[k] for k in pick], [quals[k] for k in pick], pool[-1]
+
+
 def chain_expected(oracle, oenc, ref, reads, quals, go=5, ge=1):
     """The oracle chain: (scores, edits, errorFinder result, homopolymerMatcher result), lists not folded."""
     scores, edits, aref, aqry = oracle.general_align(reads, quals, oenc, go, ge, ref, False)

@@ -1,10 +1,12 @@
 """GPU parity of the alignment-profiling routines through the C ABI: the literal alignment strings of
 the reference's tests (tests/testthat/test-homopolymer.R, test-error.R; tests/profile_cases.py) and random gapped
-alignments against the CPU oracle -- integer lists, identical including their order."""
+alignments against the CPU oracle -- integer lists, identical including their order; and the structured strings of
+tests/profile_walk_cases.py, whose features span whole 64-character steps of the walks."""
 import numpy as np
 import pytest
 
 from tests.profile_cases import ERROR_CASES, FIND_SEQS, MATCH_CASES, checkfun, findcheck, matchcheck
+from tests.profile_walk_cases import by_reference, family, random_pairs
 
 pytestmark = pytest.mark.gpu
 
@@ -105,3 +107,176 @@ def test_find_errors(oracle):
             calls.find_errors(rf, rd)
         with pytest.raises(oracle.OracleError, match=msg):
             oracle.find_errors(rf, rd)
+
+
+# ---- what the walks carry from step to step: the structured family and the random pairs of tests/profile_walk_cases.py,
+# ---- whose features (gap runs, runs, runs split by gaps) span one to three 64-character steps at every phase
+@pytest.fixture(scope="module")
+def walk_pairs():
+    return [(rf, rd) for _, rf, rd in family()] + list(random_pairs())
+
+
+def with_empties(xs, where):
+    xs = list(xs)
+    for k in where:
+        xs[k] = ""
+    return xs
+
+
+def test_family_find_homopolymers(oracle, walk_pairs):
+    from sarlacc_amd import calls
+    for seqs in ([rf for rf, _ in walk_pairs], [rd for _, rd in walk_pairs]):
+        got = calls.find_homopolymers(seqs)
+        assert len(got[0]) > len(seqs) // 2
+        same(got, oracle.find_homopolymers(seqs))
+
+
+def test_family_match_homopolymers(oracle, walk_pairs):
+    from sarlacc_amd import calls
+    refs, reads = [rf for rf, _ in walk_pairs], [rd for _, rd in walk_pairs]
+    got = calls.match_homopolymers(refs, reads)
+    assert len(got[0]) > len(refs) // 2
+    same(got, oracle.match_homopolymers(refs, reads))
+    # the reads the restated checker decides by the run proper: 0 in the extension only, everything with one base of it
+    named = [(n, rf, rd) for n, rf, rd in family() if n[0] in "df" and n.split(":")[-1] in ("iv", "v")]
+    got = calls.match_homopolymers([rf for _, rf, _ in named], [rd for _, _, rd in named])
+    assert np.asarray(got[2]).tolist() == [0 if n.endswith(":iv") else int(n.split(":")[2]) + 1 for n, _, _ in named]
+    assert [np.asarray(x).tolist() for x in got[1:]] == [sum((matchcheck(rf, rd)[k] for _, rf, rd in named), []) for k in (0, 1)]
+
+
+def test_family_find_errors(oracle, walk_pairs):
+    from sarlacc_amd import calls
+    groups = by_reference(walk_pairs)
+    for refs, reads in groups.values():
+        same(calls.find_errors(refs, reads), oracle.find_errors(refs, reads))
+    refs, reads = max(groups.values(), key=lambda g: len(g[0]))
+    assert len(refs) >= 30 and max(map(len, refs)) > 192
+    got = calls.find_errors(refs, reads)
+    want = checkfun(refs, reads)
+    assert got[0] == want[0] and [np.asarray(x).tolist() for x in got[1:6]] == list(want[1:6])
+    ins = {}
+    for p, l in zip(np.asarray(got[6]).tolist(), np.asarray(got[7]).tolist()):
+        ins.setdefault(p, []).append(l)
+    assert {p: sorted(v) for p, v in ins.items()} == want[6]
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 8193])
+def test_list_sizes_around_the_workgroup(oracle, walk_pairs, n):
+    """PF_WAVES = 4 strings per workgroup: lists that fill a workgroup partly, exactly, with one string over, and a long
+    one; empty strings at the front, in the middle and at the end"""
+    from sarlacc_amd import calls
+    start = next(k for k, (rf, _) in enumerate(walk_pairs) if len(rf) > 256)
+    pairs = [walk_pairs[(start + k) % len(walk_pairs)] for k in range(n)]
+    holes = sorted({0, n // 2, n - 1})
+    for where in ([], holes):
+        refs, reads = with_empties([rf for rf, _ in pairs], where), with_empties([rd for _, rd in pairs], where)
+        same(calls.find_homopolymers(refs), oracle.find_homopolymers(refs))
+        same(calls.find_homopolymers(reads), oracle.find_homopolymers(reads))
+        same(calls.match_homopolymers(refs, reads), oracle.match_homopolymers(refs, reads))
+    # find_errors: alignments of one reference (the first one says which), the empty ones behind it
+    grefs, greads = max(by_reference(walk_pairs).values(), key=lambda g: len(g[0]))
+    refs, reads = [grefs[k % len(grefs)] for k in range(n)], [greads[k % len(grefs)] for k in range(n)]
+    for where in ([], holes[1:]):
+        a, b = with_empties(refs, where), with_empties(reads, where)
+        same(calls.find_errors(a, b), oracle.find_errors(a, b))
+
+
+def capacities(monkeypatch):
+    """the capacities calls._grow hands out from here on"""
+    from sarlacc_amd import calls
+    seen, grow = [], calls._grow
+
+    def recording(cap, need):
+        for c in grow(cap, need):
+            seen.append(c)
+            yield c
+    monkeypatch.setattr(calls, "_grow", recording)
+    return seen
+
+
+def test_sizing_protocol_second_call(oracle, monkeypatch):
+    """results larger than the first capacity guess (total / 8 runs, total / 16 insertions): the sizing call reports the
+    size and the second call fills the lists"""
+    from sarlacc_amd import calls
+    seen = capacities(monkeypatch)
+    runs = ["AACCGGTT" * 200, "", "ACGT" * 100]
+    same(calls.find_homopolymers(runs), oracle.find_homopolymers(runs))
+    assert seen == [(1600 + 400) // 8, 800]
+    del seen[:]
+    same(calls.match_homopolymers(runs, runs), oracle.match_homopolymers(runs, runs))
+    assert seen == [(1600 + 400) // 8, 800]
+    del seen[:]
+    gapped = ["A-" * 400]
+    same(calls.find_errors(gapped, gapped), oracle.find_errors(gapped, gapped))
+    assert seen == [64, 400]
+    del seen[:]
+    same(calls.match_homopolymers(gapped, gapped), oracle.match_homopolymers(gapped, gapped))
+    same(calls.find_homopolymers(gapped), oracle.find_homopolymers(gapped))
+    assert seen == [100, 100]          # one run of 400 bases: the first guess holds it
+
+
+def test_find_errors_accumulates_over_alignments(oracle):
+    """5 000 alignments of one 130-base reference, each with an insertion of 64 bases in front of base 64 (a whole step
+    of gaps, listed at the next step's first character), every seventh with a short second one, noisy reads"""
+    from sarlacc_amd import calls
+    rng = np.random.default_rng(130)
+    ref = "".join("ACGT"[(k + k // 7) % 4] for k in range(130))
+    noise = np.where(rng.random((5000, 130)) > 0.1, np.frombuffer(ref.encode(), np.uint8), np.frombuffer(b"ACGT-", np.uint8)[rng.integers(0, 5, (5000, 130))])
+    inserted = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, (5000, 64))]
+    refs, reads = [], []
+    for i in range(5000):
+        rd = noise[i].astype(np.uint8).tobytes().decode()
+        a, b = ref[:64] + "-" * 64 + ref[64:], rd[:64] + inserted[i].tobytes().decode() + rd[64:]
+        if i % 7 == 0:
+            k = 1 + i % 3
+            a, b = a[:-20] + "-" * k + a[-20:], b[:-20] + "T" * k + b[-20:]
+        refs.append(a); reads.append(b)
+    got = calls.find_errors(refs, reads)
+    want = checkfun(refs, reads)
+    assert got[0] == want[0] == ref and [np.asarray(x).tolist() for x in got[1:6]] == list(want[1:6])
+    assert sum(int(np.asarray(got[k]).sum()) for k in range(1, 6)) == 5000 * 130
+    pos, lens = np.asarray(got[6]).tolist(), np.asarray(got[7]).tolist()
+    assert [l for p, l in zip(pos, lens) if p == 64] == [64] * 5000
+    assert [(p, l) for p, l in zip(pos, lens) if p != 64] == [(110, 1 + i % 3) for i in range(0, 5000, 7)]
+    same(got, oracle.find_errors(refs, reads))
+
+
+def test_find_errors_precedence_beyond_the_first_step(oracle):
+    """the error the reference's loop meets first -- alignment by alignment, left to right -- where the characters lie in
+    the second and third step of a string"""
+    from sarlacc_amd import SarlaccError, calls
+    ref = "".join("ACGT"[(k + k // 5) % 4] for k in range(131))
+
+    def put(s, k, c):
+        return s[:k] + c + s[k + 1:]
+    long_ref = ref + "AC"                     # bases 131 and 132 are more than the first alignment's reference holds
+    gapped = ref[:10] + "-" * 70 + ref[10:]   # index = position + 70 behind the gaps
+    cases = [
+        # an unknown character far into alignment 0 against one at the very start of alignment 1
+        ([ref, ref], [put(ref, 70, "N"), put(ref, 0, "X")], "unknown character 'N'"),
+        ([ref, ref], [put(ref, 130, "N"), put(ref, 0, "X")], "unknown character 'N'"),
+        ([gapped, ref], [put(gapped, 150, "N"), put(ref, 0, "X")], "unknown character 'N'"),
+        # an unknown character and a reference that is too long in one alignment: whichever comes first by position
+        ([ref, long_ref], [ref, put(long_ref, 70, "N")], "unknown character 'N'"),
+        ([ref, long_ref], [ref, put(long_ref, 130, "N")], "unknown character 'N'"),
+        ([ref, long_ref], [ref, put(long_ref, 132, "N")], "same for all alignments"),
+        ([ref, long_ref], [ref, put(long_ref, 131, "N")], "same for all alignments"),     # in the same column
+        ([ref, ref[:64] + "-" * 64 + long_ref[64:]], [ref, put(ref[:64] + "A" * 64 + long_ref[64:], 131 + 64, "N")], "same for all alignments"),
+        ([ref, ref, long_ref], [put(ref, 129, "X"), ref, put(long_ref, 3, "N")], "unknown character 'X'"),
+        # a length mismatch in alignment 2 against an unknown character in alignment 1
+        ([ref, ref, ref], [ref, put(ref, 130, "N"), ref[:-1]], "unknown character 'N'"),
+        ([ref, ref, ref], [ref, ref[:-1], put(ref, 130, "N")], "equal length"),
+        ([ref, long_ref, ref], [ref, long_ref, ref[:-1]], "same for all alignments"),
+    ]
+    for refs, reads, msg in cases:
+        with pytest.raises(SarlaccError, match=msg) as g:
+            calls.find_errors(refs, reads)
+        with pytest.raises(oracle.OracleError, match=msg) as o:
+            oracle.find_errors(refs, reads)
+        assert str(g.value) == str(o.value)
+    # an unknown character opposite reference gaps only is no error: the loop never looks at the read there
+    for rf, rd in ((gapped, put(gapped, 10, "N")), (gapped, put(gapped, 79, "N")), (gapped, gapped[:10] + "N" * 70 + gapped[80:]),
+                   (ref + "-" * 70, ref + "N" * 70), ("-" * 70 + ref, "X" * 70 + ref)):
+        got = calls.find_errors([ref, rf], [ref, rd])
+        same(got, oracle.find_errors([ref, rf], [ref, rd]))
+        assert np.asarray(got[7]).tolist() == [70]

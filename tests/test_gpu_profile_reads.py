@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from tests.encodings import BY_NAME, draw_quals
-from tests.profile_reads_cases import cases, chain_expected, plain
+from tests.profile_reads_cases import DENSE, EDGE, TILE, cases, chain_expected, long_cases, noisy, phred_quals, plain, stride_case
 
 pytestmark = pytest.mark.gpu
 
@@ -168,3 +168,161 @@ def test_several_references():
         alone = generics.profileReads(rd.subset(np.flatnonzero(assignment == j)), refs[j])
         assert plain(part) == plain(alone)
     assert plain(generics.profileReads(rd, refs, assignment=assignment)) == plain(parts)
+
+
+# ---- beyond one tile of reference positions (2 048), beyond one sweep of the persistent grid, and where the dense
+# ---- table of event lengths ends and the list begins (64)
+LONG = long_cases()
+
+
+@pytest.fixture(scope="module")
+def long_expected(oracle, oenc):
+    return {name: chain_expected(oracle, oenc, ref, reads, quals) for name, (ref, reads, quals) in LONG.items()}
+
+
+def edge_rows(rows, lengths):
+    """the rows that hold the lengths 63, 64 and 65"""
+    rows, lengths = np.asarray(rows), np.asarray(lengths)
+    return sorted(int(r) for r in np.unique(rows) if set(EDGE) <= set(lengths[rows == r].tolist()))
+
+
+@pytest.mark.parametrize("name", sorted(LONG, key=lambda k: int(k[1:])))
+def test_tile_edge(name, long_expected):
+    from sarlacc_amd import generics
+    from sarlacc_amd.resident import DeviceReads
+    ref, reads, quals = LONG[name]
+    R = len(ref)
+    scores, edits, errors, homopolymers = long_expected[name]
+    # what the comparison is about, on the expected side: insertions of 63, 64 and 65 bases at the start, beyond the tile
+    # edge and behind the last base; a run beyond the edge observed with 63, 64 and 65 bases; a run across the edge
+    ins = errors["full"]["insertion"]
+    assert len(ins) == R + 1 and sum(errors["full"]["deletion"][2000:min(2100, R)]) >= min(2100, R) - 2000
+    at = [p for p in range(R + 1) if set(EDGE) <= set(ins[p])]
+    assert min(at) <= 1 and max(at) == R and (R <= TILE or any(TILE <= p < R for p in at)), at
+    seen = [h["start"] for h in homopolymers if set(EDGE) <= set(h["observed"])]
+    assert len(seen) >= 3 and (R < 4100 or any(s - 1 > TILE for s in seen)), seen
+    if R > TILE:
+        assert R == int(name[1:]) and any(h["start"] - 1 <= TILE - 4 and h["end"] > TILE and h["base"] == "G" for h in homopolymers)
+    rd = generics.Reads(reads, quals)
+    same_profile(generics.profileReads(rd, ref), scores, edits, errors, homopolymers, generics)
+    dev = DeviceReads.upload(rd)
+    same_profile(generics.profileReads(dev, ref), scores, edits, errors, homopolymers, generics)
+    qa = generics.qualityAlign(rd, ref)
+    same_profile(generics.profileReads(dev, ref, expand=True), qa["score"], qa["edit"], generics.errorFinder(qa["reference"], qa["query"]),
+                 generics.homopolymerMatcher(qa["reference"], qa["query"]), generics, folded=False)
+
+
+def test_dense_table_and_list_on_one_row(enc, long_expected):
+    """lengths 63 (dense table), 64 and 65 (list) of one position / one run come out side by side, in ascending order"""
+    from sarlacc_amd import calls, generics
+    ref, reads, quals = LONG["r4100"]
+    errors, homopolymers = generics.foldProfile(*long_expected["r4100"][2:])
+    raw = calls.profile_reads(reads, quals, enc, 5, 1, ref)
+    for rows, lengths, mult, want in ((raw["ins_pos"], raw["ins_len"], raw["ins_mult"], [(p, v) for p, v in enumerate(errors["full"]["insertion"])]),
+                                      (raw["obs_run"], raw["obs_len"], raw["obs_mult"], [(k, h["observed"]) for k, h in enumerate(homopolymers)])):
+        found = edge_rows(rows, lengths)
+        assert found and found[-1] > 0
+        for r in found:
+            mine = np.flatnonzero(rows == r)
+            assert (np.diff(mine) == 1).all() and (np.diff(lengths[mine]) > 0).all()
+            l, m = dict(want)[r]
+            keep = np.asarray(l) > 0 if rows is raw["ins_pos"] else np.ones(len(l), bool)   # (no insertion: no event)
+            assert lengths[mine].tolist() == np.asarray(l)[keep].tolist() and mult[mine].tolist() == np.asarray(m)[keep].tolist()
+        assert (np.diff(rows) >= 0).all() and (mult > 0).all()
+
+
+def test_tile_edge_in_chunks(long_expected):
+    import sarlacc_amd
+    from sarlacc_amd import calls, generics
+    from sarlacc_amd.resident import DeviceReads
+    name = "r%d" % (TILE + 1)
+    ref, reads, quals = LONG[name]
+    n = len(reads)
+    dev = DeviceReads.upload(generics.Reads(reads, quals))
+    try:
+        for chunk, want in ((1, n), (7, (n + 6) // 7)):
+            calls.set_option("profile_chunk_reads", chunk)
+            same_profile(generics.profileReads(dev, ref), *long_expected[name], generics)
+            assert sarlacc_amd.stage_count("profile_chunks") == want
+    finally:
+        calls.set_option("profile_chunk_reads", 0)
+
+
+def test_grid_stride(oracle, oenc):
+    """more alignments than one sweep of the persistent grid (4 x CUs workgroups of 8): every wavefront walks a second
+    alignment into the same counters, and a list event comes with a multiplicity"""
+    import torch
+    from sarlacc_amd import calls, generics
+    from sarlacc_amd.resident import DeviceReads
+    n = 32 * torch.cuda.get_device_properties(0).multi_processor_count + 300
+    ref, reads, quals, inserted = stride_case(n)
+    scores, edits, errors, homopolymers = chain_expected(oracle, oenc, ref, reads, quals)
+    shared = reads.count(inserted)
+    events = [(p, l, v.count(l)) for p, v in enumerate(errors["full"]["insertion"]) for l in sorted(set(v)) if l >= DENSE]
+    assert shared > 1 and len(events) == 1 and events[0][1] >= 70 - 2 and events[0][2] == shared, events
+    rd = generics.Reads(reads, quals)
+    same_profile(generics.profileReads(rd, ref), scores, edits, errors, homopolymers, generics)
+    same_profile(generics.profileReads(DeviceReads.upload(rd), ref), scores, edits, errors, homopolymers, generics)
+    raw = calls.profile_reads(reads, quals, rd.encoding, 5, 1, ref)
+    k = np.flatnonzero(raw["ins_len"] >= DENSE)
+    assert [(int(raw["ins_pos"][j]), int(raw["ins_len"][j]), int(raw["ins_mult"][j])) for j in k] == events
+    assert int(raw["counts"].sum()) == len(ref) * n
+
+
+def outcome(f):
+    from sarlacc_amd import SarlaccError
+    try:
+        return ("value", f())
+    except SarlaccError as e:
+        return ("error", str(e))
+
+
+def test_error_order_across_tiles():
+    """the unknown character the chain meets first: by alignment, then by position from the front -- while the walk goes from
+    the back and each tile sees its own positions only"""
+    from sarlacc_amd import generics
+    ref = LONG["r4100"][0]
+    rng = np.random.default_rng(4100)
+    reads = [noisy(rng, ref, 0.02) for _ in range(6)] + [""]
+    quals = phred_quals(rng, reads)
+
+    def put(s, k, c):
+        return s[:k] + c + s[k + 1:]
+
+    def chain(rd):
+        qa = generics.qualityAlign(rd, ref)
+        return plain([generics.errorFinder(qa["reference"], qa["query"]), generics.homopolymerMatcher(qa["reference"], qa["query"])])
+
+    def fused(rd):
+        got = generics.profileReads(rd, ref, expand=True)
+        return plain([got["errors"], got["homopolymers"]])
+    mid = reads[2][:2500] + "ACGTANACGT" + reads[2][2500:]   # (ten bases the reference does not hold there: an insertion)
+    for bad, letter in (([put(r, 3000, "R") if i == 3 else put(r, 10, "N") if i == 5 else r for i, r in enumerate(reads)], "R"),
+                        ([put(put(r, 3000, "N"), 100, "R") if i == 4 else r for i, r in enumerate(reads)], "R"),
+                        ([put(r, len(r) - 5, "N") if i == 1 else put(r, 2, "R") if i == 2 else r for i, r in enumerate(reads)], "N"),
+                        ([mid if i == 2 else r for i, r in enumerate(reads)], None)):
+        q = [x if len(x) == len(r) else x[:2500] + "5" * 10 + x[2500:] for x, r in zip(quals, bad)]
+        rd = generics.Reads(bad, q)
+        want, got = outcome(lambda: chain(rd)), outcome(lambda: fused(rd))
+        assert got == want
+        if letter:
+            assert want == ("error", "unknown character '%s' in alignment string" % letter)
+
+
+def test_several_references_with_different_tile_counts():
+    from sarlacc_amd import generics
+    from sarlacc_amd.resident import DeviceReads
+    names = ("r40", "r%d" % (TILE + 1), "r4100")
+    sets = [CASES["r40"]] + [LONG[k] for k in names[1:]]
+    refs = [s[0] for s in sets]
+    assert [(len(r) + TILE - 1) // TILE for r in refs] == [1, 2, 3]
+    reads, quals, assignment = [], [], []
+    for j, (_, rds, qs) in enumerate(sets):
+        reads += rds[:20]; quals += qs[:20]; assignment += [j] * 20
+    order = np.random.default_rng(12).permutation(len(reads))
+    reads, quals, assignment = [reads[i] for i in order], [quals[i] for i in order], np.array(assignment)[order]
+    rd = generics.Reads(reads, quals)
+    parts = generics.profileReads(DeviceReads.upload(rd), refs, assignment=assignment)
+    assert len(parts) == 3
+    for j, part in enumerate(parts):
+        assert plain(part) == plain(generics.profileReads(rd.subset(np.flatnonzero(assignment == j)), refs[j]))
