@@ -35,6 +35,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
+#include <utility>
 
 namespace sarlacc {
 
@@ -1919,68 +1921,6 @@ __global__ void __launch_bounds__(WIDE_MAXT) k_align_wide_q(const AlignArgs A) {
 // ---------------------------------------------------------------------------
 // host side
 
-// Per-column lookup info: which fp64 table a column reads, decided by the
-// reference character alone (src/reference_align.cpp:184-212, SURVEY App.B Q2).
-int column_info(char r, uint32_t* info) {
-    uint32_t code = 7, tmatch, tmis;
-    switch (r) {
-        case 'A': code = 0; tmatch = 0; tmis = 1; break;
-        case 'C': code = 1; tmatch = 0; tmis = 1; break;
-        case 'G': code = 2; tmatch = 0; tmis = 1; break;
-        case 'T': code = 3; tmatch = 0; tmis = 1; break;
-        case 'M': case 'R': case 'W': case 'S': case 'Y': case 'K': tmatch = tmis = 2; break;
-        case 'V': case 'H': case 'D': case 'B': tmatch = tmis = 3; break;
-        case 'N': tmatch = tmis = 4; break;
-        default: return 1;
-    }
-    *info = code | (tmatch << 8) | (tmis << 16);
-    return 0;
-}
-
-// (src/reference_align.cpp:21-52) -- built on the host with the host libm so the
-// device never evaluates a transcendental on the scoring path.
-void build_tables(const double* errors, int n, std::vector<double>& tab) {
-    tab.assign(static_cast<size_t>(5) * n, 0.0);
-    const double four = 4.0, ratio = four / (four - 1.0);
-    auto odds = [&](double g, double e) { return std::log(g * (1 - e) * four + (1 - g) * e * ratio) / M_LN2; };
-    for (int q = 0; q < n; ++q) {
-        const double e = errors[q];
-        tab[0 * n + q] = odds(1.0 / 1.0, e);          // exact, match      (mode 1 match)
-        tab[1 * n + q] = odds(1 - 1.0 / 1.0, e);      // exact, mismatch   (mode 1 mismatch)
-        tab[2 * n + q] = odds(1 - 1.0 / 2.0, e);      // 2-fold            (mode 2 mismatch)
-        tab[3 * n + q] = odds(1.0 / 3.0, e);          // 3-fold            (mode 3 match)
-        tab[4 * n + q] = odds(1.0 / 4.0, e);          // N                 (mode 4 match)
-    }
-}
-
-// Device layout of the cost table: rows of n doubles, addressed as
-//     colbase[column] + (read base code * n + quality) * 8          (one add per cell)
-// with read base codes 0-3 = ACGT, 4 = anything else.
-//   * columns holding A/C/G/T share eight rows "mis mis mis MATCH mis mis mis mis"; the column
-//     of reference base r starts 3 - r rows in, so code == r lands on the match row and every
-//     other code (including 4) on a mismatch row;
-//   * each ambiguity class present in the reference (2-fold, 3-fold, N) gets five identical
-//     rows: its score does not depend on the read base (src/reference_align.cpp:184-212).
-void build_cost_rows(const std::vector<double>& tab, int n, const uint32_t* colinfo, int R,
-                     std::vector<double>& rows, std::vector<uint32_t>& colbase) {
-    rows.clear();
-    auto append = [&](int t) { rows.insert(rows.end(), tab.begin() + static_cast<size_t>(t) * n, tab.begin() + static_cast<size_t>(t + 1) * n); };
-    for (int r = 0; r < 8; ++r) append(r == 3 ? 0 : 1);
-    uint32_t class_base[5] = {0, 0, 0, 0, 0};
-    colbase.assign(static_cast<size_t>(R) + 1, 0);
-    const uint32_t row_bytes = static_cast<uint32_t>(n * sizeof(double));
-    for (int col = 1; col <= R; ++col) {
-        const uint32_t code = colinfo[col] & 0xff, tmatch = (colinfo[col] >> 8) & 0xff;
-        if (code < 4) { colbase[col] = (3 - code) * row_bytes; continue; }
-        if (!class_base[tmatch]) {
-            class_base[tmatch] = static_cast<uint32_t>(rows.size() * sizeof(double));
-            for (int r = 0; r < 5; ++r) append(static_cast<int>(tmatch));
-        }
-        colbase[col] = class_base[tmatch];
-    }
-    colbase[0] = colbase[R ? 1 : 0];
-}
-
 // MODE 4 (see LOC_NEG): the integer tables and the constants of the exactness argument, or false when the call is not
 // eligible (it then runs MODE 3): GE > 0, gapopen >= 0, GO 2^k and GE 2^k integers, and an integer range that fits.
 struct LocPlan {
@@ -2084,136 +2024,46 @@ static Shape pick_shape(int R) {
     return best;
 }
 
-template <int K, int ROW16, int KLAST, bool PENSEL>
-static int launch_mode(int mode, bool local, const AlignArgs& a, int grid, size_t lds, hipStream_t s) {
-    // adaptor_align is always local, general_align always global; score-only comes in both
-    if (mode == 0 && local) hipLaunchKernelGGL((k_align<K, 0, true, ROW16, KLAST, PENSEL>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
-    else if (mode == 0) hipLaunchKernelGGL((k_align<K, 0, false, ROW16, KLAST, PENSEL>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
-    else if (mode == 1 && local) hipLaunchKernelGGL((k_align<K, 1, true, ROW16, KLAST, PENSEL>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
-    else if (mode == 3 && local && !PENSEL) hipLaunchKernelGGL((k_align<K, 3, true, ROW16, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
-    else if (mode == 2 && !local) hipLaunchKernelGGL((k_align<K, 2, false, ROW16, KLAST, PENSEL>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
-    else return fail("sarlacc_amd: unsupported alignment mode");
-    SL_HIP(hipGetLastError());
-    return 0;
-}
-
-template <int K, int ROW16, int KLAST>
-static int launch_pen(bool pensel, int mode, bool local, const AlignArgs& a, int grid, size_t lds, hipStream_t s) {
-    return pensel ? launch_mode<K, ROW16, KLAST, true>(mode, local, a, grid, lds, s)
-                  : launch_mode<K, ROW16, KLAST, false>(mode, local, a, grid, lds, s);
-}
-
-// What a MODE 4 call with window classes launches beside `a` (whose tiles then hold window codes only): the window order
-// and the tiles, with snapshots, of the two small snapshot launches.
-struct LocLaunch {
-    int* order = nullptr;                  // [n + 2] k_loc_order's output
-    void* redo_dirs = nullptr;
-    unsigned long long redo_per_wave = 0;
-    int redo_grid = 0;
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
+// Everything a call decides before it touches the device
+struct AlignPlan {
+    double GO = 0, GE = 0;
+    std::vector<double> rows, rowzero;   // the call's tables on the host: cost rows (build_cost_rows), DP row 0
+    std::vector<uint32_t> colbase;
+    Shape sh{1, 64, 1, 0};
+    int klast = -1;   // index of column R inside its lane where k_align knows it at compile time (KLAST), else -1
+    int mode = 0;   // the kernels': 0 scores, 1 / 2 the code stream (map / strings), 3 snapshots, 4 locator + window
+    bool pensel = false, wide = false, classes = false, wide_queue = false;   // wide_queue: k_align_wide by k_align_wide_q
+    size_t per_wave = 0, word_bytes = 4, lds = 0, redo_per_wave = 0;   // traceback tile of one wavefront (wide: of one workgroup), in words; LDS bytes
+    long long grid = 0;
+    int win_nb = 0, redo_grid = 0;   // window classes: the tiles (redo_per_wave) and the grid of the two small snapshot launches
+    int wide_T = 0, wide_strips = 0, wide_band = 0;   // k_align_wide: threads, strips, see AlignArgs::wide_band
 };
 
-template <int K, int KLAST>
-static int launch_il(int mode, const AlignArgs& a, int grid, size_t lds, hipStream_t s, const LocLaunch* ll) {
-    if (mode == 4) {
-        // the locator (its LDS: rings + the integer table), the windows, then the snapshot kernel on the reads the windows
-        // put on their list (count read on the device)
-        const size_t lds5 = sizeof(uint16_t) * NWAVES * NGMAX2 * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
-        if (a.loc_framed) hipLaunchKernelGGL((k_align<K, 6, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
-        else hipLaunchKernelGGL((k_align<K, 5, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds5, s, a);
-        AlignArgs r = a;
-        r.bad_done = 1;
-        // the windows: with the code ring in LDS behind the maps (three wavefronts per SIMD), or the tile alone
-        const size_t lds4 = lds + static_cast<size_t>(NWAVES) * a.win_nb * 64 * sizeof(uint32_t);
-        auto windows = [&](const AlignArgs& w) -> int {
-            if (!a.win_nb) {
-                hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, w);
-                return 0;
-            }
-            static thread_local size_t lds_set = 0;   // (per instantiation: the attribute is raised once, not at every launch)
-            if (lds4 > 48 * 1024 && lds4 > lds_set) {
-                SL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_align<K, 4, true, 2, KLAST, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds4)));
-                lds_set = lds4;
-            }
-            hipLaunchKernelGGL((k_align<K, 4, true, 2, KLAST, false, true>), dim3(grid), dim3(64 * NWAVES), lds4, s, w);
-            return 0;
-        };
-        if (!ll) {
-            SL_TRY(windows(a));
-            r.read_list = a.loc_redo;
-            hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, r);
-        } else {
-            // The locator has listed the oversize reads: the snapshot kernel aligns them on the side stream while this one
-            // orders and runs the windows.  Both snapshot launches are small (their item loop strides) and share tiles: the
-            // second, on the reads whose walk stalled, starts after the join.
-            r.dirs = ll->redo_dirs;
-            r.dirs_per_wave = ll->redo_per_wave;
-            SL_HIP(hipEventRecord(ll->fork, s));
-            SL_HIP(hipStreamWaitEvent(ll->side, ll->fork, 0));
-            r.read_list = a.loc_over;
-            hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(ll->redo_grid), dim3(64 * NWAVES), lds, ll->side, r);
-            SL_HIP(hipEventRecord(ll->join, ll->side));
-            hipLaunchKernelGGL(k_loc_order, dim3(static_cast<unsigned>((a.n + 255) / 256)), dim3(256), 0, s, a.loc_cls, a.n, a.loc_ccount, ll->order);
-            AlignArgs w = a;
-            w.read_list = ll->order;
-            w.bad_done = 1;
-            SL_TRY(windows(w));
-            SL_HIP(hipStreamWaitEvent(s, ll->join, 0));
-            r.read_list = a.loc_redo;
-            hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(ll->redo_grid), dim3(64 * NWAVES), lds, s, r);
-        }
-    } else if (mode == 3) hipLaunchKernelGGL((k_align<K, 3, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
-    else hipLaunchKernelGGL((k_align<K, 0, true, 2, KLAST, false>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
-    SL_HIP(hipGetLastError());
-    return 0;
+// Far more workgroups than fit at once: each wave then owns only a few work items and the
+// hardware hands out workgroups as CUs free up, which balances the load much better than an
+// exactly resident grid with a static stride (1.74 -> 2.07 TCUPS at 1M x 2kb; flat from 128 to
+// 384 waves per CU).  The per-wave scratch tiles scale with the grid and are capped by the caller.
+long long align_grid(long long nitems, int waves, int num_cu) {
+    int waves_per_cu = 128;
+    if (option(OPT_ALIGN_WAVES_PER_CU) > 0) waves_per_cu = option(OPT_ALIGN_WAVES_PER_CU);
+    return std::min<long long>((nitems + waves - 1) / waves, (static_cast<long long>(num_cu) * waves_per_cu + waves - 1) / waves);
 }
 
-static int launch_k(int K, int rowf, int R, bool pensel, int mode, bool local, const AlignArgs& a, int grid, size_t lds,
-                    hipStream_t s, const LocLaunch* ll = nullptr) {
-    const int klast = (R - 1) % K;
-    if (rowf == 2) {
-        // interleaved alignments: local mode without penalty selects only (adaptor_align by snapshots, score-only)
-        if (!local || pensel || !(mode == 3 || mode == 4 || mode == 0)) return fail("sarlacc_amd: interleaved alignments serve local modes 0 and 3 only");
-        const int key = K * 4 + klast;
-        switch (key) {
-            case 2 * 4 + 0: return launch_il<2, 0>(mode, a, grid, lds, s, ll);
-            case 2 * 4 + 1: return launch_il<2, 1>(mode, a, grid, lds, s, ll);
-            case 4 * 4 + 0: return launch_il<4, 0>(mode, a, grid, lds, s, ll);
-            case 4 * 4 + 1: return launch_il<4, 1>(mode, a, grid, lds, s, ll);
-            case 4 * 4 + 2: return launch_il<4, 2>(mode, a, grid, lds, s, ll);
-            case 4 * 4 + 3: return launch_il<4, 3>(mode, a, grid, lds, s, ll);
-        }
-        return fail("sarlacc_amd: unsupported columns-per-lane %d for interleaved alignments", K);
-    }
-    const bool row16 = rowf == 1;
-    if (K == 1) return row16 ? launch_pen<1, 1, 0>(pensel, mode, local, a, grid, lds, s) : launch_pen<1, 0, 0>(pensel, mode, local, a, grid, lds, s);
-    if (K == 2) {
-        if (row16) return klast == 0 ? launch_pen<2, 1, 0>(pensel, mode, local, a, grid, lds, s) : launch_pen<2, 1, 1>(pensel, mode, local, a, grid, lds, s);
-        return klast == 0 ? launch_pen<2, 0, 0>(pensel, mode, local, a, grid, lds, s) : launch_pen<2, 0, 1>(pensel, mode, local, a, grid, lds, s);
-    }
-    switch (K) {
-        case 4: return row16 ? launch_pen<4, 1, -1>(pensel, mode, local, a, grid, lds, s) : launch_pen<4, 0, -1>(pensel, mode, local, a, grid, lds, s);
-        case 8: return row16 ? launch_pen<8, 1, -1>(pensel, mode, local, a, grid, lds, s) : launch_pen<8, 0, -1>(pensel, mode, local, a, grid, lds, s);
-        case 16: return row16 ? launch_pen<16, 1, -1>(pensel, mode, local, a, grid, lds, s) : launch_pen<16, 0, -1>(pensel, mode, local, a, grid, lds, s);
-    }
-    return fail("sarlacc_amd: unsupported columns-per-lane %d", K);
-}
-
-// References beyond MAX_REF columns: one workgroup per alignment (k_align_wide).  `a` is complete except for the scratch.
-static int launch_wide(AlignArgs& a, int R, int kernel_mode, int32_t max_len, long long n, hipStream_t stream) {
-    Context& c = ctx();
-    constexpr int K = 8;   // (12 or 16 columns per thread at 2 kb: 3 x slower -- the unrolled columns spill at the 128 registers a 1 024-thread bound leaves)
+constexpr int WIDE_K = 8;   // (12 or 16 columns per thread at 2 kb: 3 x slower -- the unrolled columns spill at the 128 registers a 1 024-thread bound leaves)
+// References beyond MAX_REF columns: one workgroup per alignment (k_align_wide).
+static int plan_wide(const AlignJob& job, int num_cu, AlignPlan& p) {
+    constexpr int K = WIDE_K;
+    const int R = job.R, kernel_mode = p.mode == 3 ? 1 : p.mode;
+    const int32_t max_len = job.batch.max_len;
     if (R > (1 << 20)) return fail("sarlacc_amd: reference longer than %d columns is not supported", 1 << 20);
-    if (kernel_mode == 2 && a.nmask) return fail("sarlacc_amd: alignment strings need ASCII reads");
+    if (kernel_mode == 2 && job.batch.d_nmask) return fail("sarlacc_amd: alignment strings need ASCII reads");
     // up to 8 192 columns one strip of as many threads as the columns need; beyond, strips of 1 024 threads x 8 columns
     const int T = R <= K * WIDE_MAXT ? ((R + K - 1) / K + 63) / 64 * 64 : WIDE_MAXT;
     const int nstrips = (R + T * K - 1) / (T * K);
     const size_t word = 4;
     size_t per_wg = 0;   // words: codes of every step of every strip, then the reference -> read map
     if (kernel_mode) per_wg = static_cast<size_t>(nstrips) * (static_cast<size_t>(max_len) + T + 1) * T + ((static_cast<size_t>(R) + 1) * 4 + word - 1) / word;
-    long long grid = std::min<long long>(n, static_cast<long long>(c.num_cu) * std::max(1, 2048 / T));
+    long long grid = std::min<long long>(job.batch.n, static_cast<long long>(num_cu) * std::max(1, 2048 / T));
     if (kernel_mode) {
         const size_t budget = static_cast<size_t>(16) << 30;
         // (4 bits per cell of the whole matrix per alignment in flight: a 2^20-column reference against 100-kb reads would be 50 GB)
@@ -2223,144 +2073,43 @@ static int launch_wide(AlignArgs& a, int R, int kernel_mode, int32_t max_len, lo
                         static_cast<double>(per_wg * word) / 1073741824.0);
         grid = std::min(grid, std::max<long long>(1, static_cast<long long>(budget / (per_wg * word))));
     }
-    void* d_dirs = nullptr;
-    if (kernel_mode) SL_TRY(c.buffer("align.dirs", static_cast<size_t>(grid) * per_wg * word, &d_dirs));
-    double* d_bnd = nullptr;
-    SL_TRY(scratch("align.bnd", nstrips > 1 ? static_cast<size_t>(grid) * 6 * (static_cast<size_t>(max_len) + 2) : 8, &d_bnd));
-    a.dirs = d_dirs;
-    a.dirs_per_wave = per_wg;
-    a.wide_maxlen = max_len;
-    a.wide_bnd = d_bnd;
-    const size_t lds = sizeof(double) * a.tab_doubles + static_cast<size_t>(T) * (2 * 8 + 2 * 8 + 2 * 4) + static_cast<size_t>(WIDE_CH) * (8 + 8 + 4) +
-                       WIDE_RING * sizeof(uint16_t);
-    if (lds > 150 * 1024) return fail("sarlacc_amd: alignment tables do not fit in LDS");
-    const dim3 g(static_cast<unsigned>(grid)), b(static_cast<unsigned>(T));
-    const bool pensel = !(a.GO >= a.GE) || option(OPT_ALIGN_PENSEL) != 0;   // (gapopen < 0, or the tests' switch)
+    p.wide_T = T; p.wide_strips = nstrips; p.per_wave = per_wg; p.word_bytes = word; p.grid = grid;
+    p.lds = sizeof(double) * p.rows.size() + static_cast<size_t>(T) * (2 * 8 + 2 * 8 + 2 * 4) + static_cast<size_t>(WIDE_CH) * (8 + 8 + 4) +
+            WIDE_RING * sizeof(uint16_t);
+    if (p.lds > 150 * 1024) return fail("sarlacc_amd: alignment tables do not fit in LDS");
     // global mode, no penalty selects, one strip: the kernel without a barrier per step (k_align_wide_q); align_wide_barrier = 1: the A/B
-    if (!pensel && !a.local && nstrips == 1 && !option(OPT_ALIGN_WIDE_BARRIER)) {
-        const int NWV = T / 64;
-        const size_t ldq = sizeof(double) * a.tab_doubles + static_cast<size_t>(NWV) * WQ_B * (8 + 8 + 4) + static_cast<size_t>(2 * NWV + 2) * 4 +
-                           static_cast<size_t>(NWV) * 128 * sizeof(uint16_t);
-        if (ldq > 150 * 1024) return fail("sarlacc_amd: alignment tables do not fit in LDS");
-#define WIDEQ_LAUNCH(MM)                                                                                                          \
-    {                                                                                                                              \
-        static thread_local size_t lds_set = 0;   /* (per instantiation: the attribute is raised once, not at every launch) */      \
-        if (ldq > 48 * 1024 && ldq > lds_set) {                                                                                    \
-            SL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_align_wide_q<K, MM>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       static_cast<int>(ldq)));                                                                    \
-            lds_set = ldq;                                                                                                         \
-        }                                                                                                                          \
-        hipLaunchKernelGGL((k_align_wide_q<K, MM>), g, b, ldq, stream, a);                                                         \
-    }
-        // With traceback: codes only for the steps that can hold cells within WIDE_BAND rows of the main diagonal (40 % of the steps
-        // at 2 kb x 2 kb), then a second launch, with the codes of every cell, over the reads whose walks left them (their count
-        // stays on the device: no wait in between; none for reads of the reference's molecule).  align_wide_band = -1: no band.
-        const int band = kernel_mode == 0 || option(OPT_ALIGN_WIDE_BAND) < 0 ? 0 : (option(OPT_ALIGN_WIDE_BAND) > 0 ? option(OPT_ALIGN_WIDE_BAND) : WIDE_BAND);
-        int* d_redo = nullptr;
-        if (band > 0) {
-            SL_TRY(scratch("align.redo", static_cast<size_t>(n) + 2, &d_redo));
-            SL_HIP(hipMemsetAsync(d_redo, 0, sizeof(int), stream));
-        }
-        a.wide_band = band; a.wide_redo = d_redo; a.wide_list = nullptr;
-        if (kernel_mode == 0) WIDEQ_LAUNCH(0) else if (kernel_mode == 1) WIDEQ_LAUNCH(1) else WIDEQ_LAUNCH(2)
-        if (band > 0) {
-            a.wide_band = 0; a.wide_list = d_redo + 1;
-            if (kernel_mode == 1) WIDEQ_LAUNCH(1) else WIDEQ_LAUNCH(2)
-        }
-#undef WIDEQ_LAUNCH
-        SL_HIP(hipGetLastError());
-        return 0;
-    }
-#define WIDE_LAUNCH2(MM, PP, SS)                                                                                                   \
-    {                                                                                                                              \
-        static thread_local size_t lds_set = 0;   /* (per instantiation: the attribute is raised once, not at every launch) */      \
-        if (lds > 48 * 1024 && lds > lds_set) {                                                                                    \
-            SL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_align_wide<K, MM, PP, SS>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       static_cast<int>(lds)));                                                                    \
-            lds_set = lds;                                                                                                         \
-        }                                                                                                                          \
-        hipLaunchKernelGGL((k_align_wide<K, MM, PP, SS>), g, b, lds, stream, a);                                                   \
-    }
-#define WIDE_LAUNCH(MM, PP) { if (nstrips > 1) WIDE_LAUNCH2(MM, PP, true) else WIDE_LAUNCH2(MM, PP, false) }
-    if (pensel) { if (kernel_mode == 0) WIDE_LAUNCH(0, true) else if (kernel_mode == 1) WIDE_LAUNCH(1, true) else WIDE_LAUNCH(2, true) }
-    else { if (kernel_mode == 0) WIDE_LAUNCH(0, false) else if (kernel_mode == 1) WIDE_LAUNCH(1, false) else WIDE_LAUNCH(2, false) }
-#undef WIDE_LAUNCH
-#undef WIDE_LAUNCH2
-    SL_HIP(hipGetLastError());
+    p.wide_queue = !p.pensel && !job.local && nstrips == 1 && !option(OPT_ALIGN_WIDE_BARRIER);
+    if (!p.wide_queue) return 0;
+    const int NWV = T / 64;
+    p.lds = sizeof(double) * p.rows.size() + static_cast<size_t>(NWV) * WQ_B * (8 + 8 + 4) + static_cast<size_t>(2 * NWV + 2) * 4 +
+            static_cast<size_t>(NWV) * 128 * sizeof(uint16_t);
+    if (p.lds > 150 * 1024) return fail("sarlacc_amd: alignment tables do not fit in LDS");
+    // With traceback: codes only for the steps that can hold cells within WIDE_BAND rows of the main diagonal (40 % of the steps
+    // at 2 kb x 2 kb), then a second launch, with the codes of every cell, over the reads whose walks left them (their count
+    // stays on the device: no wait in between; none for reads of the reference's molecule).  align_wide_band = -1: no band.
+    p.wide_band = kernel_mode == 0 || option(OPT_ALIGN_WIDE_BAND) < 0 ? 0 : (option(OPT_ALIGN_WIDE_BAND) > 0 ? option(OPT_ALIGN_WIDE_BAND) : WIDE_BAND);
     return 0;
 }
 
-// kernel_mode: 0 scores, 1 map, 2 strings.  Returns in *bad_qual_read the smallest
-// index of a read with a quality character below the encoding offset (or INT_MAX).
-// (ChunkOpts, align_host.hpp: a host call may hand its batch over in chunks.)
-int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
-              int32_t max_len, const double* enc_errors, const char* enc_names, int enc_n,
-              double gapopen, double gapext, const char* ref, int R, bool local, int kernel_mode,
-              const int32_t* sec_starts, const int32_t* sec_ends, int nsec, const AlignOut& out,
-              hipStream_t stream, int* bad_qual_read, const ChunkOpts& co) {
-    Context& c = ctx();
-    if (co.init_bad) *bad_qual_read = std::numeric_limits<int>::max();
-    if (n <= 0) return 0;
-    const bool wide = R > MAX_REF;   // one workgroup per alignment instead of (a part of) one wavefront
-    if (enc_n > 256) return fail("sarlacc_amd: encoding vector longer than 256 entries");
-    if (n > std::numeric_limits<int>::max() - 8) return fail("sarlacc_amd: more than 2^31 reads in one call");
-    const double GO = gapopen + gapext, GE = gapext;  // (src/reference_align.cpp:8)
-
-    if (R == 0) {
-        const int bs = 256;
-        hipLaunchKernelGGL(k_align_emptyref, dim3(static_cast<unsigned>((n + bs - 1) / bs)), dim3(bs), 0, stream,
-                           d_off, static_cast<long long>(n), local ? 1 : 0, GO, GE, out.d_scores, out.d_starts,
-                           out.d_ends, nsec, out.d_sec_so, out.d_sec_wo, out.d_aln_len, out.d_edits, d_seq,
-                           out.d_aln_ref, out.d_aln_qry);
-        SL_HIP(hipGetLastError());
-        return 0;
-    }
-
-    // ---- small per-call tables ----
+// No HIP call and no allocation: the small per-call tables, the shape, the mode and the sizes of tiles, grid and LDS (and,
+// for MODE 4, the locator's tables in `lp`).
+static int plan_align(const AlignJob& job, int num_cu, AlignPlan& p, LocPlan& lp) {
+    const int R = job.R, enc_n = job.sc.enc_n;
     std::vector<double> tab;
-    build_tables(enc_errors, enc_n, tab);
-    std::vector<double> rowzero(R + 1);
-    rowzero[0] = 0.0;
-    for (int col = 1; col <= R; ++col) rowzero[col] = rowzero[col - 1] - (col == 1 ? GO : GE);  // (:115-118)
+    build_tables(job.sc.enc_errors, enc_n, tab);
+    p.rowzero.assign(R + 1, 0.0);
+    for (int col = 1; col <= R; ++col) p.rowzero[col] = p.rowzero[col - 1] - (col == 1 ? p.GO : p.GE);  // (:115-118)
     std::vector<uint32_t> colinfo(R + 1, 0);
     for (int col = 1; col <= R; ++col)
-        if (column_info(ref[col - 1], &colinfo[col])) colinfo[col] = 7u | (4u << 8) | (4u << 16);  // caller reports the error
-
-    std::vector<double> rows;
-    std::vector<uint32_t> colbase;
-    build_cost_rows(tab, enc_n, colinfo.data(), R, rows, colbase);
+        if (column_info(job.ref[col - 1], &colinfo[col])) colinfo[col] = 7u | (4u << 8) | (4u << 16);  // caller reports the error
+    build_cost_rows(tab, enc_n, colinfo.data(), R, p.rows, p.colbase);
     if (4u * enc_n * sizeof(double) + enc_n * sizeof(double) > 0xffffu) return fail("sarlacc_amd: encoding vector too long for the staged read format");
-
-    AlignArgs a{};
-    double* d_tab; double* d_rz; uint32_t* d_cb; uint8_t* d_ref; int32_t* d_ss = nullptr; int32_t* d_se = nullptr; int* d_bad;
-    if (co.init_bad) {
-        SL_TRY(upload("align.tab", rows.data(), rows.size(), &d_tab, stream));
-        SL_TRY(upload("align.rz", rowzero.data(), rowzero.size(), &d_rz, stream));
-        SL_TRY(upload("align.cb", colbase.data(), colbase.size(), &d_cb, stream));
-        SL_TRY(upload("align.ref", reinterpret_cast<const uint8_t*>(ref), static_cast<size_t>(R), &d_ref, stream));
-        if (nsec) {
-            SL_TRY(upload("align.ss", sec_starts, static_cast<size_t>(nsec), &d_ss, stream));
-            SL_TRY(upload("align.se", sec_ends, static_cast<size_t>(nsec), &d_se, stream));
-        }
-        const int sentinel[2] = {std::numeric_limits<int>::max(), 0};   // [0] bad-quality read, [1] walk exceeded its bound
-        SL_TRY(upload("align.bad", sentinel, 2, &d_bad, stream));
-        // a chunk that returns without waiting for its kernel must not leave copies from this
-        // frame's vectors in flight (nothing else is queued on the stream yet)
-        if (!co.finish) SL_HIP(hipStreamSynchronize(stream));
-    } else {   // later chunks of the same call: the tables of the first chunk are still in place
-        SL_TRY(scratch("align.tab", rows.size(), &d_tab));
-        SL_TRY(scratch("align.rz", rowzero.size(), &d_rz));
-        SL_TRY(scratch("align.cb", colbase.size(), &d_cb));
-        SL_TRY(scratch("align.ref", static_cast<size_t>(R), &d_ref));
-        if (nsec) {
-            SL_TRY(scratch("align.ss", static_cast<size_t>(nsec), &d_ss));
-            SL_TRY(scratch("align.se", static_cast<size_t>(nsec), &d_se));
-        }
-        SL_TRY(scratch("align.bad", 2, &d_bad));
-    }
-
+    const int32_t max_len = job.batch.max_len;
+    const bool local = job.local;
+    int kernel_mode = job.kernel_mode;
+    const bool wide = p.wide = R > MAX_REF;   // one workgroup per alignment instead of (a part of) one wavefront
     // gapopen >= 0 (GO >= GE): no penalty selects on the device, see k_align
-    bool pensel = !(GO >= GE);
+    bool pensel = !(p.GO >= p.GE);
     pensel = pensel || option(OPT_ALIGN_PENSEL) != 0;  // testing: force the general path
     Shape sh = wide ? Shape{1, 64, 1, 0} : pick_shape(R);
     // interleaved alignments exist for the local modes without penalty selects (adaptor_align by snapshots, score-only);
@@ -2378,7 +2127,7 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
             if (option(OPT_ALIGN_INTERLEAVE) > 0 && il_mode && W <= 8 && (K == 2 || K == 4)) sh = {K, 8, NGMAX2, 2};
         }
     }
-    const long long nitems = (n + sh.ngroups - 1) / sh.ngroups;
+    const long long nitems = (job.batch.n + sh.ngroups - 1) / sh.ngroups;
     // traceback tile of one resident wave: one word per lane per TbSteps<K> steps (4 bits per cell)
     const int tb_steps = std::max(1, 8 / sh.K);
     const size_t word_bytes = sh.K == 16 ? 8 : 4;
@@ -2393,95 +2142,38 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     // ... and, where eligible, by the integer locator + one fp64 window, the snapshot kernel redoing the reads it
     // cannot certify (same tiles).  align_locate = -1: the snapshot path alone (A/B); 2: the un-framed locator, 3: the same
     // at the frame's k (A/B)
-    LocPlan lp;
     const int loc_frame = option(OPT_ALIGN_LOCATE) == 2 ? 0 : option(OPT_ALIGN_LOCATE) == 3 ? 2 : 1;
     if (kernel_mode == 3 && sh.rowf == 2 && option(OPT_ALIGN_LOCATE) >= 0 &&
-        plan_locate(rows, colbase, enc_n, R, GO, GE, rowzero, max_len, loc_frame, lp))
+        plan_locate(p.rows, p.colbase, enc_n, R, p.GO, p.GE, p.rowzero, max_len, loc_frame, lp))
         kernel_mode = 4;
     // MODE 4 with window classes (align_window_classes = -1: without, A/B): its own tiles hold the codes of one window and
     // the two small snapshot launches get tiles of their own
-    const bool classes = kernel_mode == 4 && option(OPT_ALIGN_WINDOW_CLASSES) >= 0;
+    const bool classes = p.classes = kernel_mode == 4 && option(OPT_ALIGN_WINDOW_CLASSES) >= 0;
     // (the locator serves eight-lane alignments only: R <= 32, W = 8, a tile of 120 steps at most)
     if (classes && snap_win(R, sh.W) / 8 >= LOC_NCLS) return fail("sarlacc_amd: internal error: window tile of %d steps exceeds the window classes", snap_win(R, sh.W));
     const size_t redo_per_wave = per_wave_elems;
     if (classes) per_wave_elems = static_cast<size_t>(snap_win(R, sh.W) / tb_steps) * 64;
-    // Far more workgroups than fit at once: each wave then owns only a few work items and the
-    // hardware hands out workgroups as CUs free up, which balances the load much better than an
-    // exactly resident grid with a static stride (1.74 -> 2.07 TCUPS at 1M x 2kb; flat from 128 to
-    // 384 waves per CU).  The per-wave scratch tiles scale with the grid and are capped below.
-    int waves_per_cu = 128;
-    if (option(OPT_ALIGN_WAVES_PER_CU) > 0) waves_per_cu = option(OPT_ALIGN_WAVES_PER_CU);
     // workgroups of NWAVES wavefronts; every wavefront owns a traceback tile
-    long long grid = std::min<long long>((nitems + NWAVES - 1) / NWAVES,
-                                         (static_cast<long long>(c.num_cu) * waves_per_cu + NWAVES - 1) / NWAVES);
+    long long grid = align_grid(nitems, NWAVES, num_cu);
     if (kernel_mode) {
         const size_t budget = static_cast<size_t>(6) << 30;
         const long long fit = std::max<long long>(1, static_cast<long long>(budget / std::max<size_t>(1, per_wave_elems * word_bytes * NWAVES)));
         grid = std::min(grid, fit);
     }
-    void* d_dirs = nullptr;
-    if (kernel_mode && !wide) SL_TRY(c.buffer("align.dirs", static_cast<size_t>(grid) * NWAVES * per_wave_elems * word_bytes, &d_dirs));
-
-    a.seq = d_seq; a.nmask = d_nmask; a.qual = d_qual; a.off = d_off; a.n = n;
-    a.R = R; a.W = sh.W; a.ngroups = sh.ngroups; a.local = local ? 1 : 0;
-    a.qoffset = static_cast<int>(enc_names[0]); a.navail = enc_n;
-    a.GO = GO; a.GE = GE;
-    a.tables = d_tab; a.tab_doubles = static_cast<int>(rows.size()); a.row_bytes = static_cast<int>(enc_n * sizeof(double));
-    a.rowzero = d_rz; a.colbase = d_cb; a.refchars = d_ref;
-    a.scores = out.d_scores; a.starts = out.d_starts; a.ends = out.d_ends;
-    a.sec_s = d_ss; a.sec_e = d_se; a.nsec = nsec; a.sec_so = out.d_sec_so; a.sec_wo = out.d_sec_wo;
-    a.dirs = d_dirs; a.dirs_per_wave = per_wave_elems; a.badqual = d_bad;
-    a.read_base = co.read_base; a.sec_stride = co.sec_stride ? co.sec_stride : n;
-    a.snap_head = snap_head(R); a.snap_win = snap_win(R, sh.W);
-    a.aln_ref = out.d_aln_ref; a.aln_qry = out.d_aln_qry; a.aln_len = out.d_aln_len; a.edits = out.d_edits;
-    int* d_stats = nullptr;
-    int* d_ccount = nullptr;
-    LocLaunch ll;
-    if (kernel_mode == 4) {
-        int *d_ltab, *d_lrz, *d_redo;
-        if (co.init_bad) {
-            SL_TRY(upload("align.ltab", lp.tab.data(), lp.tab.size(), &d_ltab, stream));
-            SL_TRY(upload("align.lrz", lp.rz.data(), lp.rz.size(), &d_lrz, stream));
-            const int zero[LOC_STATS] = {};
-            SL_TRY(upload("align.lstats", zero, LOC_STATS, &d_stats, stream));
-            if (!co.finish) SL_HIP(hipStreamSynchronize(stream));
-        } else {
-            SL_TRY(scratch("align.ltab", lp.tab.size(), &d_ltab));
-            SL_TRY(scratch("align.lrz", lp.rz.size(), &d_lrz));
-            SL_TRY(scratch("align.lstats", LOC_STATS, &d_stats));
-        }
-        SL_TRY(scratch("align.lredo", static_cast<size_t>(n) + 2, &d_redo));
-        SL_TRY(scratch("align.lout", static_cast<size_t>(n) * 3, &a.loc_out));
-        SL_HIP(hipMemsetAsync(d_redo, 0, 2 * sizeof(int), stream));
-        a.loc_tab = d_ltab; a.loc_rz = d_lrz; a.loc_redo = d_redo; a.loc_stats = d_stats;
-        a.loc_GO = lp.GO; a.loc_GE = lp.GE; a.loc_D = lp.D; a.loc_force = option(OPT_ALIGN_LOCATE) == 1 ? 1 : 0;
-        a.loc_framed = lp.framed ? 1 : 0;
-        a.loc_unit = lp.unit; a.loc_slack = lp.slack; a.loc_top = lp.top;
-        if (classes) {
-            SL_TRY(scratch("align.lcls", static_cast<size_t>(n), &a.loc_cls));
-            SL_TRY(scratch("align.lccount", static_cast<size_t>(2 * LOC_NCLS), &d_ccount));
-            SL_TRY(scratch("align.lover", static_cast<size_t>(n) + 2, &a.loc_over));
-            SL_TRY(scratch("align.lorder", static_cast<size_t>(n) + 2, &ll.order));
-            SL_HIP(hipMemsetAsync(d_ccount, 0, 2 * LOC_NCLS * sizeof(int), stream));
-            SL_HIP(hipMemsetAsync(a.loc_over, 0, 2 * sizeof(int), stream));
-            a.loc_ccount = d_ccount;
-            // about one workgroup per four CUs, each wavefront with a whole tile (codes of a window + snapshots)
-            const size_t wg_bytes = std::max<size_t>(1, redo_per_wave * word_bytes * NWAVES);
-            ll.redo_grid = static_cast<int>(std::max<size_t>(1, std::min<size_t>((c.num_cu + 3) / 4, (static_cast<size_t>(6) << 30) / wg_bytes)));
-            ll.redo_per_wave = redo_per_wave;
-            SL_TRY(c.buffer("align.rdirs", static_cast<size_t>(ll.redo_grid) * wg_bytes, &ll.redo_dirs));
-            SL_TRY(c.side_stream(&ll.side, &ll.fork, &ll.join));
-        }
+    if (classes) {
+        // about one workgroup per four CUs, each wavefront with a whole tile (codes of a window + snapshots)
+        const size_t wg_bytes = std::max<size_t>(1, redo_per_wave * word_bytes * NWAVES);
+        p.redo_grid = static_cast<int>(std::max<size_t>(1, std::min<size_t>((num_cu + 3) / 4, (static_cast<size_t>(6) << 30) / wg_bytes)));
+        p.redo_per_wave = redo_per_wave;
     }
-
-    const size_t lds = sizeof(uint16_t) * NWAVES * (sh.rowf == 2 ? NGMAX2 * (RING + RING_MIRROR) : NGMAX * RING_SLOT) + sizeof(double) * rows.size() +
+    const size_t lds = sizeof(uint16_t) * NWAVES * (sh.rowf == 2 ? NGMAX2 * (RING + RING_MIRROR) : NGMAX * RING_SLOT) + sizeof(double) * p.rows.size() +
                        sizeof(int32_t) * NWAVES * sh.ngroups * (R + 1) + 16;
     if (!wide && lds > 64 * 1024) return fail("sarlacc_amd: alignment tables do not fit in LDS");
     // MODE 4: the window's codes also in an LDS ring of win_nb blocks per wavefront behind the maps (WIN_LDS_WAVES), as many
     // blocks as the 64 KB leave at most.  align_window_lds = -1: the global tile alone (A/B, tests); >= 2: that many blocks
     // (tests: a small ring wraps often and sends most walks to the tile)
-    int win_nb = 0;
     if (kernel_mode == 4 && option(OPT_ALIGN_WINDOW_LDS) >= 0) {
+        int& win_nb = p.win_nb;
         const int tile_blocks = snap_win(R, sh.W) / tb_steps;
         win_nb = option(OPT_ALIGN_WINDOW_LDS) >= 2 ? option(OPT_ALIGN_WINDOW_LDS) : win_ring_blocks(R, sh.W, tb_steps);
         win_nb = std::min(win_nb, tile_blocks);
@@ -2489,28 +2181,231 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
         win_nb = static_cast<int>(std::min<size_t>(win_nb, (64 * 1024 - lds) / block_bytes));
         if (win_nb < 2) win_nb = 0;
     }
-    a.win_nb = win_nb;
-    if (co.stage) SL_TRY(c.stage_begin(co.stage, stream));
-    else SL_HIP(hipEventRecord(c.ev_start, stream));
-    if (wide) SL_TRY(launch_wide(a, R, kernel_mode == 3 ? 1 : kernel_mode, max_len, n, stream));
-    else SL_TRY(launch_k(sh.K, sh.rowf, R, pensel, kernel_mode, local, a, static_cast<int>(grid), lds, stream, classes ? &ll : nullptr));
-    if (co.stage) {
-        SL_TRY(c.stage_end(co.stage, stream));
-    } else {
-        SL_HIP(hipEventRecord(c.ev_stop, stream));
-        c.timed = true;
-    }
+    p.sh = sh; p.klast = sh.rowf == 2 || sh.K <= 2 ? (R - 1) % sh.K : -1; p.mode = kernel_mode; p.pensel = pensel;
+    p.per_wave = per_wave_elems; p.word_bytes = word_bytes; p.grid = grid; p.lds = lds;
+    return wide ? plan_wide(job, num_cu, p) : 0;
+}
 
-    if (!co.finish) return 0;
+// What a MODE 4 call with window classes launches beside its arguments: the window order (k_loc_order's output, [n + 2]),
+// the tiles of the two small snapshot launches and the side stream they fork onto
+struct LocLaunch { int* order = nullptr; void* redo_dirs = nullptr; hipStream_t side = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+
+// A per-call table: uploaded by the call's first chunk, still in place for the later chunks of the same call.
+template <typename T, typename D>
+static int call_table(const ChunkOpts& co, const char* name, const T* host, size_t count, D** dev, hipStream_t s) {   // (D: T or const T)
+    return co.init_bad ? upload(name, host, count, const_cast<T**>(dev), s) : scratch(name, count, const_cast<T**>(dev));
+}
+
+// Every device pointer of the arguments (the outputs apart, which the caller owns), allocated, uploaded or reset.
+static int align_buffers(const AlignJob& job, const AlignPlan& p, const LocPlan& lp, const ChunkOpts& co, AlignArgs& a, LocLaunch& ll) {
+    Context& c = ctx();
+    hipStream_t stream = job.stream;
+    const size_t n = static_cast<size_t>(job.batch.n), nsec = static_cast<size_t>(job.nsec);
+    SL_TRY(call_table(co, "align.tab", p.rows.data(), p.rows.size(), &a.tables, stream));
+    SL_TRY(call_table(co, "align.rz", p.rowzero.data(), p.rowzero.size(), &a.rowzero, stream));
+    SL_TRY(call_table(co, "align.cb", p.colbase.data(), p.colbase.size(), &a.colbase, stream));
+    SL_TRY(call_table(co, "align.ref", reinterpret_cast<const uint8_t*>(job.ref), static_cast<size_t>(job.R), &a.refchars, stream));
+    if (nsec) {
+        SL_TRY(call_table(co, "align.ss", job.sec_starts, nsec, &a.sec_s, stream));
+        SL_TRY(call_table(co, "align.se", job.sec_ends, nsec, &a.sec_e, stream));
+    }
+    static const int sentinel[2] = {std::numeric_limits<int>::max(), 0};   // [0] bad-quality read, [1] walk exceeded its bound
+    SL_TRY(call_table(co, "align.bad", sentinel, 2, &a.badqual, stream));
+    if (p.mode == 4) {
+        static const int zero[LOC_STATS] = {};   // (static, as the sentinel: the copies may outlive this frame)
+        SL_TRY(call_table(co, "align.ltab", lp.tab.data(), lp.tab.size(), &a.loc_tab, stream));
+        SL_TRY(call_table(co, "align.lrz", lp.rz.data(), lp.rz.size(), &a.loc_rz, stream));
+        SL_TRY(call_table(co, "align.lstats", zero, LOC_STATS, &a.loc_stats, stream));
+    }
+    // a chunk that returns without waiting for its kernel must not leave copies from the caller's
+    // vectors in flight (nothing else is queued on the stream yet)
+    if (co.init_bad && !co.finish) SL_HIP(hipStreamSynchronize(stream));
+    if (p.wide) {
+        if (p.per_wave) SL_TRY(c.buffer("align.dirs", static_cast<size_t>(p.grid) * p.per_wave * p.word_bytes, &a.dirs));
+        SL_TRY(scratch("align.bnd", p.wide_strips > 1 ? static_cast<size_t>(p.grid) * 6 * (static_cast<size_t>(job.batch.max_len) + 2) : 8, &a.wide_bnd));
+        if (p.wide_band > 0) {
+            SL_TRY(scratch("align.redo", n + 2, &a.wide_redo));
+            SL_HIP(hipMemsetAsync(a.wide_redo, 0, sizeof(int), stream));
+        }
+        return 0;
+    }
+    if (p.mode) SL_TRY(c.buffer("align.dirs", static_cast<size_t>(p.grid) * NWAVES * p.per_wave * p.word_bytes, &a.dirs));
+    if (p.mode != 4) return 0;
+    SL_TRY(scratch("align.lredo", n + 2, &a.loc_redo));
+    SL_TRY(scratch("align.lout", n * 3, &a.loc_out));
+    SL_HIP(hipMemsetAsync(a.loc_redo, 0, 2 * sizeof(int), stream));
+    if (p.classes) {
+        SL_TRY(scratch("align.lcls", n, &a.loc_cls));
+        SL_TRY(scratch("align.lccount", static_cast<size_t>(2 * LOC_NCLS), &a.loc_ccount));
+        SL_TRY(scratch("align.lover", n + 2, &a.loc_over));
+        SL_TRY(scratch("align.lorder", n + 2, &ll.order));
+        SL_HIP(hipMemsetAsync(a.loc_ccount, 0, 2 * LOC_NCLS * sizeof(int), stream));
+        SL_HIP(hipMemsetAsync(a.loc_over, 0, 2 * sizeof(int), stream));
+        SL_TRY(c.buffer("align.rdirs", static_cast<size_t>(p.redo_grid) * std::max<size_t>(1, p.redo_per_wave * p.word_bytes * NWAVES), &ll.redo_dirs));
+        SL_TRY(c.side_stream(&ll.side, &ll.fork, &ll.join));
+    }
+    return 0;
+}
+
+// ... and everything else in them, from the job and the plan.
+static void align_args(const AlignJob& job, const AlignPlan& p, const LocPlan& lp, const ChunkOpts& co, AlignArgs& a) {
+    const AlignOut& out = job.out;
+    a.seq = job.batch.d_seq; a.nmask = job.batch.d_nmask; a.qual = job.batch.d_qual; a.off = job.batch.d_off; a.n = job.batch.n;
+    a.R = job.R; a.W = p.sh.W; a.ngroups = p.sh.ngroups; a.local = job.local ? 1 : 0;
+    a.qoffset = static_cast<int>(job.sc.enc_names[0]); a.navail = job.sc.enc_n;
+    a.GO = p.GO; a.GE = p.GE;
+    a.tab_doubles = static_cast<int>(p.rows.size()); a.row_bytes = static_cast<int>(job.sc.enc_n * sizeof(double));
+    a.scores = out.d_scores; a.starts = out.d_starts; a.ends = out.d_ends;
+    a.nsec = job.nsec; a.sec_so = out.d_sec_so; a.sec_wo = out.d_sec_wo;
+    a.dirs_per_wave = p.per_wave;
+    a.read_base = co.read_base; a.sec_stride = co.sec_stride ? co.sec_stride : job.batch.n;
+    a.snap_head = snap_head(job.R); a.snap_win = snap_win(job.R, p.sh.W);
+    a.aln_ref = out.d_aln_ref; a.aln_qry = out.d_aln_qry; a.aln_len = out.d_aln_len; a.edits = out.d_edits;
+    a.win_nb = p.win_nb;
+    if (p.wide) { a.wide_maxlen = job.batch.max_len; a.wide_band = p.wide_band; }
+    if (p.mode == 4) {
+        a.loc_GO = lp.GO; a.loc_GE = lp.GE; a.loc_D = lp.D; a.loc_force = option(OPT_ALIGN_LOCATE) == 1 ? 1 : 0;
+        a.loc_framed = lp.framed ? 1 : 0;
+        a.loc_unit = lp.unit; a.loc_slack = lp.slack; a.loc_top = lp.top;
+    }
+}
+
+// Dynamic LDS beyond 48 KB needs the kernel's limit raised first.  The attribute belongs to the function on ONE device: it is
+// remembered per (device, kernel), so it is raised once and not at every launch, and once more on this thread's next device.
+static int raise_dynamic_lds(const void* kernel, size_t bytes) {
+    static thread_local std::map<std::pair<int, const void*>, size_t> limit;
+    if (bytes <= 48 * 1024) return 0;
+    size_t& set = limit[{ctx().device, kernel}];
+    if (bytes > set) SL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+    set = std::max(set, bytes);
+    return 0;
+}
+
+// Runtime values -> template arguments: f(Int<V1>{}, Int<V2>{}, ...) with, from each list, the V that equals the runtime
+// value behind it; NO_KERNEL when a value is in none.
+constexpr int NO_KERNEL = -1;
+template <int... Vs> struct Ints {};
+template <typename F> static int pick(F&& f) { return f(); }
+template <typename F, int... Vs, typename... Rest>
+static int pick(F&& f, Ints<Vs...>, int v, Rest... rest) {
+    int rc = NO_KERNEL;
+    (void)((v == Vs && ((rc = pick([&](auto... tags) { return f(Int<Vs>{}, tags...); }, rest...)), true)) || ...);
+    return rc;
+}
+
+// The instantiations of k_align the library is built with (each costs compile time and code-object size).
+// KLAST is known for one or two columns per lane and for interleaved alignments.
+constexpr bool shape_exists(int K, int rowf, int klast) {
+    if (rowf == 2) return (K == 2 || K == 4) && klast >= 0 && klast < K;
+    return K <= 2 ? klast >= 0 && klast < K : klast == -1;
+}
+constexpr bool mode_exists(int rowf, int mode, bool local, bool pensel, bool wlds) {
+    // interleaved alignments: local mode without penalty selects only (adaptor_align by snapshots or by the locator 5 / 6 and
+    // its window 4, score-only)
+    if (rowf == 2) return local && !pensel && (wlds ? mode == 4 : (mode == 0 || (mode >= 3 && mode <= 6)));
+    // adaptor_align is always local, general_align always global; score-only comes in both
+    return !wlds && (mode == 0 || (mode == 1 && local) || (mode == 3 && local && !pensel) || (mode == 2 && !local));
+}
+
+// One launch of k_align in the plan's shape; `mode` and `wlds` are the launch's (MODE 4 is a sequence of several).
+static int launch_k(const AlignPlan& p, int mode, bool wlds, const AlignArgs& a, int grid, size_t lds, hipStream_t s) {
+    const bool il = p.sh.rowf == 2;
+    const int rc = pick([&](auto k_, auto r_, auto l_) {
+        constexpr int K = decltype(k_)::value, ROWF = decltype(r_)::value, KLAST = decltype(l_)::value;
+        if constexpr (!shape_exists(K, ROWF, KLAST)) return NO_KERNEL;
+        else {
+            const int rcm = pick([&](auto m_, auto g_, auto p_, auto w_) {
+                constexpr int MODE = decltype(m_)::value;
+                constexpr bool LOCAL = decltype(g_)::value != 0, PENSEL = decltype(p_)::value != 0, WLDS = decltype(w_)::value != 0;
+                if constexpr (!mode_exists(ROWF, MODE, LOCAL, PENSEL, WLDS)) return NO_KERNEL;
+                else {
+                    if constexpr (WLDS) SL_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(&k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS>), lds));
+                    hipLaunchKernelGGL((k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
+                    return 0;
+                }
+            }, Ints<0, 1, 2, 3, 4, 5, 6>{}, mode, Ints<0, 1>{}, a.local, Ints<0, 1>{}, p.pensel, Ints<0, 1>{}, wlds);
+            return rcm != NO_KERNEL ? rcm : fail(il ? "sarlacc_amd: interleaved alignments serve local modes 0 and 3 only" : "sarlacc_amd: unsupported alignment mode");
+        }
+    }, Ints<1, 2, 4, 8, 16>{}, p.sh.K, Ints<0, 1, 2>{}, p.sh.rowf, Ints<-1, 0, 1, 2, 3>{}, p.klast);
+    // (an interleaved shape with K and mode both unknown raised the mode's message before: plan_align produces neither)
+    return rc != NO_KERNEL ? rc : fail(il ? "sarlacc_amd: unsupported columns-per-lane %d for interleaved alignments" : "sarlacc_amd: unsupported columns-per-lane %d", p.sh.K);
+}
+
+// MODE 4: the locator, the windows, the snapshot kernel on what they could not certify.
+static int launch_locate(const AlignPlan& p, const AlignArgs& a, const LocLaunch& ll, hipStream_t s) {
+    const int grid = static_cast<int>(p.grid);
+    // the locator (its LDS: rings + the integer table), the windows, then the snapshot kernel on the reads the windows
+    // put on their list (count read on the device)
+    const size_t lds5 = sizeof(uint16_t) * NWAVES * NGMAX2 * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
+    SL_TRY(launch_k(p, a.loc_framed ? 6 : 5, false, a, grid, lds5, s));
+    AlignArgs r = a;
+    r.bad_done = 1;
+    // the windows: with the code ring in LDS behind the maps (three wavefronts per SIMD), or the tile alone
+    const size_t lds4 = p.lds + static_cast<size_t>(NWAVES) * a.win_nb * 64 * sizeof(uint32_t);
+    auto windows = [&](const AlignArgs& w) { return a.win_nb ? launch_k(p, 4, true, w, grid, lds4, s) : launch_k(p, 4, false, w, grid, p.lds, s); };
+    if (!p.classes) {
+        SL_TRY(windows(a));
+        r.read_list = a.loc_redo;
+        return launch_k(p, 3, false, r, grid, p.lds, s);
+    }
+    // The locator has listed the oversize reads: the snapshot kernel aligns them on the side stream while this one
+    // orders and runs the windows.  Both snapshot launches are small (their item loop strides) and share tiles: the
+    // second, on the reads whose walk stalled, starts after the join.
+    r.dirs = ll.redo_dirs;
+    r.dirs_per_wave = p.redo_per_wave;
+    SL_HIP(hipEventRecord(ll.fork, s));
+    SL_HIP(hipStreamWaitEvent(ll.side, ll.fork, 0));
+    r.read_list = a.loc_over;
+    SL_TRY(launch_k(p, 3, false, r, p.redo_grid, p.lds, ll.side));
+    SL_HIP(hipEventRecord(ll.join, ll.side));
+    hipLaunchKernelGGL(k_loc_order, dim3(static_cast<unsigned>((a.n + 255) / 256)), dim3(256), 0, s, a.loc_cls, a.n, a.loc_ccount, ll.order);
+    AlignArgs w = a;
+    w.read_list = ll.order;
+    w.bad_done = 1;
+    SL_TRY(windows(w));
+    SL_HIP(hipStreamWaitEvent(s, ll.join, 0));
+    r.read_list = a.loc_redo;
+    return launch_k(p, 3, false, r, p.redo_grid, p.lds, s);
+}
+
+// References beyond MAX_REF columns (the queue kernel with a band runs twice: then with every cell's codes, over the reads whose walks left it).
+static int launch_wide(const AlignPlan& p, AlignArgs a, hipStream_t stream) {
+    constexpr int K = WIDE_K;
+    const dim3 g(static_cast<unsigned>(p.grid)), b(static_cast<unsigned>(p.wide_T));
+    const int mode = p.mode == 3 ? 1 : p.mode;
+    auto launch_q = [&]() { return pick([&](auto m_) {
+        constexpr int MODE = decltype(m_)::value;
+        SL_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(&k_align_wide_q<K, MODE>), p.lds));
+        hipLaunchKernelGGL((k_align_wide_q<K, MODE>), g, b, p.lds, stream, a);
+        return 0;
+    }, Ints<0, 1, 2>{}, mode); };
+    if (p.wide_queue) {
+        SL_TRY(launch_q());
+        if (p.wide_band <= 0) return 0;
+        a.wide_band = 0; a.wide_list = a.wide_redo + 1;
+        return launch_q();
+    }
+    return pick([&](auto m_, auto p_, auto s_) {
+        constexpr int MODE = decltype(m_)::value;
+        constexpr bool PENSEL = decltype(p_)::value != 0, STRIPS = decltype(s_)::value != 0;
+        SL_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(&k_align_wide<K, MODE, PENSEL, STRIPS>), p.lds));
+        hipLaunchKernelGGL((k_align_wide<K, MODE, PENSEL, STRIPS>), g, b, p.lds, stream, a);
+        return 0;
+    }, Ints<0, 1, 2>{}, mode, Ints<0, 1>{}, p.pensel, Ints<0, 1>{}, p.wide_strips > 1);
+}
+
+static int report_align(const AlignPlan& p, const LocPlan& lp, const AlignArgs& a, hipStream_t stream, int* bad_qual_read) {
+    Context& c = ctx();
+    const int *d_stats = a.loc_stats, *d_ccount = a.loc_ccount;
     int flags[2] = {0, 0}, lstats[LOC_STATS] = {}, ccount[LOC_NCLS] = {};
-    SL_HIP(hipMemcpyAsync(flags, d_bad, sizeof flags, hipMemcpyDeviceToHost, stream));
+    SL_HIP(hipMemcpyAsync(flags, a.badqual, sizeof flags, hipMemcpyDeviceToHost, stream));
     if (d_stats) SL_HIP(hipMemcpyAsync(lstats, d_stats, sizeof lstats, hipMemcpyDeviceToHost, stream));
     if (d_ccount) SL_HIP(hipMemcpyAsync(ccount, d_ccount, sizeof ccount, hipMemcpyDeviceToHost, stream));
     SL_HIP(hipStreamSynchronize(stream));
     *bad_qual_read = flags[0];
     // adaptor_align calls: reads the locator handed to the snapshot kernel, and walks of its window that stalled (-1: the
     // call ran the snapshot path alone)
-    if (kernel_mode == 3 || kernel_mode == 4) {
+    if (p.mode == 3 || p.mode == 4) {
         c.counts["align_redo"] = d_stats ? lstats[0] : -1.0;
         c.counts["align_stalls"] = d_stats ? lstats[1] : -1.0;
         // reads the locator itself listed as oversize (part of align_redo; 0 without window classes), and the steps the
@@ -2523,16 +2418,11 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
         // ring (-1: the call ran without the ring)
         unsigned long long wglob = 0;
         std::memcpy(&wglob, lstats + 6, sizeof wglob);
-        c.counts["align_walk_global"] = d_stats && win_nb ? static_cast<double>(wglob) : -1.0;
-        c.counts["align_walk_left_ring"] = d_stats && win_nb ? lstats[3] : -1.0;
+        c.counts["align_walk_global"] = d_stats && p.win_nb ? static_cast<double>(wglob) : -1.0;
+        c.counts["align_walk_left_ring"] = d_stats && p.win_nb ? lstats[3] : -1.0;
         // reads per window class (a class is 8 steps) of the call's last launch, "align_window_class_<c>": diagnostic, for
         // the tests and the perf records
-        static const std::vector<std::string> class_keys = [] {
-            std::vector<std::string> v;
-            for (int x = 0; x < LOC_NCLS; ++x) v.push_back("align_window_class_" + std::to_string(x));
-            return v;
-        }();
-        for (int x = 1; x < LOC_NCLS; ++x) c.counts[class_keys[x]] = d_ccount ? ccount[x] : -1.0;
+        for (int x = 1; x < LOC_NCLS; ++x) c.counts["align_window_class_" + std::to_string(x)] = d_ccount ? ccount[x] : -1.0;
         // the locator's scale 2^k, negative where it ran un-framed (0: no locator)
         c.counts["align_locate_k"] = d_stats ? (lp.framed ? lp.k : -lp.k) : 0.0;
     }
@@ -2540,322 +2430,47 @@ int run_align(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qua
     return 0;
 }
 
-// Error that the reference would raise first while looping over the reads
-// (length mismatch is tested before each alignment, src/adaptor_align.cpp:51-53;
-// inside an alignment column 1 is evaluated first: its reference character, then
-// the qualities of every row, then the remaining reference characters).
-int first_error(int64_t n, const int64_t* seq_off, const int64_t* qual_off, const char* ref, int R,
-                int bad_qual_read) {
-    int64_t len_bad = -1;
-    if (qual_off)
-        for (int64_t i = 0; i < n; ++i)
-            if (seq_off[i + 1] - seq_off[i] != qual_off[i + 1] - qual_off[i]) { len_bad = i; break; }
-    int first_bad_col = -1;
-    uint32_t tmp;
-    for (int col = 0; col < R; ++col)
-        if (column_info(ref[col], &tmp)) { first_bad_col = col; break; }
-    int64_t first_nonempty = -1;
-    if (first_bad_col >= 0)
-        for (int64_t i = 0; i < n; ++i)
-            if (seq_off[i + 1] - seq_off[i] > 0) { first_nonempty = i; break; }
-
-    const int64_t INF = std::numeric_limits<int64_t>::max();
-    const int64_t e_len = len_bad >= 0 ? len_bad : INF;
-    const int64_t e_qual = (R > 0 && bad_qual_read != std::numeric_limits<int>::max()) ? bad_qual_read : INF;
-    const int64_t e_ref = first_nonempty >= 0 ? first_nonempty : INF;
-    const int64_t first = std::min(e_len, std::min(e_qual, e_ref));
-    if (first == INF) return 0;
-    if (first == e_len) return fail("sequence and quality strings should have the same length");
-    if (first == e_ref && first_bad_col == 0) return fail("unrecognized base in reference sequence");
-    if (first == e_qual) return fail("quality cannot be lower than smallest encoded value");
-    return fail("unrecognized base in reference sequence");
-}
-
-// Uploads a batch given host string sets.  Reads whose quality string has a
-// different length make the whole call fail later (first_error), so qualities
-// are copied with the sequence offsets only when every length agrees.
-int upload_batch(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off,
-                 int64_t n, HostBatch* hb, hipStream_t s, bool defer_data) {
-    int64_t mx = 0;
-    bool same = true;
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t L = seq_off[i + 1] - seq_off[i];
-        mx = std::max(mx, L);
-        if (L != qual_off[i + 1] - qual_off[i]) { same = false; if (hb->len_bad < 0) hb->len_bad = i; }
+// One reference against a batch on the device: tables, plan, buffers, arguments, launch, report.
+// (ChunkOpts, align_host.hpp: a host call may hand its batch over in chunks.)
+int run_align(const AlignJob& job, int* bad_qual_read, const ChunkOpts& co) {
+    Context& c = ctx();
+    hipStream_t stream = job.stream;
+    const int64_t n = job.batch.n;
+    if (co.init_bad) *bad_qual_read = std::numeric_limits<int>::max();
+    if (n <= 0) return 0;
+    if (job.sc.enc_n > 256) return fail("sarlacc_amd: encoding vector longer than 256 entries");
+    if (n > std::numeric_limits<int>::max() - 8) return fail("sarlacc_amd: more than 2^31 reads in one call");
+    AlignPlan p;
+    p.GO = job.sc.gapopen + job.sc.gapext; p.GE = job.sc.gapext;  // (src/reference_align.cpp:8)
+    if (job.R == 0) {
+        const int bs = 256;
+        const AlignOut& out = job.out;
+        hipLaunchKernelGGL(k_align_emptyref, dim3(static_cast<unsigned>((n + bs - 1) / bs)), dim3(bs), 0, stream,
+                           job.batch.d_off, static_cast<long long>(n), job.local ? 1 : 0, p.GO, p.GE, out.d_scores, out.d_starts,
+                           out.d_ends, job.nsec, out.d_sec_so, out.d_sec_wo, out.d_aln_len, out.d_edits, job.batch.d_seq,
+                           out.d_aln_ref, out.d_aln_qry);
+        SL_HIP(hipGetLastError());
+        return 0;
     }
-    if (mx > std::numeric_limits<int32_t>::max() / 2) return fail("sarlacc_amd: read longer than 2^30 bases");
-    hb->max_len = static_cast<int32_t>(mx);
-    if (!same) return 0;
-    const int64_t base = n ? seq_off[0] : 0;
-    const int64_t total = n ? seq_off[n] - base : 0;
-    std::vector<int64_t> rel(static_cast<size_t>(n) + 1);
-    for (int64_t i = 0; i <= n; ++i) rel[i] = (n ? seq_off[i] : 0) - base;
-    if (defer_data) {   // the caller copies the bases and qualities chunk by chunk
-        SL_TRY(scratch("batch.seq", static_cast<size_t>(total), &hb->d_seq));
-        SL_TRY(scratch("batch.qual", static_cast<size_t>(total), &hb->d_qual));
+    LocPlan lp;
+    SL_TRY(plan_align(job, c.num_cu, p, lp));
+    AlignArgs a{};
+    LocLaunch ll;
+    SL_TRY(align_buffers(job, p, lp, co, a, ll));
+    align_args(job, p, lp, co, a);
+    if (co.stage) SL_TRY(c.stage_begin(co.stage, stream));
+    else SL_HIP(hipEventRecord(c.ev_start, stream));
+    if (p.wide) SL_TRY(launch_wide(p, a, stream));
+    else if (p.mode == 4) SL_TRY(launch_locate(p, a, ll, stream));
+    else SL_TRY(launch_k(p, p.mode, false, a, static_cast<int>(p.grid), p.lds, stream));
+    SL_HIP(hipGetLastError());
+    if (co.stage) {
+        SL_TRY(c.stage_end(co.stage, stream));
     } else {
-        SL_TRY(upload("batch.seq", reinterpret_cast<const uint8_t*>(seq) + base, static_cast<size_t>(total), &hb->d_seq, s));
-        SL_TRY(upload("batch.qual", reinterpret_cast<const uint8_t*>(qual) + (n ? qual_off[0] : 0), static_cast<size_t>(total), &hb->d_qual, s));
+        SL_HIP(hipEventRecord(c.ev_stop, stream));
+        c.timed = true;
     }
-    SL_TRY(upload("batch.off", rel.data(), rel.size(), &hb->d_off, s));
-    if (defer_data) SL_HIP(hipStreamSynchronize(s));   // `rel` goes out of scope
-    return 0;
-}
-
-static int check_sections(const int32_t* ss, const int32_t* se, int nsec, int R) {
-    for (int x = 0; x < nsec; ++x)
-        if (ss[x] < 0 || ss[x] > R || se[x] < 0 || se[x] > R)
-            return fail("sarlacc_amd: section bounds outside the adaptor (the reference reads out of range here)");
-    return 0;
-}
-
-static int host_align(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off, int64_t n,
-                      const double* enc_errors, const char* enc_names, int enc_n, double gapopen, double gapext,
-                      const char* ref, int R, bool local, int kernel_mode,
-                      const int32_t* sec_starts, const int32_t* sec_ends, int nsec,
-                      double* scores, int32_t* starts, int32_t* ends, int32_t* sec_so, int32_t* sec_wo,
-                      int32_t* edits, char* aln_ref, char* aln_qry, int64_t* aln_off, int64_t aln_cap) {
-    SL_TRY(check_encoding(enc_errors, enc_names, enc_n));
-    if (n < 0) return fail("sarlacc_amd: negative number of sequences");
-    if (kernel_mode == 1) SL_TRY(check_sections(sec_starts, sec_ends, nsec, R));
-    SL_TRY(ensure_device());
-    hipStream_t s = nullptr;
-    if (n == 0) { if (aln_off) aln_off[0] = 0; return 0; }
-
-    // Large score / map calls go to the device in chunks: the bases and qualities of chunk k+1
-    // cross PCIe on a stream of their own while chunk k is aligned.
-    const int64_t total_bytes = seq_off[n] - seq_off[0];
-    int64_t nchunks = 1;
-    if (kernel_mode != 2 && R > 0) {
-        if (total_bytes >= (static_cast<int64_t>(512) << 20)) nchunks = std::min<int64_t>(8, total_bytes / (static_cast<int64_t>(256) << 20));
-        if (option(OPT_ALIGN_CHUNKS) > 0) nchunks = option(OPT_ALIGN_CHUNKS);   // testing
-        nchunks = std::max<int64_t>(1, std::min<int64_t>(nchunks, n));
-    }
-    HostBatch hb;
-    SL_TRY(upload_batch(seq, seq_off, qual, qual_off, n, &hb, s, nchunks > 1));
-    if (hb.len_bad >= 0) {
-        // reads before the offending one could still raise an earlier error, but
-        // only a bad reference character is detectable without the qualities
-        return first_error(n, seq_off, qual_off, ref, R, std::numeric_limits<int>::max());
-    }
-    AlignOut out;
-    const size_t nn = static_cast<size_t>(n);
-    SL_TRY(scratch("out.scores", nn, &out.d_scores));
-    if (kernel_mode == 1) {
-        SL_TRY(scratch("out.starts", nn, &out.d_starts));
-        SL_TRY(scratch("out.ends", nn, &out.d_ends));
-        SL_TRY(scratch("out.sso", nn * std::max(nsec, 1), &out.d_sec_so));
-        SL_TRY(scratch("out.swo", nn * std::max(nsec, 1), &out.d_sec_wo));
-    }
-    const int64_t total = seq_off[n] - seq_off[0];
-    const size_t aln_bytes = static_cast<size_t>(total + n * R);
-    if (kernel_mode == 2) {
-        SL_TRY(scratch("out.aref", aln_bytes, &out.d_aln_ref));
-        SL_TRY(scratch("out.aqry", aln_bytes, &out.d_aln_qry));
-        SL_TRY(scratch("out.alen", nn, &out.d_aln_len));
-        SL_TRY(scratch("out.edits", nn, &out.d_edits));
-    }
-    int bad = 0;
-    if (nchunks == 1) {
-        SL_TRY(run_align(hb.d_seq, nullptr, hb.d_qual, hb.d_off, n, hb.max_len, enc_errors, enc_names, enc_n, gapopen, gapext,
-                         ref, R, local, kernel_mode, sec_starts, sec_ends, nsec, out, s, &bad));
-    } else {
-        hipStream_t copy_stream = nullptr;
-        SL_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-        std::vector<hipEvent_t> ready(static_cast<size_t>(nchunks), nullptr);
-        const int64_t sbase = seq_off[0], qbase = qual_off[0];
-        auto bound = [&](int64_t k) { return n * k / nchunks; };
-        auto send = [&](int64_t k) -> int {   // bases and qualities of the reads of chunk k
-            const int64_t lo = seq_off[bound(k)] - sbase, hi = seq_off[bound(k + 1)] - sbase;
-            if (hi > lo) {
-                SL_HIP(hipMemcpyAsync(hb.d_seq + lo, seq + sbase + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, copy_stream));
-                SL_HIP(hipMemcpyAsync(hb.d_qual + lo, qual + qbase + lo, static_cast<size_t>(hi - lo), hipMemcpyHostToDevice, copy_stream));
-            }
-            SL_HIP(hipEventCreateWithFlags(&ready[k], hipEventDisableTiming));
-            SL_HIP(hipEventRecord(ready[k], copy_stream));
-            return 0;
-        };
-        int rc = send(0);
-        for (int64_t k = 0; k < nchunks && !rc; ++k) {
-            const int64_t lo = bound(k), hi = bound(k + 1);
-            rc = hipStreamWaitEvent(s, ready[k], 0) == hipSuccess ? 0 : fail("HIP error waiting for a chunk upload");
-            if (rc) break;
-            AlignOut co_out = out;
-            co_out.d_scores = out.d_scores + lo;
-            if (out.d_starts) { co_out.d_starts = out.d_starts + lo; co_out.d_ends = out.d_ends + lo; }
-            if (out.d_sec_so) { co_out.d_sec_so = out.d_sec_so + lo; co_out.d_sec_wo = out.d_sec_wo + lo; }
-            ChunkOpts co;
-            co.sec_stride = n; co.read_base = static_cast<int>(lo); co.init_bad = (k == 0); co.finish = (k + 1 == nchunks);
-            rc = run_align(hb.d_seq, nullptr, hb.d_qual, hb.d_off + lo, hi - lo, hb.max_len, enc_errors, enc_names, enc_n, gapopen,
-                           gapext, ref, R, local, kernel_mode, sec_starts, sec_ends, nsec, co_out, s, &bad, co);
-            if (!rc && k + 1 < nchunks) rc = send(k + 1);   // travels while chunk k is being aligned
-        }
-        (void)hipStreamSynchronize(copy_stream);
-        (void)hipStreamSynchronize(s);
-        for (hipEvent_t e : ready) if (e) (void)hipEventDestroy(e);
-        (void)hipStreamDestroy(copy_stream);
-        if (rc) return rc;
-    }
-    SL_TRY(first_error(n, seq_off, nullptr, ref, R, bad));
-
-    SL_HIP(hipMemcpy(scores, out.d_scores, nn * sizeof(double), hipMemcpyDeviceToHost));
-    if (kernel_mode == 1) {
-        SL_HIP(hipMemcpy(starts, out.d_starts, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
-        SL_HIP(hipMemcpy(ends, out.d_ends, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (nsec) {
-            SL_HIP(hipMemcpy(sec_so, out.d_sec_so, nn * nsec * sizeof(int32_t), hipMemcpyDeviceToHost));
-            SL_HIP(hipMemcpy(sec_wo, out.d_sec_wo, nn * nsec * sizeof(int32_t), hipMemcpyDeviceToHost));
-        }
-    }
-    if (kernel_mode == 2) {
-        SL_HIP(hipMemcpy(edits, out.d_edits, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (aln_ref) {
-            std::vector<uint8_t> hr(aln_bytes), hq(aln_bytes);
-            std::vector<int32_t> hl(nn);
-            SL_HIP(hipMemcpy(hr.data(), out.d_aln_ref, aln_bytes, hipMemcpyDeviceToHost));
-            SL_HIP(hipMemcpy(hq.data(), out.d_aln_qry, aln_bytes, hipMemcpyDeviceToHost));
-            SL_HIP(hipMemcpy(hl.data(), out.d_aln_len, nn * sizeof(int32_t), hipMemcpyDeviceToHost));
-            int64_t used = 0;
-            aln_off[0] = 0;
-            for (int64_t i = 0; i < n; ++i) {
-                const int64_t base = (seq_off[i] - seq_off[0]) + i * static_cast<int64_t>(R);
-                const int32_t m = hl[i];
-                if (used + m > aln_cap) return fail("sarlacc_amd: alignment string buffer too small");
-                for (int32_t x = 0; x < m; ++x) {  // the device wrote them end-first
-                    aln_ref[used + x] = static_cast<char>(hr[base + m - 1 - x]);
-                    aln_qry[used + x] = static_cast<char>(hq[base + m - 1 - x]);
-                }
-                used += m;
-                aln_off[i + 1] = used;
-            }
-        }
-    }
-    return 0;
+    return co.finish ? report_align(p, lp, a, stream, bad_qual_read) : 0;
 }
 
 }  // namespace sarlacc
-
-using namespace sarlacc;
-
-extern "C" {
-
-int sarlacc_adaptor_align(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off,
-                          int64_t n, const double* enc_errors, const char* enc_names, int enc_n, double gapopen,
-                          double gapext, const char* adaptor, int adaptor_len, const int32_t* sec_starts,
-                          const int32_t* sec_ends, int nsec, double* scores, int32_t* starts, int32_t* ends,
-                          int32_t* sec_start_out, int32_t* sec_width_out) {
-    return host_align(seq, seq_off, qual, qual_off, n, enc_errors, enc_names, enc_n, gapopen, gapext, adaptor,
-                      adaptor_len, true, 1, sec_starts, sec_ends, nsec, scores, starts, ends, sec_start_out,
-                      sec_width_out, nullptr, nullptr, nullptr, nullptr, 0);
-}
-
-int sarlacc_adaptor_align_score_only(const char* seq, const int64_t* seq_off, const char* qual,
-                                     const int64_t* qual_off, int64_t n, const double* enc_errors,
-                                     const char* enc_names, int enc_n, double gapopen, double gapext,
-                                     const char* adaptor, int adaptor_len, double* scores) {
-    return host_align(seq, seq_off, qual, qual_off, n, enc_errors, enc_names, enc_n, gapopen, gapext, adaptor,
-                      adaptor_len, true, 0, nullptr, nullptr, 0, scores, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, 0);
-}
-
-int sarlacc_barcode_align(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off,
-                          int64_t n, const double* enc_errors, const char* enc_names, int enc_n, double gapopen,
-                          double gapext, const char* reference, int reference_len, double* scores) {
-    return host_align(seq, seq_off, qual, qual_off, n, enc_errors, enc_names, enc_n, gapopen, gapext, reference,
-                      reference_len, false, 0, nullptr, nullptr, 0, scores, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, nullptr, 0);
-}
-
-int sarlacc_general_align(const char* seq, const int64_t* seq_off, const char* qual, const int64_t* qual_off,
-                          int64_t n, const double* enc_errors, const char* enc_names, int enc_n, double gapopen,
-                          double gapext, const char* reference, int reference_len, int edit_only, double* scores,
-                          int32_t* edits, char* aln_ref, char* aln_query, int64_t* aln_off, int64_t aln_cap) {
-    return host_align(seq, seq_off, qual, qual_off, n, enc_errors, enc_names, enc_n, gapopen, gapext, reference,
-                      reference_len, false, 2, nullptr, nullptr, 0, scores, nullptr, nullptr, nullptr, nullptr, edits,
-                      edit_only ? nullptr : aln_ref, edit_only ? nullptr : aln_query, aln_off, aln_cap);
-}
-
-static int dev_align_impl(const uint8_t* d_seq, const uint8_t* d_nmask, const uint8_t* d_qual, const int64_t* d_off,
-                          int64_t n, int32_t max_len, const double* enc_errors, const char* enc_names, int enc_n,
-                          double gapopen, double gapext, const char* reference, int reference_len, int mode,
-                          const int32_t* sec_starts, const int32_t* sec_ends, int nsec, double* d_scores,
-                          int32_t* d_starts, int32_t* d_ends, int32_t* d_sec_start_out, int32_t* d_sec_width_out,
-                          void* stream) {
-    SL_TRY(check_encoding(enc_errors, enc_names, enc_n));
-    SL_TRY(ensure_device());
-    const bool trace = d_starts != nullptr;
-    if (trace && mode != 0) return fail("sarlacc_amd: positions are only defined for the local (adaptor) mode");
-    if (trace) SL_TRY(check_sections(sec_starts, sec_ends, nsec, reference_len));
-    AlignOut out;
-    out.d_scores = d_scores;
-    out.d_starts = d_starts;
-    out.d_ends = d_ends;
-    out.d_sec_so = d_sec_start_out;
-    out.d_sec_wo = d_sec_width_out;
-    int bad = 0;
-    SL_TRY(run_align(d_seq, d_nmask, d_qual, d_off, n, max_len, enc_errors, enc_names, enc_n, gapopen, gapext, reference,
-                     reference_len, mode == 0, trace ? 1 : 0, sec_starts, sec_ends, trace ? nsec : 0, out,
-                     static_cast<hipStream_t>(stream), &bad));
-    if (reference_len > 0 && bad != std::numeric_limits<int>::max())
-        return fail("quality cannot be lower than smallest encoded value");
-    uint32_t tmp;
-    for (int col = 0; col < reference_len; ++col)
-        if (column_info(reference[col], &tmp) && max_len > 0) return fail("unrecognized base in reference sequence");
-    return 0;
-}
-
-// 8 bases per thread: 2 bytes of 2-bit codes + 1 byte of exception bits
-__global__ void k_pack_reads(const uint8_t* seq, long long total, uint8_t* packed, uint8_t* nmask) {
-    const long long o = (blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x) * 8;
-    if (o >= total) return;
-    uint32_t bits = 0, exc = 0;
-    for (int k = 0; k < 8; ++k) {
-        const uint8_t c = (o + k < total) ? seq[o + k] : static_cast<uint8_t>('A');
-        uint32_t v;
-        switch (c) {
-            case 'A': v = 0; break;
-            case 'C': v = 1; break;
-            case 'G': v = 2; break;
-            case 'T': v = 3; break;
-            default: v = 0; exc |= 1u << k; break;
-        }
-        bits |= v << (2 * k);
-    }
-    packed[o / 4] = static_cast<uint8_t>(bits);
-    packed[o / 4 + 1] = static_cast<uint8_t>(bits >> 8);  // the buffer has one spare byte
-    nmask[o / 8] = static_cast<uint8_t>(exc);
-}
-
-int sarlacc_dev_pack_reads(const uint8_t* d_seq, int64_t total, uint8_t* d_packed, uint8_t* d_nmask, void* stream) {
-    if (total < 0) return fail("sarlacc_amd: negative size");
-    if (total == 0) return 0;
-    SL_TRY(ensure_device());
-    const long long threads = (total + 7) / 8;
-    hipLaunchKernelGGL(k_pack_reads, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), d_seq, static_cast<long long>(total), d_packed, d_nmask);
-    SL_HIP(hipGetLastError());
-    return 0;
-}
-
-int sarlacc_dev_align(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
-                      int32_t max_len, const double* enc_errors, const char* enc_names, int enc_n, double gapopen,
-                      double gapext, const char* reference, int reference_len, int mode, const int32_t* sec_starts,
-                      const int32_t* sec_ends, int nsec, double* d_scores, int32_t* d_starts, int32_t* d_ends,
-                      int32_t* d_sec_start_out, int32_t* d_sec_width_out, void* stream) {
-    return dev_align_impl(d_seq, nullptr, d_qual, d_off, n, max_len, enc_errors, enc_names, enc_n, gapopen, gapext,
-                          reference, reference_len, mode, sec_starts, sec_ends, nsec, d_scores, d_starts, d_ends,
-                          d_sec_start_out, d_sec_width_out, stream);
-}
-
-int sarlacc_dev_align_packed(const uint8_t* d_packed, const uint8_t* d_nmask, const uint8_t* d_qual,
-                             const int64_t* d_off, int64_t n, int32_t max_len, const double* enc_errors,
-                             const char* enc_names, int enc_n, double gapopen, double gapext, const char* reference,
-                             int reference_len, int mode, const int32_t* sec_starts, const int32_t* sec_ends, int nsec,
-                             double* d_scores, int32_t* d_starts, int32_t* d_ends, int32_t* d_sec_start_out,
-                             int32_t* d_sec_width_out, void* stream) {
-    if (!d_nmask) return fail("sarlacc_amd: packed alignment needs the exception mask of sarlacc_dev_pack_reads");
-    return dev_align_impl(d_packed, d_nmask, d_qual, d_off, n, max_len, enc_errors, enc_names, enc_n, gapopen, gapext,
-                          reference, reference_len, mode, sec_starts, sec_ends, nsec, d_scores, d_starts, d_ends,
-                          d_sec_start_out, d_sec_width_out, stream);
-}
-}

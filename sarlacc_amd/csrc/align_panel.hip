@@ -201,7 +201,7 @@ __global__ void k_panel_fold(long long n, const double* row, int id1, int32_t* b
     next[r] = x;
 }
 
-// What first_error (align.hip) needs to know about the batch: out[0] the first read holding a quality below the encoding's
+// What first_error (align_host.cpp) needs to know about the batch: out[0] the first read holding a quality below the encoding's
 // first name, out[1] the first read that is not empty (INT_MAX: none).
 __global__ void k_panel_scan(const uint8_t* qual, const int64_t* off, long long n, int qoffset, int* out) {
     const long long r = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x;
@@ -215,7 +215,7 @@ __global__ void k_panel_scan(const uint8_t* qual, const int64_t* off, long long 
     if (bad) atomicMin(out, me);
 }
 
-// The error sarlacc_barcode_align raises for this barcode (first_error in align.hip, which reads host offsets): inside an
+// The error sarlacc_barcode_align raises for this barcode (first_error in align_host.cpp, which reads host offsets): inside an
 // alignment column 1 is evaluated first -- its reference character, then the qualities of every row -- then the other columns.
 static int panel_error(const char* ref, int R, int64_t len_bad, int64_t bad_qual_read, int64_t first_nonempty) {
     const int64_t INF = std::numeric_limits<int64_t>::max();
@@ -328,11 +328,8 @@ static int run_panel(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t*
         a.bc_len = d_len; a.bc_id = d_id; a.bc_colbase = d_cb;
         a.best = d_best; a.cur = d_score; a.next = d_next; a.all = d_all;
     }
-    int waves_per_cu = 128;   // as run_align: far more workgroups than fit at once
-    if (option(OPT_ALIGN_WAVES_PER_CU) > 0) waves_per_cu = option(OPT_ALIGN_WAVES_PER_CU);
     const long long nbatch = (n + 63) / 64;
-    const int grid = static_cast<int>(std::min<long long>((nbatch + PANEL_WAVES - 1) / PANEL_WAVES,
-                                                          (static_cast<long long>(c.num_cu) * waves_per_cu + PANEL_WAVES - 1) / PANEL_WAVES));
+    const int grid = static_cast<int>(align_grid(nbatch, PANEL_WAVES, c.num_cu));   // as run_align: far more workgroups than fit at once
 
     // ---- the panel in its order ----
     hipLaunchKernelGGL(k_panel_init, dim3(nblk), dim3(256), 0, stream, static_cast<long long>(n), d_best, d_score, d_next);
@@ -358,7 +355,9 @@ static int run_panel(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t*
             f = f1;
             continue;
         }
-        AlignOut out;
+        AlignJob job{{d_seq, d_qual, d_off, n, max_len}, {enc_errors, enc_names, enc_n, gapopen, gapext}, barcodes + barcode_off[b], len_of(b), false, 0};
+        job.stream = stream;
+        AlignOut& out = job.out;
         if (d_all) out.d_scores = d_all + static_cast<size_t>(b) * static_cast<size_t>(n);
         else {
             if (!d_row) SL_TRY(scratch("panel.row", static_cast<size_t>(n), &d_row));
@@ -367,8 +366,7 @@ static int run_panel(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t*
         int bad = 0;
         ChunkOpts co;
         co.stage = "panel_dp";
-        SL_TRY(run_align(d_seq, nullptr, d_qual, d_off, n, max_len, enc_errors, enc_names, enc_n, gapopen, gapext,
-                         barcodes + barcode_off[b], len_of(b), false, 0, nullptr, nullptr, 0, out, stream, &bad, co));
+        SL_TRY(run_align(job, &bad, co));
         hipLaunchKernelGGL(k_panel_fold, dim3(nblk), dim3(256), 0, stream, static_cast<long long>(n), out.d_scores, b + 1, d_best,
                            d_score, d_next);
         SL_HIP(hipGetLastError());

@@ -322,14 +322,14 @@ static int profile_impl(const uint8_t* d_seq, const uint8_t* d_qual, const int64
     int bad_char = 0;
     for (int64_t k = 0; k < nchunks; ++k) {
         const int64_t lo = bounds[k], hi = bounds[k + 1];
+        AlignJob job{{d_seq, d_qual, d_off + lo, hi - lo, max_len}, {enc_errors, enc_names, enc_n, gapopen, gapext}, ref, R, false, 2};
+        job.stream = s;
         // the aligner addresses a slot by the read's offset in the whole batch: hand it the buffers shifted by the chunk's first offset
-        AlignOut out;
-        out.d_scores = d_scores + lo; out.d_edits = d_edits + lo; out.d_aln_len = d_alen;
-        out.d_aln_ref = d_aref - h_off[lo]; out.d_aln_qry = d_aqry - h_off[lo];
+        job.out.d_scores = d_scores + lo; job.out.d_edits = d_edits + lo; job.out.d_aln_len = d_alen;
+        job.out.d_aln_ref = d_aref - h_off[lo]; job.out.d_aln_qry = d_aqry - h_off[lo];
         ChunkOpts co;
         co.read_base = static_cast<int>(lo); co.init_bad = (k == 0); co.finish = true; co.stage = "profile_align";
-        SL_TRY(run_align(d_seq, nullptr, d_qual, d_off + lo, hi - lo, max_len, enc_errors, enc_names, enc_n, gapopen, gapext, ref, R, false, 2,
-                         nullptr, nullptr, 0, out, s, &bad_qual, co));
+        SL_TRY(run_align(job, &bad_qual, co));
         if (first_bad != ~0ull) continue;   // (the chain fails at that character; later chunks only matter for the aligner's own errors)
         a.aln_ref = d_aref; a.aln_qry = d_aqry; a.aln_len = d_alen; a.off = d_off + lo; a.n = hi - lo; a.read_base = lo;
         const unsigned gx = static_cast<unsigned>(std::max<long long>(1, std::min<long long>((hi - lo + PR_WAVES - 1) / PR_WAVES, static_cast<long long>(c.num_cu) * 4)));

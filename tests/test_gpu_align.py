@@ -393,6 +393,45 @@ def test_wide_local_mode_across_strips(oracle, oenc, enc):
         compare_adaptor(oracle, oenc, enc, reads, quals, ref, 5, 1, [0, 8000, 8100, 8191], [8192, min(8300, R), R, 8193])
 
 
+def test_dynamic_lds_limit_on_a_second_device(oracle, oenc, enc):
+    """Kernels launched with more than 48 KB of dynamic LDS need their limit raised on every device they run on, not once
+    per thread.  A reference of 8 192 columns takes 1 024 threads per alignment: k_align_wide (local: score-only
+    adaptor_align) then asks for 55 KB + the cost table, k_align_wide_q (global: barcode_align) for 45 KB + the table.  The
+    window kernel with its codes in LDS passes 48 KB too: at Phred+33 from 22 columns on when the adaptor holds all three
+    ambiguity classes (23 table rows of 752 B, 21 ring blocks of 1 KB, 8.5 KB of read rings, 2.9 KB of maps: 50 464 B).
+    Device 0 against the oracle, then the same calls on device 1: the same bits."""
+    import sarlacc_amd
+    from sarlacc_amd import _lib, calls
+    if sarlacc_amd.device_count() < 2:
+        pytest.skip("needs two devices")
+    rng = np.random.default_rng(48)
+    ref = "".join(rng.choice(list("ACGT"), 8192))
+    reads = ["", ref[10:11], ref[100:140], ref[4000:4041]]
+    quals = rand_quals(reads, 48)
+    adaptor = "ACGTMACGTVACGTNACGTACG"   # 22 columns
+    wreads = ["", "A", "TT" + adaptor.replace("M", "A").replace("V", "C").replace("N", "G") + "CAGTCAGTCAGTCAGT", "G" * 19 + adaptor[:22].replace("M", "C").replace("V", "T").replace("N", "T")]
+    wquals = rand_quals(wreads, 49)
+    assert [len(r) for r in reads] == [0, 1, 40, 41] and [len(r) for r in wreads] == [0, 1, 40, 41]
+
+    def run():
+        w = calls.adaptor_align(wreads, wquals, enc, 5, 1, adaptor, [4], [5])
+        assert _lib.stage_count("align_walk_global") >= 0, "the adaptor did not take the window kernel with its codes in LDS"
+        return [bits(calls.adaptor_align_score_only(reads, quals, enc, 5, 1, ref)), bits(calls.barcode_align(reads, quals, enc, 5, 1, ref)),
+                bits(w[0]), w[1], w[2], w[3][0], w[4][0]]
+
+    wo = oracle.adaptor_align(wreads, wquals, oenc, 5, 1, adaptor, [4], [5])
+    want = [bits(oracle.adaptor_align_score_only(reads, quals, oenc, 5, 1, ref)), bits(oracle.barcode_align(reads, quals, oenc, 5, 1, ref)),
+            bits(wo[0]), wo[1], wo[2], wo[3][0], wo[4][0]]
+    try:
+        first = run()
+        assert all(np.array_equal(a, b) for a, b in zip(want, first)), "device 0 differs from the oracle"
+        sarlacc_amd.set_device(1)
+        second = run()
+        assert all(np.array_equal(a, b) for a, b in zip(first, second)), "device 1 differs from device 0"
+    finally:
+        sarlacc_amd.set_device(0)
+
+
 def test_error_behaviour(oracle, oenc, enc):
     from sarlacc_amd import SarlaccError, calls
     with pytest.raises(SarlaccError, match="same length"):
