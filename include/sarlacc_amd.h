@@ -477,6 +477,9 @@ int sarlacc_set_msa_spec(int spec);
  *   at five wavefronts per SIMD; >= 2 that many blocks in the per-wave LDS code ring instead of the default; the counters
  *   "align_walk_global" (code words walks read from the global tile) and "align_walk_left_ring" (walks that read any)
  *   report the last call, -1 without the ring),
+ *   "align_locate_trim" (adaptor_align's locator in its frame: -1 the fill loop without its trims; 1 the jump score's lane
+ *   hand-over folded into its max alone, 2 the staging prefetch held as raw load results until the next refill alone, 3 both,
+ *   which is the default),
  *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel),
  *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a

@@ -161,6 +161,16 @@ __device__ __forceinline__ int lane_shr1(int v, int keep) {
     if (ROWF == 2) return __builtin_amdgcn_update_dpp(keep, v, 0x112 /* row_shr:2 */, 0xf, 0xf, false);
     return __builtin_amdgcn_update_dpp(v, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
 }
+// max(lane_shr1(v, -inf), other): the hand-over of a value whose only consumer is one max.  The fill value is the identity
+// of max, so the compiler folds the move into the max itself (v_max_i32 with the DPP modifier, `other` in the destination);
+// a leader, which has no source lane, ends with `other`.
+template <int ROWF>
+__device__ __forceinline__ int lane_shr1_max(int v, int other) {
+    static_assert(ROWF == 1 || ROWF == 2, "row shifts only");
+    constexpr int NEG = -0x7fffffff - 1;
+    if (ROWF == 1) return max(__builtin_amdgcn_update_dpp(NEG, v, 0x111 /* row_shr:1 */, 0xf, 0xf, false), other);
+    return max(__builtin_amdgcn_update_dpp(NEG, v, 0x112 /* row_shr:2 */, 0xf, 0xf, false), other);
+}
 template <int ROWF>
 __device__ __forceinline__ double lane_shr1(double v, double keep) {
     return mk64(lane_shr1<ROWF>(hi32(v), hi32(keep)), lane_shr1<ROWF>(lo32(v), lo32(keep)));
@@ -313,7 +323,7 @@ __global__ void __launch_bounds__(256) k_loc_order(const uint8_t* cls, long long
 // subtracts the opening penalty and selects nothing.  Only the "jump continued" flag differs
 // (true instead of false), and the true flag is raw && !(previous cell's move is the same gap
 // kind) -- the traceback applies that from the neighbour's code, which it reads anyway.
-template <int K, int MODE, bool LOCAL, int ROWF, int KLAST, bool PENSEL, bool WLDS = false>
+template <int K, int MODE, bool LOCAL, int ROWF, int KLAST, bool PENSEL, bool WLDS = false, int LTRIM = 0>
 // (six wavefronts per SIMD for the snapshot mode; five with eight alignments per wavefront: four columns per lane need the registers --
 // at six the recompute code spilled -- 2 182 -> 2 213 GCUPS on the same box)
 // (WLDS: the MODE 4 window with its codes in an LDS ring and the walk by whole lane groups, three wavefronts per SIMD, see WIN_LDS_WAVES)
@@ -454,13 +464,39 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                           static_cast<unsigned>(__shfl(static_cast<int>(start), sgl));
             stoffs[ps] = 0;
         }
-        struct Pf { uint32_t q, b; };   // four qualities (one per byte); four 2-bit base codes | four exception bits << 8
+        // four qualities (one per byte); four 2-bit base codes | four exception bits << 8.  RAWPF (the locator with LTRIM & 2):
+        // what the loads returned and nothing else, so that no wait for them stands between a refill and the next one, where
+        // stage4 decodes them -- q the four quality bytes and, ASCII reads, b the four characters, both taken from the read's
+        // last four bytes where fewer than four positions are left (stage4 shifts); packed reads, b / b2 and m / m2 the
+        // bytes of the bases and of the mask that hold the first and the last of the positions
+        struct Pf { uint32_t q, b, b2, m, m2; };
+        constexpr bool RAWPF = MODE == 6 && (LTRIM & 2) != 0;
         auto fetch4 = [&](int slen, long long sstart, int r0) -> Pf {
             const int r = r0 + sq;
             const int nv = min(max(slen - r, 0), 4);
-            Pf v{0u, 0u};
+            Pf v{0u, 0u, 0u, 0u, 0u};
             if (nv == 0) return v;
             const long long idx = sstart + r;
+            if (RAWPF) {   // every byte read lies inside the read, or is a byte of packed bases / mask that holds one of its positions
+                if (slen >= 4) {
+                    const long long at = idx - (4 - nv);
+                    __builtin_memcpy(&v.q, A.qual + at, 4);
+                    if (!A.nmask) __builtin_memcpy(&v.b, A.seq + at, 4);
+                } else {   // a read of one to three bases
+                    for (int e = 0; e < nv; ++e) {
+                        v.q |= static_cast<uint32_t>(A.qual[idx + e]) << (8 * e);
+                        if (!A.nmask) v.b |= static_cast<uint32_t>(A.seq[idx + e]) << (8 * e);
+                    }
+                }
+                if (A.nmask) {
+                    const long long last = idx + nv - 1;
+                    v.b = A.seq[idx >> 2];
+                    v.b2 = A.seq[last >> 2];
+                    v.m = A.nmask[idx >> 3];
+                    v.m2 = A.nmask[last >> 3];
+                }
+                return v;
+            }
             if (nv == 4) {
                 __builtin_memcpy(&v.q, A.qual + idx, 4);   // every byte read lies inside the read (no over-read of caller memory)
                 if (A.nmask) {  // 2-bit packed bases + exception mask (sarlacc_dev_pack_reads)
@@ -495,10 +531,30 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
             }
             return v;
         };
-        auto stage4 = [&](int sg, int slen, int r0, Pf v) {
+        auto stage4 = [&](int sg, int slen, int r0, Pf v, long long sstart = 0) {
             const int r = r0 + sq;
             uint32_t ent[4];
             bool bad = false;
+            if (RAWPF) {   // into the decoded form; what lies past the read's last position is masked below
+                const int nv = min(max(slen - r, 0), 4);
+                const int back = (slen >= 4 && nv > 0) ? 8 * (4 - nv) : 0;
+                v.q >>= back;
+                if (A.nmask) {
+                    const long long idx = sstart + r;
+                    const uint32_t two = (v.b | (v.b2 << 8)) >> ((idx & 3) * 2), exc = (v.m | (v.m2 << 8)) >> (idx & 7);
+                    v.b = (two & 0xffu) | ((exc & 0xfu) << 8);
+                } else {
+                    const uint32_t s4 = v.b >> back;
+                    v.b = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const uint32_t b = (s4 >> (8 * e)) & 0xffu;
+                        const uint32_t x = (b >> 1) & 3u, code = x ^ (x >> 1);         // A C G T -> 0 1 2 3
+                        const uint32_t exc = ((0x54474341u >> (8 * code)) & 0xffu) != b;   // anything else
+                        v.b |= (code << (2 * e)) | (exc << (8 + e));
+                    }
+                }
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 int qi = static_cast<int>(static_cast<signed char>((v.q >> (8 * e)) & 0xffu)) - A.qoffset;
@@ -741,17 +797,26 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
             const int GOi = A.loc_GO, GEi = A.loc_GE, D = A.loc_D;
             // framed: a block's last row lies UNR - 1 rows, that many GE, above its first in the frame
             const int D_lo = FRAMED ? D + (UNR - 1) * GEi : D;
+            // LTRIM & 1 (framed steady state): the horizontal jump score stays in the lane that formed it and its hand-over
+            // rides on the consumer's max (see lane_shr1_max); lj_src is that score before the move
+            constexpr bool FOLD = FRAMED && (LTRIM & 1) != 0;
             auto run_loc = [&](auto guard_tag, int t_begin, int t_end) {
                 constexpr bool GUARD = decltype(guard_tag)::value;
                 constexpr int NO_ROW = -0x7fffffff - 1;
                 int hi_blk = NO_ROW;   // steady state: first row of the last block that sets loc_hi (the row loc_lo takes too)
+                int lj_src = 0;
+                // what row_shr:2 will bring back: lji_in of the lane two to the right (the leaders' LOC_NEG is implied)
+                if (FOLD && !GUARD) lj_src = __builtin_amdgcn_update_dpp(lji_in, lji_in, 0x102 /* row_shl:2 */, 0xf, 0xf, false);
+                // RAWPF: nothing the item's first loads returned is still in flight when the steady state begins, so its blocks
+                // hold no wait for global memory (the refills' own loads are waited for at the next refill)
+                if (RAWPF && !GUARD) __builtin_amdgcn_s_waitcnt(0x0f70 /* vmcnt(0) */);
                 for (int t0 = t_begin; t0 < t_end; t0 += UNR) {
                     if ((t0 & 63) == 0) {
                         int t0s = t0;
                         asm volatile("" : "+s"(t0s));
 #pragma unroll
                         for (int ps = 0; ps < NPASS; ++ps) {
-                            stage4(sgs[ps], slens[ps], t0s, pf[ps]);
+                            stage4(sgs[ps], slens[ps], t0s, pf[ps], sstarts[ps]);
                             pf[ps] = fetch4(slens[ps], sstarts[ps], t0s + 64);
                         }
                     }
@@ -776,7 +841,7 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                             int lg = si_in - GOi;   // the cell to the left less the opening
 #pragma unroll
                             for (int k = 0; k < K; ++k) {
-                                const int H = max(FRAMED ? lj : lj - GEi, lg);
+                                const int H = (FOLD && !GUARD && k == 0) ? lane_shr1_max<ROWF>(lj_src, lg) : max(FRAMED ? lj : lj - GEi, lg);
                                 lj = H;
                                 const int V = max(UJi[k] - vgei[k], Sg[k]);
                                 UJi[k] = V;
@@ -810,10 +875,12 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                         // framed: column 0, which the leaders keep, is GE i; the register of two steps back holds GE (i - 1)
                         if (FRAMED) si_in = GUARD ? lane_shr1<ROWF>(left, GEi * ((x2 >> 1) + 2)) : lane_shr1<ROWF>(left, s_two_back + 2 * GEi);
                         else si_in = GUARD ? lane_shr1<ROWF>(left, si_in) : lane_shr1<ROWF>(left, s_two_back);
-                        lji_in = lane_shr1<ROWF>(lj, lji_in);
+                        if (FOLD && !GUARD) lj_src = lj;
+                        else lji_in = lane_shr1<ROWF>(lj, lji_in);
                         x2 += 2;
                     }
                 }
+                if (FOLD && !GUARD) lji_in = lane_shr1<ROWF>(lj_src, lji_in);   // the leaders keep their LOC_NEG
                 if (!GUARD && hi_blk != NO_ROW) loc_hi = hi_blk + 2 * (UNR - 1);
             };
             run_loc(Flag<true>{}, 0, t_a);
@@ -2308,27 +2375,37 @@ constexpr bool mode_exists(int rowf, int mode, bool local, bool pensel, bool wld
 }
 
 // One launch of k_align in the plan's shape; `mode` and `wlds` are the launch's (MODE 4 is a sequence of several).
-static int launch_k(const AlignPlan& p, int mode, bool wlds, const AlignArgs& a, int grid, size_t lds, hipStream_t s) {
+// (ltrim: the framed locator's LTRIM, see locate_trim)
+static int launch_k(const AlignPlan& p, int mode, bool wlds, const AlignArgs& a, int grid, size_t lds, hipStream_t s, int ltrim = 0) {
     const bool il = p.sh.rowf == 2;
+    if (ltrim && mode != 6) return fail("sarlacc_amd: internal error: a trimmed locator outside the frame");
     const int rc = pick([&](auto k_, auto r_, auto l_) {
         constexpr int K = decltype(k_)::value, ROWF = decltype(r_)::value, KLAST = decltype(l_)::value;
         if constexpr (!shape_exists(K, ROWF, KLAST)) return NO_KERNEL;
         else {
-            const int rcm = pick([&](auto m_, auto g_, auto p_, auto w_) {
-                constexpr int MODE = decltype(m_)::value;
+            const int rcm = pick([&](auto m_, auto g_, auto p_, auto w_, auto t_) {
+                constexpr int MODE = decltype(m_)::value, LTRIM = decltype(t_)::value;
                 constexpr bool LOCAL = decltype(g_)::value != 0, PENSEL = decltype(p_)::value != 0, WLDS = decltype(w_)::value != 0;
-                if constexpr (!mode_exists(ROWF, MODE, LOCAL, PENSEL, WLDS)) return NO_KERNEL;
+                if constexpr (!mode_exists(ROWF, MODE, LOCAL, PENSEL, WLDS) || (LTRIM != 0 && MODE != 6)) return NO_KERNEL;
                 else {
-                    if constexpr (WLDS) SL_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(&k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS>), lds));
-                    hipLaunchKernelGGL((k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
+                    if constexpr (WLDS) SL_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(&k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS, LTRIM>), lds));
+                    hipLaunchKernelGGL((k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS, LTRIM>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
                     return 0;
                 }
-            }, Ints<0, 1, 2, 3, 4, 5, 6>{}, mode, Ints<0, 1>{}, a.local, Ints<0, 1>{}, p.pensel, Ints<0, 1>{}, wlds);
+            }, Ints<0, 1, 2, 3, 4, 5, 6>{}, mode, Ints<0, 1>{}, a.local, Ints<0, 1>{}, p.pensel, Ints<0, 1>{}, wlds, Ints<0, 1, 2, 3>{}, ltrim);
             return rcm != NO_KERNEL ? rcm : fail(il ? "sarlacc_amd: interleaved alignments serve local modes 0 and 3 only" : "sarlacc_amd: unsupported alignment mode");
         }
     }, Ints<1, 2, 4, 8, 16>{}, p.sh.K, Ints<0, 1, 2>{}, p.sh.rowf, Ints<-1, 0, 1, 2, 3>{}, p.klast);
     // (an interleaved shape with K and mode both unknown raised the mode's message before: plan_align produces neither)
     return rc != NO_KERNEL ? rc : fail(il ? "sarlacc_amd: unsupported columns-per-lane %d for interleaved alignments" : "sarlacc_amd: unsupported columns-per-lane %d", p.sh.K);
+}
+
+// The framed locator's LTRIM (k_align): 1 the jump score's hand-over folded into its max (lane_shr1_max), 2 the staging
+// prefetch kept as raw load results until the next refill (RAWPF); both by default.  align_locate_trim = -1: neither (the
+// loop as it was: A/B, tests), 1 / 2: that one alone.
+static int locate_trim() {
+    const int o = option(OPT_ALIGN_LOCATE_TRIM);
+    return o < 0 ? 0 : o == 0 ? 3 : (o & 3);
 }
 
 // MODE 4: the locator, the windows, the snapshot kernel on what they could not certify.
@@ -2337,7 +2414,7 @@ static int launch_locate(const AlignPlan& p, const AlignArgs& a, const LocLaunch
     // the locator (its LDS: rings + the integer table), the windows, then the snapshot kernel on the reads the windows
     // put on their list (count read on the device)
     const size_t lds5 = sizeof(uint16_t) * NWAVES * NGMAX2 * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
-    SL_TRY(launch_k(p, a.loc_framed ? 6 : 5, false, a, grid, lds5, s));
+    SL_TRY(launch_k(p, a.loc_framed ? 6 : 5, false, a, grid, lds5, s, a.loc_framed ? locate_trim() : 0));
     AlignArgs r = a;
     r.bad_done = 1;
     // the windows: with the code ring in LDS behind the maps (three wavefronts per SIMD), or the tile alone

@@ -72,6 +72,7 @@ enum Opt {
     OPT_PROFILE_CHUNK_READS,  // profile_reads: reads per chunk of the batch (0 = by the byte budget of the aligner's scratch; tests force several chunks)
     OPT_ALIGN_WINDOW_CLASSES, // adaptor_align by the locator: -1 the windows in index order, one redo list filled by the window kernel and its launch on the caller's stream (A/B, tests)
     OPT_ALIGN_WINDOW_LDS,     // adaptor_align by the locator: -1 the window's codes in the global tile alone, five wavefronts per SIMD (A/B, tests); >= 2 that many blocks in the LDS code ring (tests)
+    OPT_ALIGN_LOCATE_TRIM,    // adaptor_align's framed locator: -1 the fill loop without its trims (A/B, tests); 1 the folded hand-over of the jump score alone, 2 the raw staging prefetch alone, 3 both (the default)
     OPT_N
 };
 int option(Opt o);
