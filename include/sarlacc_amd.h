@@ -374,14 +374,46 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
  * sarlacc_dev_copy copies bytes within device memory (ranges that do not overlap, any alignment): the tail of one
  * text buffer to the front of the next.  sarlacc_dev_rfind_byte reports the position of the last byte of d_text equal
  * to value (-1: none): where a block of lines ends.  Both return when the device has finished.
- * Out of scope: compressed output, BAM records, random access via .gzi, device inflate of gzip that is not BGZF
- * (the Python layer inflates that on the host). */
+ * Out of scope: compressed output, random access via .gzi, device inflate of gzip that is not BGZF (the Python
+ * layer inflates that on the host).
+ * BAM (SAM specification section 4.2: the same container around binary records) -> ranges.  d_bam holds nbytes of
+ * inflated BAM in device memory whose byte 0 is the start of an alignment record: the caller reads the header
+ * (magic, text, reference list) and starts every later buffer at the carried tail.  A record is block_size (int32)
+ * followed by block_size bytes, at any byte alignment.  sarlacc_dev_bam_index locates every record that lies wholly in
+ * the buffer -- exactly: each start is reached from byte 0 through size fields alone -- and reports their number in
+ * *n_records and in *used_bytes the offset of the first record that does not (nbytes when none is cut): the carry.
+ * first_record is the 1-based number of the buffer's first record among the file's alignment records, used in error
+ * messages; at_eof says that no bytes follow.  n_ref is the number of references of the header; a record's seqname
+ * code is its refID, or n_ref for refID -1 ('*', last in the seqinfo as on the SAM path).  restricted_mask (n_ref + 1
+ * bytes, the last for '*', NULL = no restriction) marks the names in `restricted`.  A record is kept when
+ * !(flag & 4), mapq >= minq (if use_minq) and its reference is marked (if a mask is given; a refID outside
+ * [-1, n_ref) is not).  Errors are "BAM record K: <reason>" for the lowest failing record: "file ends inside the
+ * record" (at_eof only), "block size below 32" (negative sizes included), on every record "record fields do not fit
+ * its block size" (l_read_name 0, a name without its NUL, l_seq < 0, or name + CIGAR + SEQ + QUAL beyond block_size),
+ * and on kept records, in this order: "POS is not a 32-bit integer" (pos 2^31 - 1), "reference ID outside the
+ * header's reference list", "no CIGAR on a kept record", "CIGAR operation code above 8", "malformed tags or CG tag
+ * behind a long-CIGAR stand-in", "CIGAR length above 2^31 - 1" (the width or a clip), "CIGAR has only H and S
+ * operations", "alignment end outside the 32-bit integer range".  A kept record whose CIGAR is <l_seq>S<n>N stands in
+ * for one of more than 65 535 operations: its tags are walked, and a CG tag of type B,I with at least one entry is the
+ * CIGAR; without a CG tag the two operations stand as they are.
+ * sarlacc_dev_bam_extract is step 2 of the same two-step contract as the SAM pair, with the parameters and the
+ * thread-local state of sarlacc_dev_sam_extract: start is pos + 1, the names are the read names without their NUL.
+ * sarlacc_bam_tile_bytes is the tile of the locator (tests place records around its multiples).  The locator takes
+ * 4 bytes of workspace per byte of d_bam.
+ * Out of scope: BAM output, .bai / .csi random access, CRAM, SEQ / QUAL of the records. */
 int sarlacc_bgzf_scan(const uint8_t* buf, int64_t nbytes, int64_t max_blocks, int64_t first_block, int64_t* comp_off,
                       int64_t* text_off, int64_t* n_blocks, int64_t* used_bytes, int* last_is_eof);
 int sarlacc_dev_bgzf_inflate(const uint8_t* d_comp, const int64_t* d_comp_off, const int64_t* d_text_off, int64_t n_blocks,
                              int64_t first_block, uint8_t* d_text, int check_crc, void* stream);
 int sarlacc_dev_copy(void* d_dst, const void* d_src, int64_t bytes, void* stream);
 int sarlacc_dev_rfind_byte(const uint8_t* d_text, int64_t nbytes, int value, int64_t* pos, void* stream);
+int sarlacc_dev_bam_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_record, int at_eof, int64_t n_ref,
+                          const uint8_t* restricted_mask, int use_minq, int64_t minq, int64_t* n_records,
+                          int64_t* used_bytes, int64_t* n_kept, int64_t* kept_name_bytes, void* stream);
+int sarlacc_dev_bam_extract(const uint8_t* d_bam, int32_t* d_ref, int32_t* d_start, int32_t* d_width,
+                            uint8_t* d_strand, int32_t* d_lclip, int32_t* d_rclip, uint8_t* d_names,
+                            int64_t* d_name_off, void* stream);
+int sarlacc_bam_tile_bytes(void);
 
 /* ------------------------------------------------------------------ */
 /* masked Levenshtein, neighbour search, clustering                      */

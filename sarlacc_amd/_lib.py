@@ -150,6 +150,9 @@ def _prototypes():
         "sarlacc_dev_fastq_format": (i, [p, p, p, p, p, i64, p, i64, i64, p, p]),
         "sarlacc_dev_sam_index": (i, [p, i64, i64, p, p, i64, p, p, p, i64, i, i64, p, p, p, p]),
         "sarlacc_dev_sam_extract": (i, [p, p, p, p, p, p, p, p, p, p]),
+        "sarlacc_dev_bam_index": (i, [p, i64, i64, i, i64, p, i, i64, p, p, p, p, p]),
+        "sarlacc_dev_bam_extract": (i, [p, p, p, p, p, p, p, p, p, p]),
+        "sarlacc_bam_tile_bytes": (i, []),
         "sarlacc_bgzf_scan": (i, [p, i64, i64, i64, p, p, p, p, p]),
         "sarlacc_dev_bgzf_inflate": (i, [p, p, p, i64, i64, p, i, p]),
         "sarlacc_dev_copy": (i, [p, p, i64, p]),

@@ -18,6 +18,7 @@
 // Streaming byte work, HBM-bound: 2 reads of the text by the line passes + the fields up to the end of the CIGAR.
 #include "common.hpp"
 #include "devprim.hpp"
+#include "sam_rec.hpp"
 #include "text_lines.hpp"
 
 #include "../../include/sarlacc_amd.h"
@@ -51,12 +52,6 @@ struct SamName {
     int code;           // seqinfo index, -1 for a `restricted` name that is not in the header
     int restricted;     // listed in `restricted`
     int pad;
-};
-
-// per line; written for kept lines only
-struct SamRec {
-    long long name_pos;
-    int ref, start, width, lclip, rclip, strand;
 };
 
 __host__ __device__ __forceinline__ unsigned long long fnv1a64(const uint8_t* s, long long n) {
@@ -294,12 +289,7 @@ __global__ void __launch_bounds__(SAM_THREADS) k_sam_scatter(const uint8_t* text
     }
 }
 
-// state of the last sarlacc_dev_sam_index call on this thread
-struct SamIndex {
-    const uint8_t* text = nullptr;
-    int64_t nlines = 0, nkept = 0, name_bytes = 0;
-};
-static thread_local SamIndex g_sam;
+thread_local SamIndex g_sam;   // (sam_rec.hpp; sarlacc_dev_bam_index of bam.hip fills it too)
 
 }  // namespace sarlacc
 
@@ -439,9 +429,12 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
         SL_TRY(scratch("sam.noff", static_cast<size_t>(nlines) + 1, &d_noff));
         Context& c = ctx();
         const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nlines, SAM_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
+        c.stage_reset("sam_scatter");
+        SL_TRY(c.stage_begin("sam_scatter", s));
         hipLaunchKernelGGL(k_sam_scatter, dim3(grid), dim3(SAM_THREADS), 0, s, d_text, d_rec, d_keep, d_koff, d_noff,
                            static_cast<long long>(nlines), d_ref, d_start, d_width, d_strand, d_lclip, d_rclip, d_names, d_name_off);
         SL_HIP(hipGetLastError());
+        SL_TRY(c.stage_end("sam_scatter", s));
     }
     SL_HIP(hipStreamSynchronize(s));
     return 0;

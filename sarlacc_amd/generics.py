@@ -745,6 +745,10 @@ def sam2ranges(sam, minq=10, restricted=None, block_bytes=256 << 20):
     "left.clip", "right.clip" (int32), "strand" ('+' / '-'), "names" (the QNAMEs) and "seqinfo" ({"seqnames": the @SQ
     names then '*', "seqlengths": int64, 0 for '*'}).  A header-only or empty file returns the empty result without a
     device.  A BGZF file (`.sam.gz` by bgzip) has its header inflated on the host and its body on the device; plain gzip is
-    inflated on the host (slow).  Departures from the reference: DESIGN.md §8, "Known deviations"."""
+    inflated on the host (slow).  A BAM file (BGZF whose inflated bytes start with the BAM magic) gives the table of the
+    equivalent SAM text: its header is read on the host, with the seqinfo taken from the binary reference list, and its
+    records are inflated, located and parsed on the device (bam.hip); a malformed record is refused as
+    "BAM record K: <reason>", K 1-based over the alignment records, and a CIGAR above 65 535 operations is read from its
+    CG tag.  Departures from the reference: DESIGN.md §8, "Known deviations"."""
     from .sam import sam2ranges as _sam2ranges
     return _sam2ranges(sam, minq=minq, restricted=restricted, block_bytes=block_bytes)

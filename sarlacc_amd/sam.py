@@ -6,6 +6,9 @@ regular expressions over every CIGAR (:49-74, .get_clip_length :80-95).  Where t
 ("Known deviations"): the first alignment record is kept (the reference's `skip = N` drops it), the
 seqinfo comes from the @SQ lines only whatever other header lines stand between them, and inputs on which the
 reference would produce NA or fail further down are refused with the 1-based file line.
+
+A BAM file takes the same road in its binary form: read_bam_header on the host, the records inflated on the device and
+located and parsed there (bam.hip: sarlacc_dev_bam_index / _extract); refusals name the 1-based alignment record.
 """
 import ctypes as C
 import math
@@ -125,23 +128,27 @@ class _Tables:
 
 def _parse_block(d_text, nbytes, first_line, tables, use_minq, thr):
     """One block of body text in HBM -> (number of lines, columns of the kept records)."""
-    from .resident import DevBuffer
     lib = _lib.lib()
     nlines, nk, nb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     check(lib.sarlacc_dev_sam_index(d_text, nbytes, first_line, tables.ref, tables.ref_off, tables.n_ref, tables.mask,
                                     tables.extra, tables.extra_off, tables.n_extra, 1 if use_minq else 0, thr, C.byref(nlines),
                                     C.byref(nk), C.byref(nb), None))
-    n = nk.value
+    return nlines.value, _columns(lib.sarlacc_dev_sam_extract, d_text, nk.value, nb.value)
+
+
+def _columns(extract, d_text, n, nbytes):
+    """Step 2 of either pair (sarlacc_dev_sam_extract / sarlacc_dev_bam_extract): the columns of the `n` kept records."""
+    from .resident import DevBuffer
     cols = DevBuffer(max(21 * n, 1))            # five int32 columns, then the strand bytes
-    names, noff = DevBuffer(max(nb.value, 1)), DevBuffer(8 * (n + 1))
+    names, noff = DevBuffer(max(nbytes, 1)), DevBuffer(8 * (n + 1))
     base = cols.ptr.value
-    check(lib.sarlacc_dev_sam_extract(d_text, *[base + 4 * n * k for k in (0, 1, 2)], base + 20 * n,
-                                      *[base + 4 * n * k for k in (3, 4)], names, noff, None))
+    check(extract(d_text, *[base + 4 * n * k for k in (0, 1, 2)], base + 20 * n,
+                  *[base + 4 * n * k for k in (3, 4)], names, noff, None))
     host = cols.to_numpy(np.uint8, 21 * n)
     out = [host[4 * n * k:4 * n * (k + 1)].view(np.int32) for k in range(5)] + [host[20 * n:21 * n]]
-    chars = names.to_numpy(np.uint8, nb.value)
+    chars = names.to_numpy(np.uint8, nbytes)
     out.append(StringSet(chars if chars.size else np.zeros(1, np.uint8), noff.to_numpy(np.int64, n + 1)))
-    return nlines.value, out
+    return out
 
 
 def blocks(fh, block_bytes):
@@ -242,14 +249,132 @@ def _bgzf_parts(path, block_bytes, restricted, use_minq, thr):
     return names, lengths, parts
 
 
+BAM_MAGIC = b"BAM\1"
+
+
+def is_bam(path):
+    """Whether the file is BGZF and its first four inflated bytes are the BAM magic."""
+    from . import bgzf
+    if bgzf.sniff(path) != bgzf.BGZF:
+        return False
+    head = b""
+    try:
+        with open(path, "rb") as fh:
+            for _, _, text in bgzf.host_blocks(fh):
+                head += text[:4 - len(head)]
+                if len(head) == 4:
+                    break
+    except SarlaccError:
+        return False        # a damaged first block: the BGZF text path reports it
+    return head == BAM_MAGIC
+
+
+class _HostBlocks:
+    """read(n) over bgzf.host_blocks that knows where the next unread byte lies: (file offset, number) of its BGZF block
+    and its offset in that block's inflated bytes."""
+
+    def __init__(self, fh):
+        from . import bgzf
+        self.gen, self.offset, self.number, self.text, self.p = bgzf.host_blocks(fh), 0, 0, b"", 0
+
+    def read(self, n, what):
+        out = []
+        while n > 0:
+            if self.p == len(self.text):
+                try:
+                    self.offset, self.number, self.text = next(self.gen)
+                except StopIteration:
+                    raise SarlaccError("BAM header: file ends inside %s" % what) from None
+                self.p = 0
+                continue
+            piece = self.text[self.p:self.p + n]
+            out.append(piece)
+            self.p += len(piece)
+            n -= len(piece)
+        return b"".join(out)
+
+    def i32(self, what):
+        return int.from_bytes(self.read(4, what), "little", signed=True)
+
+
+def read_bam_header(fh):
+    """The header of a BAM file opened in binary mode (SAM specification section 4.2), inflated on the host with zlib,
+    leading blocks only: magic, l_text, text, n_ref, then per reference l_name (which counts the NUL), name, l_ref.
+    Returns (seqinfo names + '*', lengths + 0, (file offset, number) of the BGZF block that holds the first byte after
+    the header and that byte's offset in the block's inflated bytes).  The seqinfo is the binary reference list, not the
+    @SQ lines of the text."""
+    r = _HostBlocks(fh)
+    if r.read(4, "the magic") != BAM_MAGIC:
+        raise SarlaccError("BAM header: the file does not start with the BAM magic")
+    l_text = r.i32("the header")
+    if l_text < 0:
+        raise SarlaccError("BAM header: negative text length")
+    r.read(l_text, "the header text")
+    n_ref = r.i32("the header")
+    if n_ref < 0:
+        raise SarlaccError("BAM header: negative number of references")
+    names, lengths, seen = [], [], set()
+    for k in range(n_ref):
+        l_name = r.i32("reference %d" % (k + 1))
+        if l_name < 0:
+            raise SarlaccError("BAM header: reference %d: negative name length" % (k + 1))
+        if l_name == 0:
+            raise SarlaccError("BAM header: reference %d: empty name field" % (k + 1))
+        raw = r.read(l_name, "reference %d" % (k + 1))
+        if raw[-1:] != b"\0":
+            raise SarlaccError("BAM header: reference %d: name without its NUL" % (k + 1))
+        l_ref = r.i32("reference %d" % (k + 1))
+        if l_ref < 0:
+            raise SarlaccError("BAM header: reference %d: negative length" % (k + 1))
+        name = raw[:-1].decode()
+        if name in seen or name == "*":
+            raise SarlaccError("BAM header: reference %d: duplicate name '%s'" % (k + 1, name))
+        seen.add(name)
+        names.append(name)
+        lengths.append(l_ref)
+    return names + ["*"], np.array(lengths + [0], dtype=np.int64), (r.offset, r.number, r.p)
+
+
+def _bam_parts(path, block_bytes, restricted, use_minq, thr):
+    """_bgzf_parts for a BAM file: the records are inflated on the device from the block that holds the first of them, a
+    parse block ends at its last complete record (used_bytes of sarlacc_dev_bam_index) and the rest is carried over on
+    the device; a buffer in which no record is complete grows."""
+    from . import bgzf
+    lib = _lib.lib()
+    with open(path, "rb") as fh:
+        names, lengths, origin = read_bam_header(fh)
+        mask = None
+        if restricted is not None:       # names that are not in the header never match
+            listed = set(restricted)
+            mask = np.array([n in listed for n in names], np.uint8)
+        fh.seek(origin[0])
+        stream = bgzf.DeviceTextStream(fh, block_bytes, first_block=origin[1], skip=origin[2])
+        parts, record, carry, eof = [], 1, None, False
+        while not eof:
+            d_bam, nbytes, eof = stream.next(carry)
+            if d_bam is None or nbytes == 0:
+                break
+            nrec, used, nk, nb = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            check(lib.sarlacc_dev_bam_index(d_bam, nbytes, record, 1 if eof else 0, len(names) - 1, mask, 1 if use_minq else 0,
+                                            thr, C.byref(nrec), C.byref(used), C.byref(nk), C.byref(nb), None))
+            if nrec.value:
+                parts.append(_columns(lib.sarlacc_dev_bam_extract, d_bam, nk.value, nb.value))
+                record += nrec.value
+            carry = (d_bam, used.value, nbytes - used.value) if used.value < nbytes else None
+    return names, lengths, parts
+
+
 def sam2ranges(sam, minq=10, restricted=None, block_bytes=256 << 20):
     """sam2ranges (R/sam2ranges.R:8-95).  See generics.sam2ranges.  `sam` may be plain text, BGZF (the body is inflated on
-    the device, bgzf.py) or plain gzip (inflated by Python's gzip module on the host: slow, for correctness only)."""
+    the device, bgzf.py), BAM (BGZF around binary records: located and parsed on the device, bam.hip) or plain gzip
+    (inflated by Python's gzip module on the host: slow, for correctness only)."""
     from . import bgzf
     use_minq, thr, restricted = check_args(minq, restricted)
     if int(block_bytes) < 1:
         raise ValueError("'block_bytes' must be a positive integer")
-    if bgzf.sniff(sam) == bgzf.BGZF:
+    if is_bam(sam):
+        names, lengths, parts = _bam_parts(sam, block_bytes, restricted, use_minq, thr)
+    elif bgzf.sniff(sam) == bgzf.BGZF:
         names, lengths, parts = _bgzf_parts(sam, block_bytes, restricted, use_minq, thr)
     else:
         with bgzf.open_text(sam) as fh:
