@@ -400,7 +400,31 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
  * thread-local state of sarlacc_dev_sam_extract: start is pos + 1, the names are the read names without their NUL.
  * sarlacc_bam_tile_bytes is the tile of the locator (tests place records around its multiples).  The locator takes
  * 4 bytes of workspace per byte of d_bam.
- * Out of scope: BAM output, .bai / .csi random access, CRAM, SEQ / QUAL of the records. */
+ * BAM -> resident read batch: SEQ and QUAL of the records, unpacked on the device into the flat layout of
+ * sarlacc_dev_fastq_extract.  d_bam, nbytes, first_record, at_eof, *n_records and *used_bytes are those of
+ * sarlacc_dev_bam_index, and the records are located the same way.  A record becomes a read unless
+ * flag & exclude_flags (0x900 drops secondary and supplementary records, whose reads would appear several times, partly
+ * hard-clipped; unmapped records, flag 0x4, are reads); reads keep file order and *n_reads is their number.  SEQ is
+ * decoded through "=ACMGRSVTWYHKDBN", high nibble first; QUAL values q in 0..93 become q + 33 (Phred+33).  With
+ * flag & 0x10 the stored SEQ is the reverse complement of what was sequenced and the read is restored: bases reversed,
+ * each code complemented (its four bits in reverse order: A 1 <-> T 8, C 2 <-> G 4, M 3 <-> K 12, ..., N 15 <-> N), QUAL
+ * reversed.  A first QUAL byte of 0xff says the record holds no qualities (section 4.2.3): every quality of the read is
+ * then missing_qual + 33, missing_qual in 0..93.  The name is the read name without its NUL (no /1 or /2 is added),
+ * l_seq 0 is a read of length 0, tags are ignored.  Errors are "BAM record K: <reason>" for the lowest failing record,
+ * within a record in this order: the locator's two messages and, on every record, "record fields do not fit its block
+ * size" as above; on records that become reads "SEQ holds '='" (a code 0) and "quality value above 93" (0xff anywhere
+ * but first included).  All of them are reported by sarlacc_dev_bam_reads_index, which keeps its state thread-local
+ * like the pairs above (a later locator run on the thread, sarlacc_dev_bam_index included, ends it).
+ * sarlacc_dev_bam_reads_range reports what the reads first .. first + count of the buffer indexed last need: their
+ * bases, their name bytes, and in *next_byte the offset of the record behind the last of them (used_bytes for
+ * first + count == n_reads, which takes the dropped records at the end along; 0 for first + count == 0): where the carry of
+ * a chunk that continues in the next buffer starts.  sarlacc_dev_bam_reads_records reports how many records lie in
+ * front of that offset for the reads 0 .. reads_taken: what the next buffer's first_record moves on by.
+ * sarlacc_dev_bam_reads_extract fills exactly that range: total_bases bytes of d_seq and of d_qual, count + 1 offsets
+ * in d_off that start at 0, the names and count + 1 offsets in d_names / d_name_off (both NULL: no names).  Every
+ * output may have any alignment; nothing outside those ranges is written.  count == 0 and nbytes == 0 succeed without a
+ * launch.  The three calls return when the device has finished.
+ * Out of scope: tags, BAM output, .bai / .csi random access, CRAM. */
 int sarlacc_bgzf_scan(const uint8_t* buf, int64_t nbytes, int64_t max_blocks, int64_t first_block, int64_t* comp_off,
                       int64_t* text_off, int64_t* n_blocks, int64_t* used_bytes, int* last_is_eof);
 int sarlacc_dev_bgzf_inflate(const uint8_t* d_comp, const int64_t* d_comp_off, const int64_t* d_text_off, int64_t n_blocks,
@@ -414,6 +438,13 @@ int sarlacc_dev_bam_extract(const uint8_t* d_bam, int32_t* d_ref, int32_t* d_sta
                             uint8_t* d_strand, int32_t* d_lclip, int32_t* d_rclip, uint8_t* d_names,
                             int64_t* d_name_off, void* stream);
 int sarlacc_bam_tile_bytes(void);
+int sarlacc_dev_bam_reads_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_record, int at_eof, int exclude_flags,
+                                int64_t* n_records, int64_t* used_bytes, int64_t* n_reads, void* stream);
+int sarlacc_dev_bam_reads_range(int64_t first, int64_t count, int64_t* total_bases, int64_t* total_name_bytes,
+                                int64_t* next_byte);
+int sarlacc_dev_bam_reads_records(int64_t reads_taken, int64_t* n_records);
+int sarlacc_dev_bam_reads_extract(const uint8_t* d_bam, int64_t first, int64_t count, int missing_qual, uint8_t* d_seq,
+                                  uint8_t* d_qual, int64_t* d_off, uint8_t* d_names, int64_t* d_name_off, void* stream);
 
 /* ------------------------------------------------------------------ */
 /* masked Levenshtein, neighbour search, clustering                      */

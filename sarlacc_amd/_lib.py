@@ -153,6 +153,10 @@ def _prototypes():
         "sarlacc_dev_bam_index": (i, [p, i64, i64, i, i64, p, i, i64, p, p, p, p, p]),
         "sarlacc_dev_bam_extract": (i, [p, p, p, p, p, p, p, p, p, p]),
         "sarlacc_bam_tile_bytes": (i, []),
+        "sarlacc_dev_bam_reads_index": (i, [p, i64, i64, i, i, p, p, p, p]),
+        "sarlacc_dev_bam_reads_range": (i, [i64, i64, p, p, p]),
+        "sarlacc_dev_bam_reads_records": (i, [i64, p]),
+        "sarlacc_dev_bam_reads_extract": (i, [p, i64, i64, i, p, p, p, p, p, p]),
         "sarlacc_bgzf_scan": (i, [p, i64, i64, i64, p, p, p, p, p]),
         "sarlacc_dev_bgzf_inflate": (i, [p, p, p, i64, i64, p, i, p]),
         "sarlacc_dev_copy": (i, [p, p, i64, p]),

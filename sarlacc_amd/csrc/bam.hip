@@ -24,6 +24,9 @@
 //                  for the CG:B,I array.  It fills SamRec / keep / name_len as k_sam_fields does, and the scans, the
 //                  scatter and the extract step of sam.hip are reused unchanged.
 //
+// The locator's launch sequence is bam_locate, and the layout check bam_layout_ok (bam_rec.hpp): bam_reads.hip, which
+// turns the same records into reads, calls both.
+//
 // No kernel waits on a value another workgroup writes: the launches are the synchronisation.  Every loop is bounded by
 // BAM_TILE or nbytes, no byte at or beyond nbytes is read, and a bad file is an error return (the first_bad pattern of
 // k_sam_fields: atomicMin on (record << 4 | code)), never a fault.
@@ -39,6 +42,7 @@
 //   cigar_range  CIGAR length above 2^31 - 1
 //   cigar_clips  CIGAR has only H and S operations
 //   end          alignment end outside the 32-bit integer range
+#include "bam_rec.hpp"
 #include "common.hpp"
 #include "devprim.hpp"
 #include "sam_rec.hpp"
@@ -62,10 +66,7 @@ enum {
     BAM_CIGAR_CLIPS = 8,
     BAM_END = 9,
 };
-// how the chain of records ends in a buffer
-enum { BAM_CHAIN_CLEAN = 0, BAM_CHAIN_INCOMPLETE = 1, BAM_CHAIN_SIZE = 2 };
 
-constexpr int BAM_TILE = 16384;                  // 64 KB of LDS: two workgroups per CU
 constexpr int BAM_HOP_THREADS = 1024;
 constexpr int BAM_MIN_RECORD = 36;               // block_size + the 32 fixed bytes
 constexpr int BAM_MAX_STARTS = (BAM_TILE + BAM_MIN_RECORD - 1) / BAM_MIN_RECORD;   // 456 starts of one chain in a tile
@@ -74,13 +75,6 @@ constexpr unsigned HOP_INVALID = 0xffffffffu;    // block_size below 32
 constexpr unsigned HOP_PARTIAL = 0xfffffffeu;    // size field not wholly inside the buffer
 static_assert((1 << (BAM_ROUNDS - 1)) >= BAM_MAX_STARTS, "pointer jumping needs more rounds for this tile");
 static_assert(BAM_TILE % (4 * BAM_HOP_THREADS) == 0, "the fill takes four entries per thread and step");
-
-__device__ __forceinline__ unsigned rd_u32(const uint8_t* p) {
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);      // records have no alignment
-    return v;
-}
-__device__ __forceinline__ unsigned rd_u16(const uint8_t* p) { return p[0] | (static_cast<unsigned>(p[1]) << 8); }
 
 __global__ void __launch_bounds__(BAM_HOP_THREADS) k_bam_hops(const uint8_t* bam, long long nbytes, unsigned* table) {
     __shared__ unsigned hop[BAM_TILE];
@@ -186,17 +180,16 @@ __global__ void __launch_bounds__(BAM_THREADS) k_bam_fields(const uint8_t* bam, 
     const long long nwaves = static_cast<long long>(gridDim.x) * (BAM_THREADS / 64);
     for (long long k = static_cast<long long>(blockIdx.x) * (BAM_THREADS / 64) + (threadIdx.x >> 6); k < nrec; k += nwaves) {
         const long long o = rec_off[k];
-        const long long bs = static_cast<int>(rd_u32(bam + o));     // >= 32 and wholly in the buffer: the locator checked
         const uint8_t* f = bam + o + 4;
+        BamFixed F;                                                  // block_size >= 32 and wholly in the buffer: the locator checked
+        const bool fits = bam_layout_ok(bam + o, &F);
+        const long long bs = F.bs, l_name = F.l_name, n_cig = F.n_cig, l_seq = F.l_seq;
+        const unsigned flag = F.flag;
         const int ref_id = static_cast<int>(rd_u32(f)), pos = static_cast<int>(rd_u32(f + 4));
-        const long long l_name = f[8];
         const int mapq = f[9];
-        const long long n_cig = rd_u16(f + 12);
-        const unsigned flag = rd_u16(f + 14);
-        const long long l_seq = static_cast<int>(rd_u32(f + 16));
         const long long fixed = 32 + l_name + 4 * n_cig;
         int kept = 0, bad = 0;
-        if (l_name == 0 || l_seq < 0 || fixed + (l_seq + 1) / 2 + l_seq > bs || f[32 + l_name - 1] != 0) {
+        if (!fits) {
             bad = BAM_LAYOUT;
         } else {
             const bool listed = ref_id >= -1 && ref_id < n_ref;
@@ -302,6 +295,62 @@ __global__ void __launch_bounds__(BAM_THREADS) k_bam_fields(const uint8_t* bam, 
     }
 }
 
+static thread_local unsigned long long g_bam_generation = 0;
+
+unsigned long long bam_locate_generation() { return g_bam_generation; }
+
+int bam_locate(const uint8_t* d_bam, long long nbytes, hipStream_t s, BamLocated* out) {
+    Context& c = ctx();
+    for (const char* name : {"bam_hops", "bam_chain", "bam_starts"}) c.stage_reset(name);
+    out->generation = ++g_bam_generation;
+    const long long ntiles = (nbytes + BAM_TILE - 1) / BAM_TILE;
+    if (ntiles > INT_MAX) return fail("sarlacc_amd: BAM buffer too large");
+    unsigned* d_table; long long* d_entry; long long* d_count; long long* d_base; long long* d_term;
+    SL_TRY(scratch("bam.hops", static_cast<size_t>(nbytes), &d_table));
+    SL_TRY(scratch("bam.entry", static_cast<size_t>(ntiles), &d_entry));
+    SL_TRY(scratch("bam.count", static_cast<size_t>(ntiles) + 1, &d_count));
+    SL_TRY(scratch("bam.base", static_cast<size_t>(ntiles) + 1, &d_base));
+    SL_TRY(scratch("bam.term", 2, &d_term));
+    SL_HIP(hipMemsetAsync(d_entry, 0xff, static_cast<size_t>(ntiles) * sizeof(long long), s));
+    SL_HIP(hipMemsetAsync(d_term, 0xff, 2 * sizeof(long long), s));
+    SL_HIP(hipMemsetAsync(d_count + ntiles, 0, sizeof(long long), s));
+    SL_TRY(c.stage_begin("bam_hops", s));
+    hipLaunchKernelGGL(k_bam_hops, dim3(static_cast<unsigned>(ntiles)), dim3(BAM_HOP_THREADS), 0, s, d_bam, nbytes, d_table);
+    SL_HIP(hipGetLastError());
+    SL_TRY(c.stage_end("bam_hops", s));
+    SL_TRY(c.stage_begin("bam_chain", s));
+    hipLaunchKernelGGL(k_bam_chain, dim3(1), dim3(64), 0, s, d_table, nbytes, ntiles, d_entry);
+    SL_HIP(hipGetLastError());
+    SL_TRY(c.stage_end("bam_chain", s));
+    SL_TRY(c.stage_begin("bam_starts", s));
+    hipLaunchKernelGGL(k_bam_starts<false>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, d_bam, nbytes, ntiles, d_entry, d_count, d_base,
+                       static_cast<long long*>(nullptr), d_term);
+    SL_HIP(hipGetLastError());
+    SL_TRY(exclusive_scan("bam.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
+    long long nrec = 0, term[2] = {-1, -1};
+    SL_HIP(hipMemcpyAsync(&nrec, d_base + ntiles, sizeof nrec, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipMemcpyAsync(term, d_term, sizeof term, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipStreamSynchronize(s));
+    if (term[0] < 0 || term[0] > nbytes || nrec < 0) return fail("sarlacc_amd: the BAM record chain did not end (internal error)");
+    SL_TRY(scratch("bam.off", static_cast<size_t>(nrec) + 1, &out->d_off));
+    if (nrec > 0) {
+        hipLaunchKernelGGL(k_bam_starts<true>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, d_bam, nbytes, ntiles, d_entry, d_count,
+                           d_base, out->d_off, d_term);
+        SL_HIP(hipGetLastError());
+    }
+    SL_TRY(c.stage_end("bam_starts", s));
+    out->nrec = nrec;
+    out->end = term[0];
+    out->how = static_cast<int>(term[1]);
+    return 0;
+}
+
+int bam_chain_end_error(const BamLocated& L, long long first_record, int at_eof) {
+    if (L.how == BAM_CHAIN_SIZE) return fail("BAM record %lld: block size below 32", first_record + L.nrec);
+    if (L.how == BAM_CHAIN_INCOMPLETE && at_eof) return fail("BAM record %lld: file ends inside the record", first_record + L.nrec);
+    return 0;
+}
+
 }  // namespace sarlacc
 
 using namespace sarlacc;
@@ -324,47 +373,11 @@ int sarlacc_dev_bam_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_re
         return 0;
     }
     Context& c = ctx();
-    for (const char* name : {"bam_hops", "bam_chain", "bam_starts", "bam_fields"}) c.stage_reset(name);
-
-    // the locator
-    const long long ntiles = (nbytes + BAM_TILE - 1) / BAM_TILE;
-    if (ntiles > INT_MAX) return fail("sarlacc_amd: BAM buffer too large");
-    unsigned* d_table; long long* d_entry; long long* d_count; long long* d_base; long long* d_term;
-    SL_TRY(scratch("bam.hops", static_cast<size_t>(nbytes), &d_table));
-    SL_TRY(scratch("bam.entry", static_cast<size_t>(ntiles), &d_entry));
-    SL_TRY(scratch("bam.count", static_cast<size_t>(ntiles) + 1, &d_count));
-    SL_TRY(scratch("bam.base", static_cast<size_t>(ntiles) + 1, &d_base));
-    SL_TRY(scratch("bam.term", 2, &d_term));
-    SL_HIP(hipMemsetAsync(d_entry, 0xff, static_cast<size_t>(ntiles) * sizeof(long long), s));
-    SL_HIP(hipMemsetAsync(d_term, 0xff, 2 * sizeof(long long), s));
-    SL_HIP(hipMemsetAsync(d_count + ntiles, 0, sizeof(long long), s));
-    SL_TRY(c.stage_begin("bam_hops", s));
-    hipLaunchKernelGGL(k_bam_hops, dim3(static_cast<unsigned>(ntiles)), dim3(BAM_HOP_THREADS), 0, s, d_bam,
-                       static_cast<long long>(nbytes), d_table);
-    SL_HIP(hipGetLastError());
-    SL_TRY(c.stage_end("bam_hops", s));
-    SL_TRY(c.stage_begin("bam_chain", s));
-    hipLaunchKernelGGL(k_bam_chain, dim3(1), dim3(64), 0, s, d_table, static_cast<long long>(nbytes), ntiles, d_entry);
-    SL_HIP(hipGetLastError());
-    SL_TRY(c.stage_end("bam_chain", s));
-    SL_TRY(c.stage_begin("bam_starts", s));
-    hipLaunchKernelGGL(k_bam_starts<false>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, d_bam, static_cast<long long>(nbytes), ntiles,
-                       d_entry, d_count, d_base, static_cast<long long*>(nullptr), d_term);
-    SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan("bam.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
-    long long nrec = 0, term[2] = {-1, -1};
-    SL_HIP(hipMemcpyAsync(&nrec, d_base + ntiles, sizeof nrec, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipMemcpyAsync(term, d_term, sizeof term, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipStreamSynchronize(s));
-    if (term[0] < 0 || term[0] > nbytes || nrec < 0) return fail("sarlacc_amd: the BAM record chain did not end (internal error)");
-    long long* d_off;
-    SL_TRY(scratch("bam.off", static_cast<size_t>(nrec) + 1, &d_off));
-    if (nrec > 0) {
-        hipLaunchKernelGGL(k_bam_starts<true>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, d_bam, static_cast<long long>(nbytes),
-                           ntiles, d_entry, d_count, d_base, d_off, d_term);
-        SL_HIP(hipGetLastError());
-    }
-    SL_TRY(c.stage_end("bam_starts", s));
+    c.stage_reset("bam_fields");
+    BamLocated L;
+    SL_TRY(bam_locate(d_bam, nbytes, s, &L));
+    const long long nrec = L.nrec;
+    long long* d_off = L.d_off;
 
     // the records: fields, keep flags, scans (the back end of sam.hip)
     unsigned long long bad = ~0ull;
@@ -409,11 +422,9 @@ int sarlacc_dev_bam_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_re
             default: return fail("BAM record %lld: alignment end outside the 32-bit integer range", k);
         }
     }
-    if (term[1] == BAM_CHAIN_SIZE) return fail("BAM record %lld: block size below 32", static_cast<long long>(first_record) + nrec);
-    if (term[1] == BAM_CHAIN_INCOMPLETE && at_eof)
-        return fail("BAM record %lld: file ends inside the record", static_cast<long long>(first_record) + nrec);
+    SL_TRY(bam_chain_end_error(L, first_record, at_eof));
     g_sam.text = d_bam; g_sam.nlines = nrec; g_sam.nkept = nk; g_sam.name_bytes = nb;
-    *n_records = nrec; *used_bytes = term[0];
+    *n_records = nrec; *used_bytes = L.end;
     *n_kept = nk; *kept_name_bytes = nb;
     return 0;
 }

@@ -1,0 +1,58 @@
+// bam_rec.hpp -- what the two BAM paths share (bam.hip: records -> ranges, bam_reads.hip: records -> reads): the
+// unaligned field readers, the layout predicate every record has to pass, and the locator (implemented in bam.hip).
+#pragma once
+
+#include "common.hpp"
+
+namespace sarlacc {
+
+constexpr int BAM_TILE = 16384;                  // 64 KB of LDS: two workgroups per CU
+
+__device__ __forceinline__ unsigned rd_u32(const uint8_t* p) {
+    unsigned v;
+    __builtin_memcpy(&v, p, 4);      // records have no alignment
+    return v;
+}
+__device__ __forceinline__ unsigned rd_u16(const uint8_t* p) { return p[0] | (static_cast<unsigned>(p[1]) << 8); }
+
+// The fixed fields both paths read of the record whose block_size field lies at `rec`.
+struct BamFixed {
+    long long bs, l_name, n_cig, l_seq;
+    unsigned flag;
+};
+
+// Whether the fields of a located record (block_size >= 32, wholly in the buffer) fit its block size: a name with its
+// NUL, l_seq >= 0, and name + CIGAR + SEQ + QUAL inside block_size.  "record fields do not fit its block size" otherwise.
+__device__ __forceinline__ bool bam_layout_ok(const uint8_t* rec, BamFixed* F) {
+    const uint8_t* f = rec + 4;
+    F->bs = static_cast<int>(rd_u32(rec));
+    F->l_name = f[8];
+    F->n_cig = rd_u16(f + 12);
+    F->flag = rd_u16(f + 14);
+    F->l_seq = static_cast<int>(rd_u32(f + 16));
+    const long long fixed = 32 + F->l_name + 4 * F->n_cig;
+    return !(F->l_name == 0 || F->l_seq < 0 || fixed + (F->l_seq + 1) / 2 + F->l_seq > F->bs || f[32 + F->l_name - 1] != 0);
+}
+
+// how the chain of records ends in a buffer
+enum { BAM_CHAIN_CLEAN = 0, BAM_CHAIN_INCOMPLETE = 1, BAM_CHAIN_SIZE = 2 };
+
+// What the locator found in a buffer: the offsets of the nrec records that lie wholly in it (d_off, nrec + 1 entries of
+// the workspace "bam.off", the last one unset), the offset of the first record that does not (nbytes when none is cut)
+// and how the chain ends there.  `generation` counts the locator runs of this thread: d_off belongs to the last one.
+struct BamLocated {
+    long long nrec = 0, end = 0;
+    int how = BAM_CHAIN_CLEAN;
+    long long* d_off = nullptr;
+    unsigned long long generation = 0;
+};
+
+// k_bam_hops / k_bam_chain / k_bam_starts over nbytes > 0 of inflated BAM whose byte 0 starts a record, under the stage
+// timers bam_hops, bam_chain and bam_starts.  The counts are back on the host when it returns; the launch that writes
+// d_off is still on the stream.
+int bam_locate(const uint8_t* d_bam, long long nbytes, hipStream_t s, BamLocated* out);
+unsigned long long bam_locate_generation();
+// The locator's two refusals, for a caller that found no bad record in front of the chain's end (0: none applies).
+int bam_chain_end_error(const BamLocated& L, long long first_record, int at_eof);
+
+}  // namespace sarlacc

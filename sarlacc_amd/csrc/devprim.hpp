@@ -13,6 +13,15 @@ namespace sarlacc {
 // blocks of `bs` threads that cover n items
 inline unsigned nblk(long long n, int bs) { return static_cast<unsigned>((n + bs - 1) / bs); }
 
+// largest r in [lo, hi) with a[r] <= g, given a[lo] <= g: the string of a flat layout that holds byte g
+__device__ __forceinline__ long long last_not_above(const int64_t* a, long long lo, long long hi, long long g) {
+    while (hi - lo > 1) {
+        const long long mid = (lo + hi) >> 1;
+        if (a[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // bits a radix sort needs for keys below x (at least 1)
 inline int ceil_log2(unsigned long long x) {
     int b = 1;

@@ -50,15 +50,6 @@ __device__ __forceinline__ uint32_t line_break4(uint32_t w) {
     return (((a - 0x01010101u) & ~a) | ((b - 0x01010101u) & ~b)) & 0x80808080u;
 }
 
-// largest r in [lo, hi) with a[r] <= g, given a[lo] <= g
-__device__ __forceinline__ long long last_not_above(const int64_t* a, long long lo, long long hi, long long g) {
-    while (hi - lo > 1) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // len[r] = bytes of record r (len[n] = 0 for the scan); first_bad: lowest record whose name holds a line break
 __global__ void __launch_bounds__(256) k_fqw_size(const int64_t* off, const uint8_t* names, const int64_t* name_off,
                                                   long long first_index, long long n, long long* len,

@@ -67,6 +67,22 @@ def read_fastq(path):
     return Reads(seqs, quals, names)
 
 
+def read_bam(path, exclude_flags=0x900, missing_qual=1):
+    """The reads of a BAM file -> Reads: resident.DeviceReads.from_bam (unpacked on the device), downloaded, with their
+    names.  The qualities are Phred+33."""
+    from .resident import DeviceReads
+    dev = DeviceReads.from_bam(path, exclude_flags=exclude_flags, missing_qual=missing_qual)
+    seq, qual = dev.download()
+    return Reads(seq, qual, dev.names, dev.encoding)
+
+
+def _check_bam_qual_type(path, qual_type):
+    """A BAM file stores Phred values: no other quality class can be asked of it."""
+    from . import sam
+    if qual_type != "phred" and sam.is_bam(path):
+        raise ValueError("'qual_type' is '%s', but a BAM file holds Phred qualities" % qual_type)
+
+
 def write_fastq(path, reads, append=False):
     """Reads -> 4-line FASTQ (LF only; READ_<i> where there are no names).  A resident batch (resident.DeviceReads, e.g.
     realizeReads(..., resident=True)) is formatted on the device and written block by block (DeviceReads.to_fastq,
@@ -234,7 +250,9 @@ def adaptorAlign(adaptor1, adaptor2, reads, tolerance=250, gapOpening=5, gapExte
     the resident windows (no host pass over the bases); `qual_type` ("phred", "solexa" or "illumina",
     match.arg semantics) names the quality class the file is read with (.qual2class, :97-99) and hence
     the encoding vector of every alignment.  A Reads object is accepted as well (one chunk; it carries
-    its own encoding, so `qual_type` only lands in the metadata).  The file may be plain text, BGZF or plain gzip, as the
+    its own encoding, so `qual_type` only lands in the metadata).  A BAM file (a basecaller's unaligned BAM, or an aligned
+    one) is accepted in the FASTQ file's place: its records are unpacked on the device (DeviceReads.stream_bam) and
+    `qual_type` must be "phred".  The FASTQ file may be plain text, BGZF or plain gzip, as the
     reference's FastqStreamer reads `.fastq.gz`: BGZF blocks are inflated on the device, plain gzip by zlib on the host
     (bgzf.py); `metadata["filepath"]` keeps the path as given, and realizeReads reads the same file again."""
     adaptor1, adaptor2 = str(adaptor1).upper(), str(adaptor2).upper()
@@ -246,7 +264,8 @@ def adaptorAlign(adaptor1, adaptor2, reads, tolerance=250, gapOpening=5, gapExte
     if isinstance(reads, (str, os.PathLike)):
         from .resident import DeviceReads
         filepath = os.fspath(reads)
-        for dev in DeviceReads.stream_fastq(filepath, number, encoding=enc):
+        _check_bam_qual_type(filepath, qual_type)
+        for dev in DeviceReads.stream_reads(filepath, number, encoding=enc):
             parts.append(_adaptor_align_chunk(adaptor1, adaptor2, sub1, sub2, args, tolerance, dev=dev))
             names.append(dev.names)
         if not parts:   # "Guarantee some value is returned" (:42-50): the empty table, with its columns
@@ -310,7 +329,7 @@ def filterReads(aligned, score1, score2, essential1=True, essential2=True):
 
 
 def realizeReads(aligned, number=1e5, trim=True, resident=False):
-    """realizeReads (R/realizeReads.R:5-46): the reads named in `aligned`, re-read from its FASTQ file
+    """realizeReads (R/realizeReads.R:5-46): the reads named in `aligned`, re-read from its FASTQ (or BAM) file
     (streamed in chunks of `number` records with the quality class recorded by adaptorAlign, :11-25),
     reverse-complemented where `reversed` and trimmed to [trim.start, trim.end].  Every chunk is parsed
     on the device and the orientation / trimming happen there (DeviceReads.realize); the result comes
@@ -330,7 +349,8 @@ def realizeReads(aligned, number=1e5, trim=True, resident=False):
         else:
             warnings.warn("no 'trim.start' detected, run 'filterReads' first")
     parts, part_rows, seen = [], [], set()
-    for dev in DeviceReads.stream_fastq(aligned["metadata"]["filepath"], number, encoding=enc):
+    _check_bam_qual_type(aligned["metadata"]["filepath"], qual_type)
+    for dev in DeviceReads.stream_reads(aligned["metadata"]["filepath"], number, encoding=enc):
         idx, rows = [], []
         for i, nm in enumerate(dev.names):
             if nm in rows_of and nm not in seen:   # match(): first occurrence in the file

@@ -175,6 +175,93 @@ class DeviceReads:
                     yield chunk
             carry = (d_text, pos, nbytes - pos) if pos < nbytes else None
 
+    @classmethod
+    def stream_reads(cls, path, number, encoding=None, block_bytes=256 << 20):
+        """stream_bam for a BAM file (sam.is_bam), stream_fastq for anything else: the read source of adaptorAlign and
+        realizeReads.  A BAM file stores Phred values, so `encoding` plays no part there."""
+        from . import sam
+        if sam.is_bam(path):
+            return cls.stream_bam(path, number, block_bytes=block_bytes)
+        return cls.stream_fastq(path, number, encoding=encoding, block_bytes=block_bytes)
+
+    @classmethod
+    def from_bam(cls, path, exclude_flags=0x900, missing_qual=1):
+        """The reads of a BAM file (aligned or not: a basecaller's unaligned BAM holds unmapped records only) as one
+        resident batch, unpacked on the device (sarlacc_dev_bam_reads_index / _range / _extract, bam_reads.hip).  A record
+        becomes a read unless `flag & exclude_flags` (the default drops secondary and supplementary records); a record
+        stored reverse-complemented (flag 0x10) is turned back to the read as sequenced; a record without qualities gets
+        `missing_qual` (0..93) at every base.  The encoding is Phred+33; `.names` is a StrList, as from_fastq leaves it."""
+        chunks = list(cls.stream_bam(path, None, exclude_flags, missing_qual, block_bytes=None))
+        return chunks[0] if chunks else cls._bam_range(DevBuffer(1), 0, 0, missing_qual)
+
+    @classmethod
+    def stream_bam(cls, path, number, exclude_flags=0x900, missing_qual=1, block_bytes=256 << 20):
+        """Generator over the reads of a BAM file (see from_bam) in chunks of `number` reads, each a resident batch: every
+        chunk but the last holds exactly `number`, wherever the buffers end.  The header is read on the host
+        (sam.read_bam_header); the records are inflated on the device, whole BGZF blocks worth `block_bytes` at a time
+        (bgzf.DeviceTextStream).  A chunk that continues past the buffer carries the bytes from its first unused record
+        on, on the device, into the next buffer; a buffer in which no record is complete grows."""
+        from . import bgzf, sam
+        if number is not None:      # (None: the whole file, from_bam)
+            number = int(number)
+            if number < 1:
+                raise ValueError("'number' must be a positive integer")
+        if isinstance(missing_qual, bool) or int(missing_qual) != missing_qual or not 0 <= missing_qual <= 93:
+            raise ValueError("'missing_qual' must be an integer in 0..93")
+        if isinstance(exclude_flags, bool) or int(exclude_flags) != exclude_flags or not 0 <= exclude_flags <= 0xffff:
+            raise ValueError("'exclude_flags' must be an integer in 0..65535")
+        if block_bytes is not None and int(block_bytes) < 1:
+            raise ValueError("'block_bytes' must be a positive integer")
+        lib = _lib.lib()
+        with open(path, "rb") as fh:
+            origin = sam.read_bam_header(fh)[2]
+            fh.seek(origin[0])
+            stream = bgzf.DeviceTextStream(fh, block_bytes, first_block=origin[1], skip=origin[2])
+            record, carry, eof = 1, None, False
+            while not eof:
+                d_bam, nbytes, eof = stream.next(carry)
+                if d_bam is None or nbytes == 0:
+                    break
+                nrec, used, nreads = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+                check(lib.sarlacc_dev_bam_reads_index(d_bam, nbytes, record, 1 if eof else 0, int(exclude_flags), C.byref(nrec),
+                                                      C.byref(used), C.byref(nreads), None))
+                pos, start = 0, 0
+                while pos < nreads.value and (eof or number is None or nreads.value - pos >= number):
+                    count = nreads.value - pos if number is None else min(number, nreads.value - pos)
+                    chunk, start = cls._bam_range(d_bam, pos, count, int(missing_qual), with_next=True)
+                    pos += count
+                    yield chunk
+                if pos == nreads.value:     # the dropped records at the end go too
+                    start, taken = used.value, nrec.value
+                else:                       # the chunk continues in the next buffer, from its first unused record on
+                    done = C.c_int64(0)
+                    check(lib.sarlacc_dev_bam_reads_records(pos, C.byref(done)))
+                    taken = done.value
+                record += taken
+                carry = (d_bam, start, nbytes - start) if start < nbytes else None
+
+    @classmethod
+    def _bam_range(cls, d_bam, first, count, missing_qual, with_next=False):
+        """The reads first .. first + count of the BAM buffer indexed last (sarlacc_dev_bam_reads_range / _extract) as a
+        resident batch, and with `with_next` the offset of the record behind them."""
+        lib = _lib.lib()
+        tb, tn, nxt = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        if count:
+            check(lib.sarlacc_dev_bam_reads_range(first, count, C.byref(tb), C.byref(tn), C.byref(nxt)))
+        seq, qual = DevBuffer(max(tb.value, 1)), DevBuffer(max(tb.value, 1))
+        off, names, noff = DevBuffer(8 * (count + 1)), DevBuffer(max(tn.value, 1)), DevBuffer(8 * (count + 1))
+        if count:
+            check(lib.sarlacc_dev_bam_reads_extract(d_bam, first, count, missing_qual, seq, qual, off, names, noff, None))
+            off_host, noff_host = off.to_numpy(np.int64, count + 1), noff.to_numpy(np.int64, count + 1)
+        else:
+            off_host, noff_host = np.zeros(1, np.int64), np.zeros(1, np.int64)
+            check(lib.sarlacc_dev_upload(off, off_host, 8))
+        out = cls(seq, qual, off, off_host, phred_encoding())
+        from .strset import StrList
+        nraw = names.to_numpy(np.uint8, tn.value)
+        out.names = StrList(StringSet(nraw if nraw.size else np.zeros(1, np.uint8), noff_host))   # decoded on demand
+        return (out, nxt.value) if with_next else out
+
     def __len__(self):
         return len(self.off_host) - 1
 
