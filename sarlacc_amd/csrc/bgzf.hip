@@ -110,8 +110,10 @@ __device__ __forceinline__ uint32_t peek(const Shared& sh, int wp) {
 }
 
 // Counts, Kraft check, sorted symbols of `n` code lengths (lane 0).  An over-subscribed code is refused, and an
-// incomplete one unless it has a single symbol (or, for distances, none).  Returns 0 or BZ_LENGTHS; count[0] is
-// left holding the number of symbols that have a code.
+// incomplete one as zlib refuses it: a literal/length or distance code may be a single code of 1 bit, a distance
+// code may be absent (a block of literals only), and the code-length code (NSYM == 19) is never incomplete -- after
+// a lone code-length code all lengths would be equal, and 257 to 286 equal lengths are no complete code.  Returns 0
+// or BZ_LENGTHS; count[0] is left holding the number of symbols that have a code.
 template <int NSYM, int BITS>
 __device__ int huff_prepare(Huff<NSYM, BITS>& h, const uint8_t* lens, int n) {
     for (int l = 0; l < 16; ++l) h.count[l] = 0;
@@ -122,7 +124,10 @@ __device__ int huff_prepare(Huff<NSYM, BITS>& h, const uint8_t* lens, int n) {
         if (left < 0) return BZ_LENGTHS;             // over-subscribed
         used += h.count[l];
     }
-    if (left > 0 && used != 1 && !(used == 0 && NSYM == 32)) return BZ_LENGTHS;   // incomplete (a block of literals only may have no distance code)
+    if (left > 0) {                                  // incomplete
+        const bool lone = used == 1 && h.count[1] == 1, absent = used == 0 && NSYM == 32;
+        if (NSYM == 19 || !(lone || absent)) return BZ_LENGTHS;
+    }
     int idx = 0, code = 0;
     for (int l = 1; l < 16; ++l) {
         h.first[l] = static_cast<uint16_t>(idx);

@@ -1,5 +1,6 @@
 """BGZF input on the device (bgzf.hip, sarlacc_amd/bgzf.py): the inflate kernel against Python's zlib on every block
-type and copy shape, its refusals of malformed input, and the compressed routes of from_fastq / stream_fastq /
+type and copy shape and on hand-built streams at deflate's limits (tests/bgzf_cases.py; tests/test_bgzf_streams.py shows
+on the CPU that they contain what they claim), its refusals of malformed input, and the compressed routes of from_fastq / stream_fastq /
 adaptorAlign / realizeReads / sam2ranges against the same calls on the text.  Byte work: everything must be
 identical."""
 import gzip
@@ -155,6 +156,90 @@ def test_truncated_dynamic_block_and_bad_frame():
     _refused(B.wrap(B.BitWriter().value(1, 1).value(1, 2).code(0xc6, 8).value(0, 16).bytes(), 0, 4), "invalid symbol")
 
 
+# ---- hand-built streams ---------------------------------------------------------------------------------------------
+def inflate_at(data, comp_off, text_off, first_block=0, check_crc=1):
+    """One call on the blocks that the two offset lists name, `data` and the text buffer being those of the whole file;
+    returns the failure's message (None: success) and the whole buffer with its 64 guard bytes on either side."""
+    from sarlacc_amd import _lib
+    from sarlacc_amd._lib import SarlaccError
+    from sarlacc_amd.resident import DevBuffer
+    comp_off, text_off = np.asarray(comp_off, np.int64), np.asarray(text_off, np.int64)
+    host = np.full(int(text_off[-1]) + 2 * GUARD, 0xA5, np.uint8)
+    d_text = DevBuffer.from_numpy(host)
+    d_comp, d_co, d_to = DevBuffer.from_numpy(np.frombuffer(data, np.uint8)), DevBuffer.from_numpy(comp_off), DevBuffer.from_numpy(text_off)
+    rc = _lib.lib().sarlacc_dev_bgzf_inflate(d_comp, d_co, d_to, len(comp_off) - 1, first_block, d_text.ptr.value + GUARD, check_crc, None)
+    got = d_text.to_numpy(np.uint8, host.size)
+    try:
+        _lib.check(rc)
+    except SarlaccError as e:
+        return str(e), got
+    return None, got
+
+
+def _block_by_block(items, check_crc):
+    """items: (name, text, block).  One call on all of them, every block's text compared on its own."""
+    data = B.bgzf_file(*[block for _, _, block in items])
+    got = inflate(data, check_crc=check_crc)
+    starts = np.cumsum([0] + [len(text) for _, text, _ in items])
+    for (name, text, _), a, b in zip(items, starts, starts[1:]):
+        assert got[a:b] == text, name
+    assert len(got) == starts[-1]
+    return starts
+
+
+def test_named_streams_in_one_call():
+    items = [(name, text, block) for _, name, _, text, block in B.named_streams()]
+    starts = _block_by_block(items, 1)
+    assert len(set(int(s) % 16 for s in starts)) >= 8, "the outputs should start at many alignments"
+    _block_by_block(items, 0)
+
+
+def test_named_streams_one_call_each():
+    for _, name, _, text, block in B.named_streams():
+        assert inflate(block) == text, name
+
+
+def test_generated_streams():
+    items = [("generated %d" % k, text, block) for k, (_, text, block) in enumerate(B.generated_streams())]
+    _block_by_block(items, 1)
+    # from block 100 on: the offsets are those of the whole file, so they do not start at zero
+    comp_off = np.asarray(B.block_offsets([block for _, _, block in items]), np.int64)
+    text_off = np.asarray(B.block_offsets([text for _, text, _ in items]), np.int64)
+    message, got = inflate_at(b"".join(block for _, _, block in items), comp_off[100:], text_off[100:], first_block=100)
+    assert message is None
+    assert (got[:GUARD + text_off[100]] == 0xA5).all() and (got[GUARD + text_off[-1]:] == 0xA5).all()
+    for (name, text, _), a, b in zip(items[100:], text_off[100:], text_off[101:]):
+        assert got[GUARD + a:GUARD + b].tobytes() == text, name
+
+
+@pytest.mark.parametrize("name", sorted(B.refusals()))
+def test_refusals_held_against_zlib(name):
+    reason = B.refusals()[name][2]
+    _refused(B.refusal_block(name), reason)
+    _refused(B.refusal_block(name), reason, check_crc=0)
+
+
+def test_blocks_do_not_see_each_others_text():
+    # the first block ends in a run of A; a match at distance 1 that opens the second block must not reach it
+    data = B.bgzf_block(b"A" * 100, 0) + B.refusal_block("a match opens the block")
+    for check_crc in (1, 0):
+        _refused(data, "distance beyond the start of the block", block=2, check_crc=check_crc)
+
+
+@pytest.mark.parametrize("name", B.OVERFLOWS)
+def test_overflow_writes_nothing_outside_the_refused_block(name):
+    rng = np.random.default_rng(5)
+    one, three = rng.integers(0, 256, 333, dtype=np.uint8).tobytes(), rng.integers(0, 256, 77, dtype=np.uint8).tobytes()
+    blocks = [B.bgzf_block(one), B.refusal_block(name), B.bgzf_block(three)]
+    size = B.refusals()[name][1]
+    text_off = [0, len(one), len(one) + size, len(one) + size + len(three)]
+    for check_crc in (1, 0):
+        message, got = inflate_at(b"".join(blocks), B.block_offsets(blocks), text_off, check_crc=check_crc)
+        assert message == "BGZF block 2: output exceeds the size field"
+        assert (got[:GUARD] == 0xA5).all() and (got[GUARD + text_off[-1]:] == 0xA5).all(), "guard bytes were written"
+        assert got[GUARD:GUARD + len(one)].tobytes() == one and got[GUARD + text_off[2]:GUARD + text_off[3]].tobytes() == three
+
+
 # ---- FASTQ ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def fastq(tmp_path_factory):
@@ -182,6 +267,20 @@ def test_from_fastq_of_a_compressed_file(fastq, kind):
     want = DeviceReads.from_fastq(fastq["text"])
     assert len(want) == 300
     _same_batch(DeviceReads.from_fastq(fastq[kind]), want)
+
+
+def test_from_fastq_of_hand_built_blocks(fastq, tmp_path):
+    """Every sequence line under the ladder codes (1 ... 14, 15, 15 bits on both alphabets), the other lines as stored and
+    fixed blocks: some 80 deflate blocks to a BGZF block."""
+    from sarlacc_amd.resident import DeviceReads
+    with open(fastq["text"], "rb") as fh:
+        text = fh.read()
+    data = B.handbuilt_fastq(text, records=20)
+    assert gzip.decompress(data) == text
+    (tmp_path / "hand.fastq.gz").write_bytes(data)
+    want = DeviceReads.from_fastq(fastq["text"])
+    assert len(want) == 300
+    _same_batch(DeviceReads.from_fastq(str(tmp_path / "hand.fastq.gz")), want)
 
 
 @pytest.mark.parametrize("kind", ["bgzf", "gzip", "no eof"])
