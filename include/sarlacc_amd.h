@@ -325,7 +325,8 @@ int sarlacc_dev_fastq_extract(const uint8_t* d_text, uint8_t* d_seq, uint8_t* d_
  * bytes d_rec_off[first] .. d_rec_off[first + count] of the whole text to d_text[0 ..], so a caller that plans ranges
  * of whole records needs room for one range at a time.  d_text may have any alignment.  n == 0 and count == 0 succeed
  * without a launch.  Both calls return when the device has finished.
- * Out of scope: gzip output, multi-line FASTQ, a repeated name on the '+' line. */
+ * Compressed output is sarlacc_dev_bgzf_deflate on the formatted text (below).
+ * Out of scope: multi-line FASTQ, a repeated name on the '+' line. */
 int sarlacc_dev_fastq_format_size(const int64_t* d_off, int64_t n, const uint8_t* d_names, const int64_t* d_name_off,
                                   int64_t first_index, int64_t* d_rec_off, int64_t* total_bytes, void* stream);
 int sarlacc_dev_fastq_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
@@ -374,8 +375,25 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
  * sarlacc_dev_copy copies bytes within device memory (ranges that do not overlap, any alignment): the tail of one
  * text buffer to the front of the next.  sarlacc_dev_rfind_byte reports the position of the last byte of d_text equal
  * to value (-1: none): where a block of lines ends.  Both return when the device has finished.
- * Out of scope: compressed output, random access via .gzi, device inflate of gzip that is not BGZF (the Python
- * layer inflates that on the host).
+ * Out of scope: random access via .gzi, device inflate of gzip that is not BGZF (the Python layer inflates that on
+ * the host).
+ * BGZF output: text in device memory is deflated on the device, so that only compressed bytes cross the bus.
+ * sarlacc_bgzf_deflate_bound needs no device: *n_blocks = ceil(nbytes / 65280) (block k holds the text bytes
+ * k * 65280 .. min((k + 1) * 65280, nbytes): 0xff00 as htslib cuts) and *comp_capacity = 65536 * n_blocks, what d_comp
+ * must hold; either pointer may be NULL.  sarlacc_dev_bgzf_deflate writes those n_blocks blocks, complete gzip members
+ * with the BC subfield, CRC-32 and ISIZE, side by side into d_comp (no end-of-file block: the caller appends the 28
+ * bytes once per file); d_comp_off (n_blocks + 1 entries, may be NULL) gets their offsets and *comp_bytes their total.
+ * d_text and d_comp may have any alignment.  The encoder is Huffman-only (literals and end-of-block; every table
+ * declares one distance code of length 0).  Per block it takes the smallest, by exact bit count and ties in this
+ * order, of (a) one dynamic-Huffman deflate block, (b) one dynamic-Huffman deflate block per piece -- a piece ends
+ * behind a '\n' that lies at least 64 bytes into it, or at the block's end, so a short line goes with the next one --
+ * and (c) one stored deflate block, hence never more than 31 bytes above the text.  mode 0 considers all three, mode 1
+ * (a) and (c), mode 2 (c) alone.  The same text and mode give the same bytes.  nbytes == 0 succeeds without a launch
+ * (0 blocks, 0 bytes).  Errors: a negative size, "unknown BGZF deflate mode M", "BGZF output capacity C is below the
+ * bound B".  The call returns when the device has finished; sarlacc_last_kernel_ms is the encode kernel.  Workspace:
+ * one 65536-byte slot per block, 1.004 * nbytes rounded up to whole slots, and 16 bytes per block of sizes.
+ * Out of scope: LZ77 matching (about 4 % on long reads against 17 % for the per-line tables), BAM output, .gzi / .csi
+ * indexes, compressing on the host.
  * BAM (SAM specification section 4.2: the same container around binary records) -> ranges.  d_bam holds nbytes of
  * inflated BAM in device memory whose byte 0 is the start of an alignment record: the caller reads the header
  * (magic, text, reference list) and starts every later buffer at the carried tail.  A record is block_size (int32)
@@ -429,6 +447,9 @@ int sarlacc_bgzf_scan(const uint8_t* buf, int64_t nbytes, int64_t max_blocks, in
                       int64_t* text_off, int64_t* n_blocks, int64_t* used_bytes, int* last_is_eof);
 int sarlacc_dev_bgzf_inflate(const uint8_t* d_comp, const int64_t* d_comp_off, const int64_t* d_text_off, int64_t n_blocks,
                              int64_t first_block, uint8_t* d_text, int check_crc, void* stream);
+int sarlacc_bgzf_deflate_bound(int64_t nbytes, int64_t* n_blocks, int64_t* comp_capacity);
+int sarlacc_dev_bgzf_deflate(const uint8_t* d_text, int64_t nbytes, int mode, uint8_t* d_comp, int64_t comp_capacity,
+                             int64_t* d_comp_off, int64_t* comp_bytes, void* stream);
 int sarlacc_dev_copy(void* d_dst, const void* d_src, int64_t bytes, void* stream);
 int sarlacc_dev_rfind_byte(const uint8_t* d_text, int64_t nbytes, int value, int64_t* pos, void* stream);
 int sarlacc_dev_bam_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_record, int at_eof, int64_t n_ref,

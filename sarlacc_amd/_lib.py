@@ -159,6 +159,8 @@ def _prototypes():
         "sarlacc_dev_bam_reads_extract": (i, [p, i64, i64, i, p, p, p, p, p, p]),
         "sarlacc_bgzf_scan": (i, [p, i64, i64, i64, p, p, p, p, p]),
         "sarlacc_dev_bgzf_inflate": (i, [p, p, p, i64, i64, p, i, p]),
+        "sarlacc_bgzf_deflate_bound": (i, [i64, p, p]),
+        "sarlacc_dev_bgzf_deflate": (i, [p, i64, i, p, i64, p, p, p]),
         "sarlacc_dev_copy": (i, [p, p, i64, p]),
         "sarlacc_dev_rfind_byte": (i, [p, i64, i, p, p]),
         "sarlacc_compute_lev_masked": (i, [p, p, i64, p]),

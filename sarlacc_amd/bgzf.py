@@ -5,7 +5,11 @@ A BGZF file is a series of independent gzip members of at most 64 KB each.  The 
 (sarlacc_dev_bgzf_inflate, bgzf.hip) into a device text buffer that the FASTQ and SAM parsers read where it lies, so
 the inflated text never visits the host.  Plain gzip (no BC subfield) cannot be split without inflating it: it is
 streamed through zlib on the host into the text path, a slow path kept for correctness only.  Anything that does
-not start with the gzip magic is text and takes the text path untouched."""
+not start with the gzip magic is text and takes the text path untouched.
+
+Compressed output: deflate_device turns text in device memory into BGZF blocks there (sarlacc_dev_bgzf_deflate,
+bgzf_deflate.hip), so that only compressed bytes come back; DeviceReads.to_fastq(compress=True) writes them and
+EOF_BLOCK behind them."""
 import ctypes as C
 import zlib
 
@@ -15,6 +19,8 @@ from . import _lib
 from ._lib import SarlaccError, check
 
 TEXT, GZIP, BGZF = "text", "gzip", "bgzf"
+# the empty block that ends a BGZF file (SAM specification section 4.1.2)
+EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
 def sniff_bytes(head):
@@ -139,6 +145,25 @@ def inflate_into(d_text, at, comp, comp_off, text_off, first_block, check_crc=Tr
     d_co, d_to = DevBuffer.from_numpy(comp_off), DevBuffer.from_numpy(text_off)
     check(_lib.lib().sarlacc_dev_bgzf_inflate(d_comp, d_co, d_to, n, int(first_block), d_text.ptr.value + int(at),
                                               1 if check_crc else 0, None))
+
+
+def deflate_bound(nbytes):
+    """sarlacc_bgzf_deflate_bound: (number of BGZF blocks, bytes the output buffer must hold) for `nbytes` of text."""
+    n, cap = C.c_int64(0), C.c_int64(0)
+    check(_lib.lib().sarlacc_bgzf_deflate_bound(int(nbytes), C.byref(n), C.byref(cap)))
+    return n.value, cap.value
+
+
+def deflate_device(d_text, nbytes, mode=0, out=None):
+    """Device text -> BGZF blocks in device memory (sarlacc_dev_bgzf_deflate; no end-of-file block): (DevBuffer,
+    compressed bytes).  mode 0 takes per block the smallest of one Huffman table, a table per line and stored; 1 leaves
+    the per-line tables out, 2 stores.  `out` is a buffer to reuse, of at least deflate_bound(nbytes)[1] bytes."""
+    from .resident import DevBuffer
+    cap = deflate_bound(nbytes)[1]
+    d_comp = out if out is not None else DevBuffer(max(cap, 1))
+    total = C.c_int64(0)
+    check(_lib.lib().sarlacc_dev_bgzf_deflate(d_text, int(nbytes), int(mode), d_comp, d_comp.nbytes, None, C.byref(total), None))
+    return d_comp, total.value
 
 
 class DeviceTextStream:

@@ -21,7 +21,8 @@
 // loads are the unaligned side --; a piece that holds a separator, the digits of a default name, a string's first or last
 // bytes or the ends of the text is put together byte by byte.
 //
-// Out of scope: gzip output, multi-line FASTQ, a repeated name on the '+' line.
+// Compressed output is bgzf_deflate.hip's, on the text this file leaves in device memory.
+// Out of scope: multi-line FASTQ, a repeated name on the '+' line.
 #include "common.hpp"
 #include "devprim.hpp"
 

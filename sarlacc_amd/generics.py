@@ -83,13 +83,18 @@ def _check_bam_qual_type(path, qual_type):
         raise ValueError("'qual_type' is '%s', but a BAM file holds Phred qualities" % qual_type)
 
 
-def write_fastq(path, reads, append=False):
+def write_fastq(path, reads, append=False, compress=False):
     """Reads -> 4-line FASTQ (LF only; READ_<i> where there are no names).  A resident batch (resident.DeviceReads, e.g.
     realizeReads(..., resident=True)) is formatted on the device and written block by block (DeviceReads.to_fastq,
-    whose byte count is returned); host Reads are not sent through the device."""
+    whose byte count is returned); host Reads are not sent through the device.  compress=True writes BGZF, deflated on
+    the device (DeviceReads.to_fastq): host Reads are uploaded for it.  The file's name plays no part in the choice."""
     from .resident import DeviceReads
     if isinstance(reads, DeviceReads):
-        return reads.to_fastq(path, append=append)
+        return reads.to_fastq(path, append=append, compress=compress)
+    if compress:
+        dev = DeviceReads.upload(reads)
+        dev.names = list(reads.names) if reads.names else None
+        return dev.to_fastq(path, append=append, compress=True)
     with open(path, "ab" if append else "wb") as fh:
         for i, (s, q) in enumerate(zip(reads.seq.to_strings(), reads.qual.to_strings())):
             name = reads.names[i] if reads.names else "READ_%d" % (i + 1)

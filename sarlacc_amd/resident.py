@@ -342,15 +342,44 @@ class DeviceReads:
         repeated name on the '+' line."""
         return b"".join(blk.tobytes() for blk in self._fastq_blocks(self._fastq_plan(block_bytes)))
 
-    def to_fastq(self, path, append=False, block_bytes=256 << 20):
+    def _fastq_bgzf_blocks(self, plan, mode=0):
+        """_fastq_blocks, compressed: every block of text is formatted as there, deflated where it lies into BGZF blocks
+        (bgzf.deflate_device) and only the compressed bytes are downloaded, again into ONE reused page-locked buffer."""
+        from . import bgzf
+        names, noff, rec_off, ro, ranges = plan
+        if not ranges:
+            return
+        largest = max(int(ro[b] - ro[a]) for a, b in ranges)
+        cap = bgzf.deflate_bound(largest)[1]
+        d_text, d_comp, host = DevBuffer(largest), DevBuffer(cap), _lib.host_array(cap, np.uint8)
+        for a, b in ranges:
+            check(_lib.lib().sarlacc_dev_fastq_format(self.seq, self.qual, self.off, names, noff, 1, rec_off, a, b - a, d_text, None))
+            _, nbytes = bgzf.deflate_device(d_text, int(ro[b] - ro[a]), mode, out=d_comp)
+            check(_lib.lib().sarlacc_dev_download(host, d_comp, nbytes))
+            yield host[:nbytes]
+
+    def to_fastq(self, path, append=False, block_bytes=256 << 20, compress=False):
         """Writes fastq_text() to `path` (after what is there with append=True) and returns the bytes written.  The
         text is formatted on the device in blocks of whole records of at most `block_bytes` (a single larger record
         gets a block of its own size), each downloaded into one page-locked buffer and written with one write(), so
         neither the host nor the device ever holds more than one block of text -- the bound of stream_fastq.  The file
-        is opened only once the names have passed the check: a refused batch leaves it as it was."""
+        is opened only once the names have passed the check: a refused batch leaves it as it was.
+        With compress=True the file is BGZF (what bgzip writes; from_fastq and any gzip reader take it): every block of
+        text is deflated on the device where it was formatted (sarlacc_dev_bgzf_deflate: Huffman codes, a table per line
+        where that is smaller), only the compressed bytes come to the host, and the 28-byte end-of-file block follows the
+        last of them -- alone for an empty batch.  The count returned is that of the file's new bytes.  append=True leaves
+        the end-of-file block of what was there in the middle, an empty member that BGZF permits.  Compression is never
+        inferred from the name of the file."""
         plan = self._fastq_plan(block_bytes)
         written = 0
         with open(path, "ab" if append else "wb") as fh:
+            if compress:
+                from .bgzf import EOF_BLOCK
+                for blk in self._fastq_bgzf_blocks(plan):
+                    fh.write(blk)
+                    written += blk.size
+                fh.write(EOF_BLOCK)
+                return written + len(EOF_BLOCK)
             for blk in self._fastq_blocks(plan):
                 fh.write(blk)
                 written += blk.size
