@@ -66,9 +66,25 @@ static int g_nocap = 0, g_nofilter = 0;
 static int g_library = MSA2_LIBRARY;   /* other partner positions kept per (a, p, b) beside the direct one: 3 by the spec; -1: the unbounded library of rounds 2-4 */
 enum { ST_JOINS, ST_ROWS, ST_ROWS_WITH_CAND, ST_ROWS_CAPPED, ST_CAND_IGNORED, ST_ENT_BEFORE_FILTER, ST_ENT_FILTERED,
        ST_ROWS_FILTERED, ST_ENT_KEPT, ST_TRIPLES, ST_TRIPLES_2Q, ST_TRIPLES_3Q, ST_TRIPLES_GAPDIRECT, ST_CANDIDATES,
-       ST_ROWS_MULTI, ST_MAX_ROW_ENTRIES, ST_LIB_IGNORED, ST_N };
+       ST_ROWS_MULTI, ST_MAX_ROW_ENTRIES, ST_LIB_IGNORED,
+       ST_MAX_ROW_REACH, ST_MAX_REACH_AHEAD, ST_JOINS_REACH_CERTAIN, ST_JOINS_REACH_POSSIBLE, ST_N };
 static int64_t g_stats[ST_N];
 #define STAT_ADD(k, v) __atomic_fetch_add(&g_stats[k], (int64_t)(v), __ATOMIC_RELAXED)
+static void stat_max(int k, int64_t v) {
+    int64_t cur = __atomic_load_n(&g_stats[k], __ATOMIC_RELAXED);
+    while (v > cur && !__atomic_compare_exchange_n(&g_stats[k], &cur, v, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+}
+/* How far behind the front of the chain a join's matches reach, to bound what the product's chain kernel must do
+ * (sarlacc_amd/csrc/msa2.hip, m2_chain_forward<true>: it keeps the columns in a ring and gives the join up for the variant over
+ * all columns when a block of matches reaches M2_QW - 2 columns behind the front).  The kernel takes the match list in blocks of
+ * at most 64 matches that end on row boundaries, so a block holds a run of at most 64 of the rows that have matches.  For such a
+ * row r, with jmin_r its smallest column: F_r = the largest column among the matches of the rows up to r, Fa_r = that among the
+ * matches of the rows up to the 63rd row with matches after r.  The block that holds r has its front at F_r or beyond and its
+ * smallest column at jmin_r or before: it reaches at least F_r - jmin_r.  The block whose smallest column is jmin_r has its front
+ * at Fa_r at most.  Hence, with R = MSA2_RING_REACH:  joins with some F_r - jmin_r >= R  <=  joins the kernel redoes over all
+ * columns  <=  joins with some Fa_r - jmin_r >= R. */
+#define MSA2_RING_REACH 510   /* M2_QW - 2 of msa2.hip */
+#define MSA2_BLOCK_ROWS 64
 
 void orc_msa2_set_rules(int nocap, int nofilter) { g_nocap = nocap; g_nofilter = nofilter; }
 void orc_msa2_set_library(int others) { g_library = others > MSA2_XMAX ? MSA2_XMAX : others; }
@@ -386,6 +402,26 @@ int orc_msa2_group(const char* seq, const int64_t* off, int64_t n, int ma, int m
             }
         }
         free(idxA); free(lj); free(lw);
+        if (nm > 0) {   /* reach of the rows behind the front (see MSA2_RING_REACH) */
+            int64_t* rmin = (int64_t*)malloc(sizeof(int64_t) * (size_t)nm);   /* smallest column of the k-th row with matches */
+            int64_t* fr = (int64_t*)malloc(sizeof(int64_t) * (size_t)nm);     /* largest column of the rows up to it */
+            int64_t nrw = 0, front = -1, reach = 0, ahead = 0;
+            for (int64_t m = 0; m < nm; ++m) {
+                if (m == 0 || mi[m] != mi[m - 1]) { rmin[nrw] = mj[m]; ++nrw; }   /* (columns ascend inside a row) */
+                if (mj[m] > front) front = mj[m];
+                fr[nrw - 1] = front;
+            }
+            for (int64_t k = 0; k < nrw; ++k) {
+                const int64_t ka = k + MSA2_BLOCK_ROWS - 1 < nrw ? k + MSA2_BLOCK_ROWS - 1 : nrw - 1;
+                if (fr[k] - rmin[k] > reach) reach = fr[k] - rmin[k];
+                if (fr[ka] - rmin[k] > ahead) ahead = fr[ka] - rmin[k];
+            }
+            stat_max(ST_MAX_ROW_REACH, reach);
+            stat_max(ST_MAX_REACH_AHEAD, ahead);
+            if (reach >= MSA2_RING_REACH) STAT_ADD(ST_JOINS_REACH_CERTAIN, 1);
+            if (ahead >= MSA2_RING_REACH) STAT_ADD(ST_JOINS_REACH_POSSIBLE, 1);
+            free(rmin); free(fr);
+        }
         /* heaviest chain: f(m) = w(m) + best f over matches with smaller row and smaller column;
          * "best" = larger f, then smaller match index.  bestAt[j] = best match ending in column j among the
          * processed rows; a row's matches all look at the state before the row. */

@@ -168,7 +168,9 @@ int orc_msa2_group(const char* seq, const int64_t* off, int64_t nreads,
  * joins, rows, rows with candidates, rows capped, candidates ignored by the cap, entries before the filter,
  * entries filtered, rows filtered, entries kept, (a,p,b) triples, triples naming >= 2 / >= 3 positions of b,
  * triples whose direct edge is a gap, candidates, rows with > 1 entry, most entries in a row, partner positions the
- * bounded library ignored. */
+ * bounded library ignored, the farthest a row's matches reach behind the front of a join's chain (over the rows up to it / with
+ * the 63 further rows a block of the product's chain kernel can hold), joins where that reaches the product's ring (certainly /
+ * possibly: msa2.c MSA2_RING_REACH). */
 void orc_msa2_set_rules(int nocap, int nofilter);
 /* other partner positions kept per (a, p, b) beside the direct one (spec: 3); -1 = the unbounded library of rounds 2-4 */
 void orc_msa2_set_library(int others);

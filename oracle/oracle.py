@@ -329,7 +329,10 @@ def msa2_tree(reads, match, mismatch, gap_extension, gap_opening, bandwidth):
 MSA2_STAT_NAMES = ("joins", "rows", "rows_with_candidates", "rows_capped", "candidates_ignored_by_cap",
                    "entries_before_filter", "entries_filtered", "rows_filtered", "entries_kept", "triples",
                    "triples_2_positions", "triples_3_positions", "triples_gap_direct", "candidates",
-                   "rows_multi_entry", "max_row_entries", "library_positions_ignored")
+                   "rows_multi_entry", "max_row_entries", "library_positions_ignored",
+                   # how far a join's matches reach behind the front of the chain (msa2.c, MSA2_RING_REACH): over the rows up to a
+                   # row / up to 63 rows with matches further, and the joins where that reaches the product's ring
+                   "max_row_reach", "max_reach_ahead", "joins_reach_certain", "joins_reach_possible")
 
 
 def msa2_set_rules(nocap=False, nofilter=False):

@@ -579,9 +579,11 @@ def test_pairwise_bitvector_long_reads(oracle):
 @pytest.mark.parametrize("seed,nmol,per,length", [(41, 2, 9, 500), (42, 3, 8, 400), (43, 2, 15, 900), (44, 4, 7, 250)])
 def test_msa_spec2_umi_collisions(oracle, seed, nmol, per, length):
     """Clusters of several unrelated molecules (UMI collisions: a quarter of the clusters at 10^5 molecules): their
-    library is mostly noise, matches scatter far behind the front of the chain (the windowed chain kernel hands such
-    rounds to the exact one) and profiles outgrow the first-pass capacity (second pass with exact capacity) -- rows
-    must still be those of the CPU statement, in one call with ordinary clusters around them."""
+    library is mostly noise and both row rules act -- rows must still be those of the CPU statement, in one call with ordinary
+    clusters around them.  These inputs reach neither the chain's fallback nor the second pass: over the four cases a row's matches
+    lie at most 67 to 146 columns behind the front of the chain (the ring holds 510; oracle.msa2_stats max_row_reach), and the
+    widest alignments are 548 to 1950 columns, inside even the tight capacity of two read lengths (688 to 2208 for those
+    groups).  tests/test_gpu_msa_merge.py has the inputs that reach both, and asserts by the library's counters that they ran."""
     from sarlacc_amd import calls
     from sarlacc_amd.mock import NUC, mutate
     calls.set_msa_spec(2)
@@ -608,8 +610,10 @@ def test_msa_spec2_umi_collisions(oracle, seed, nmol, per, length):
             assert a == b, "group %d differs" % g
         for rows, g in zip(got, groups):
             assert [r.replace("-", "") for r in rows] == [reads[i - 1] for i in g]
-        # the first-pass capacity grows with the group size (a cluster of n reads holds about n / 10 molecules), so these clusters
-        # fit it; with two read lengths for every group they outgrow it and take the second pass with exact capacity
+        # the first-pass capacity grows with the group size (a cluster of n reads holds about n / 10 molecules); with two read
+        # lengths for every group the profiles are laid out at a smaller stride -- these clusters still fit (the heaviest chain
+        # has no gap penalty: unrelated reads pair at most positions), so this is the same merge in tighter arrays, not the
+        # second pass (tests/test_gpu_msa_merge.py forces that one)
         calls.set_option("msa2_tight_profiles", 1)
         try:
             tight = calls.quick_msa(groups, reads, 0, -1, -5, -1, 100)
