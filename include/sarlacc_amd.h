@@ -545,7 +545,10 @@ int sarlacc_set_msa_spec(int spec);
  *   "msa_int32", "msa_affine", "msa_bitvector" (-1 never, 2 one kernel for fill and walk), "msa_bitvector_core" (-1 whole
  *   records, 1 one word), "msa_bitvector_tile_gb" (GB), "umi_full_rounds", "umi_tile_search", "umi_split_min" (a set size),
  *   "umi_scan_single", "align_wide_barrier" (references beyond 1 024 columns: the kernel with a barrier per step everywhere),
- *   "align_wide_band" (rows either side of the main diagonal whose cells carry traceback codes in k_align_wide_q's first launch; -1: all),
+ *   "align_wide_band" (rows either side of the main diagonal whose cells carry traceback codes in k_align_wide_q's first launch; -1: all;
+ *   sarlacc_stage_count "align_wide_redo" reports the last alignment call: the reads that first launch put on its redo list, their
+ *   walks having left those cells, summed over the call's chunks; -1 where the banded queue kernel did not run -- scores only,
+ *   "align_wide_band" = -1, "align_wide_barrier" = 1, local mode, gapopen < 0, several strips, a reference of up to 1 024 columns),
  *   "msa2_budget_gb" (GB a batch of groups may take), "msa2_max_columns" (a lower ceiling of spec v2's profiles),
  *   "msa2_simple_extend" (the extended library by the one-position-per-lane kernel everywhere), "msa2_wide_extend" (largest
  *   group size of the four-positions-per-lane kernel), "align_locate" (adaptor_align: -1 the snapshot path alone, 1 every read

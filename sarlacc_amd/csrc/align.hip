@@ -2474,12 +2474,20 @@ static int launch_wide(const AlignPlan& p, AlignArgs a, hipStream_t stream) {
 static int report_align(const AlignPlan& p, const LocPlan& lp, const AlignArgs& a, hipStream_t stream, int* bad_qual_read) {
     Context& c = ctx();
     const int *d_stats = a.loc_stats, *d_ccount = a.loc_ccount;
-    int flags[2] = {0, 0}, lstats[LOC_STATS] = {}, ccount[LOC_NCLS] = {};
+    const bool banded = p.wide && p.wide_queue && p.wide_band > 0;   // (a.wide_redo exists)
+    int flags[2] = {0, 0}, lstats[LOC_STATS] = {}, ccount[LOC_NCLS] = {}, wide_redo = 0;
     SL_HIP(hipMemcpyAsync(flags, a.badqual, sizeof flags, hipMemcpyDeviceToHost, stream));
     if (d_stats) SL_HIP(hipMemcpyAsync(lstats, d_stats, sizeof lstats, hipMemcpyDeviceToHost, stream));
     if (d_ccount) SL_HIP(hipMemcpyAsync(ccount, d_ccount, sizeof ccount, hipMemcpyDeviceToHost, stream));
+    if (banded) SL_HIP(hipMemcpyAsync(&wide_redo, a.wide_redo, sizeof wide_redo, hipMemcpyDeviceToHost, stream));
     SL_HIP(hipStreamSynchronize(stream));
     *bad_qual_read = flags[0];
+    // reads the banded first launch of k_align_wide_q put on its redo list (the second launch adds none), summed over the
+    // chunks of a call: run_align's first chunk has set -1, which stands where the banded queue kernel did not run
+    if (banded) {
+        double& redo = c.counts["align_wide_redo"];
+        redo = std::max(redo, 0.0) + wide_redo;
+    }
     // adaptor_align calls: reads the locator handed to the snapshot kernel, and walks of its window that stalled (-1: the
     // call ran the snapshot path alone)
     if (p.mode == 3 || p.mode == 4) {
@@ -2514,6 +2522,7 @@ int run_align(const AlignJob& job, int* bad_qual_read, const ChunkOpts& co) {
     hipStream_t stream = job.stream;
     const int64_t n = job.batch.n;
     if (co.init_bad) *bad_qual_read = std::numeric_limits<int>::max();
+    if (co.init_bad) c.counts["align_wide_redo"] = -1.0;   // (report_align counts where the banded queue kernel runs)
     if (n <= 0) return 0;
     if (job.sc.enc_n > 256) return fail("sarlacc_amd: encoding vector longer than 256 entries");
     if (n > std::numeric_limits<int>::max() - 8) return fail("sarlacc_amd: more than 2^31 reads in one call");
