@@ -117,6 +117,8 @@ void Context::side_release() {
     ev_fork = ev_join = nullptr;
 }
 
+void Context::count_add(const char* name, double v) { counts[name] += v; }
+
 void Context::stage_reset(const char* name) {
     StageTimer& t = stages[name];
     t.used = 0;

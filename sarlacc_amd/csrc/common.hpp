@@ -101,6 +101,7 @@ struct Context {
     struct StageTimer { std::vector<std::pair<hipEvent_t, hipEvent_t>> segs; size_t used = 0; bool open = false; };
     std::map<std::string, StageTimer> stages;
     std::map<std::string, double> counts;   // work counters of the last call (cells, jobs ...), sarlacc_stage_count
+    void count_add(const char* name, double v);   // counts[name] += v (a name not yet counted starts at 0)
     // A stream of the library's own beside the caller's (non-blocking, created on first use) and the event pair that
     // forks work onto it and joins it back: adaptor_align's oversize reads run there beside the window kernel.  They belong
     // to the device they were created on (sarlacc_set_device drops them with the buffers).
@@ -168,7 +169,7 @@ int msa_run(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const c
             int64_t nseq, double match, double mismatch, double gap_extension, double gap_opening, int bandwidth,
             bool want_rows, int64_t out_cap, MsaResult* res, const std::function<int()>* overlap = nullptr,
             const uint8_t* d_seq_resident = nullptr);
-// spec v1 (centre-star, msa.hip) with the same interface; msa_run (msa2.hip) applies spec v2 and hands the
+// spec v1 (centre-star, msa.hip) with the same interface; msa_run (msa2_host.cpp) applies spec v2 and hands the
 // groups v2 does not take to it
 int msa1_run(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const char* seq, const int64_t* seq_off,
              int64_t nseq, double match, double mismatch, double gap_extension, double gap_opening, int bandwidth,

@@ -32,114 +32,24 @@
 // kernels per join for all groups of a batch and spent most of the stage with a few long wavefronts on the chip).
 // A row keeps the first M2_CAP distinct partner columns (spec v2, step 5); groups whose profiles outgrow the
 // fast capacity are redone with profiles as wide as the sum of the read lengths.
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-
-#include "msa_common.hpp"
-
-#include "../../include/sarlacc_amd.h"
+//
+// This file: the kernels and the functions that launch them -- m2_prepare, m2_merge, m2_write_batch, msa_rows_gather, the
+// device half of a batch.  The tables they share with the host half (msa2_host.cpp: plan, batches, rows, msa_run): msa2.hpp.
+#include "msa2.hpp"
 
 #include <algorithm>
-#include <numeric>
 #include <type_traits>
-#include <thread>
-#include <utility>
 #include <vector>
 
 namespace sarlacc {
 
-constexpr int M2_MAXN = 64;          // group sizes aligned by spec v2 (member sets are 64-bit masks; 32-bit ones in the kernels of groups of up to 32)
-constexpr int M2_N32 = 32;
-typedef unsigned long long m2_mask;
 #ifndef M2_WAVES_EU
 #define M2_WAVES_EU 8   // wavefronts per SIMD the merge kernel is compiled for (its registers are capped accordingly)
 #endif
 #ifndef M2_NWD
 #define M2_NWD 4   // wavefronts per group of 33 .. 64 reads
 #endif
-constexpr int M2_NB = 24;   // groups of up to M2_NB reads: one wavefront; up to 32: 8 wavefronts; 33 .. 64: M2_NWD (k_m2_group; sweeps: profiles/r03_exp_m2_class_thresholds_v1.txt, r04_exp_m2_classes_v1.txt -- a 4-wavefront class between the first two lost in every sweep and is gone)
-constexpr int M2_CAP = 16;           // partner columns per row (spec v2, step 5)
 constexpr unsigned M2_NONE = 0xFFFFu;
-// profile capacity of the first pass: same-molecule reads grow a profile by 10-20 %, one or two unrelated reads in
-// the cluster by their length each
-// ... by group size: a cluster of n reads out of umi_group holds about n / 10 molecules (UMI collisions), whose profiles do
-// not align -- one more read length per 8 reads beyond 11.  (With 3 maxlen + 64 for every size the clusters of three and
-// more molecules, the most expensive groups of a call, ran out of columns and were done twice, all-pairs alignments
-// included: 85 ms of the 657 ms merge stage of bench.py's pipeline workload.)
-static inline long long m2_fast_width(long long n, long long maxlen) {
-    if (option(OPT_MSA2_TIGHT_PROFILES)) return 2 * maxlen + 64;
-    return (3 + std::max(0LL, (n - 4) / 8)) * maxlen + 64;
-}
-
-struct M2Member {         // one read of a group
-    long long seq_off;    // into d_seq
-    long long map_base;   // into d_map: (n - 1) arrays of `len` entries, the other members in member order
-    long long col_base;   // into d_col
-    long long ext_base;   // the group's (M2Group::ext_base): k_m2_extend works from the member table alone
-    int len;
-    int first_member;     // of its group
-    int n;                // reads in its group
-    int lmax;             // the group's longest read
-};
-struct M2Group {
-    int first_member;     // member a of the group is members[first_member + a]; joins at first_member + k
-    int n;
-    int wcap;             // capacity of a profile in columns
-    int lmax;             // the group's longest read: stride of the extended library's records per pair
-    long long pos_base;   // into d_pos: n * wcap
-    long long first_job;  // pairwise job of (a, b), a < b: first_job + a n - a (a + 1) / 2 + b - a - 1
-    long long dist_base;  // into the tree kernel's scratch: n * n + n doubles
-    long long ext_base;   // into a plane of the extended library: n (n - 1) / 2 pairs x lmax records
-    long long map0, col0; // map_base / col_base of the group's first member
-};
-
-// counters of one call (sarlacc_stage_count): how often spec v2's own rules act, and the chain's fallback
-enum { M2C_ROWS, M2C_ROWS_CAPPED, M2C_ENT_FILTERED, M2C_ROWS_FILTERED, M2C_ENT_KEPT, M2C_JOINS, M2C_JOINS_HBMQ,
-       M2C_GATHERS,   // wave-wide gather instructions of the rows phase (positions, map entries, records, columns): a lower bound
-       // where the wavefronts' time goes (s_memtime cycles summed over the wavefronts) and when they leave (s_memrealtime, 100 MHz)
-       M2C_CYC_ROWS, M2C_CYC_CHAIN, M2C_CYC_WALK, M2C_CYC_RENUMBER, M2C_T_START, M2C_T_FIRST_EXIT, M2C_T_LAST_EXIT,
-       M2C_T_EXIT1, M2C_T_EXIT4, M2C_T_EXIT8,   // last exit of the instantiations: one wavefront per group / groups of 33 .. 64 reads / 8 wavefronts
-       M2C_N };
-
-struct M2Args {
-    const uint8_t* seq;
-    const M2Group* groups;
-    const M2Member* members;
-    int ngroups;
-    int ma, mm;
-    const uint16_t* map;
-    const int2* stats;
-    double* dist;
-    int2* joins;
-    m2_mask* first;                // per member: the members it meets as part of the FIRST child (k_m2_first)
-    uint32_t* ext;                 // the extended library (k_m2_extend): plane 0 here, planes 1 .. 2 (unit weights) or 1 .. 3 at
-    long long ext_off1, ext_plane; //   ext + ext_off1 + (k - 1) ext_plane -- plane 0 may live in a buffer of its own (m2_merge)
-    uint16_t* col;                 // (a column is < 65535: 16 bits halve the bytes of the walk's column gathers)
-    uint16_t* pos;
-    int* ovf;                      // per group: a profile outgrew its capacity
-    int32_t* width;                // per group: columns of the final profile
-    // ---- k_m2_group: the launch's range of groups [g0, g1), work counter, counters, per-workgroup scratch (w_rows columns each) ----
-    int g0, g1;
-    int* next;
-    unsigned long long* counters;
-    unsigned long long* w_ent;     // match list: (row << 48) | (column << 32) | weight; M2_CAP entries per column
-    unsigned* w_pred;              // per match: 1 + index of its predecessor on its best chain (0: none)
-    int* w_part;                   // partner column of column i of the first child, -1 if unmatched
-    int* w_nca;                    // new numbers of the first child's columns
-    int* w_ncb;                    // ... of the second child's
-    int* w_pb;                     // partner row of column j of the second child
-    unsigned long long* w_q;       // prefix maxima over all columns (the chain's fallback when the LDS ring cannot answer)
-    long long w_rows;
-    int chain_hbm;                 // testing: the prefix maxima in HBM from the start (what the LDS ring falls back to)
-    // ---- row writer ----
-    uint8_t* out;                  // gapped rows
-    uint16_t* out16;               // rows as vote codes instead of characters (CodeSpec, common.hpp): out16 != nullptr
-    const uint8_t* qual;           // laid out like seq
-    int qoffset, navail;
-    int* bad;
-};
 
 __device__ __forceinline__ int m2_w0(int x, int y, int ma, int mm) {
     const int s = (x == y) ? ma : mm;
@@ -334,7 +244,6 @@ __host__ __device__ __forceinline__ long long m2_pair_index(int a, int b, int n)
     const int lo = a < b ? a : b, hi = a < b ? b : a;
     return static_cast<long long>(lo) * n - static_cast<long long>(lo) * (lo + 1) / 2 + hi - lo - 1;
 }
-static inline int m2_ext_planes(bool unitw) { return unitw ? 3 : 4; }
 
 // first[m] = the members b of m's group for which m is in the first child of the join that brings the two together
 __global__ void __launch_bounds__(64) k_m2_first(M2Args A) {
@@ -1323,40 +1232,9 @@ __global__ void k_m2_write(M2Args A, const int* member_group, int nmembers, cons
 
 
 // =============================================================================================
-// host side
-
-static int msa_spec() { return option(OPT_MSA_SPEC) == 1 ? 1 : 2; }
+// the launches: the device half of a batch
 
 static inline unsigned m2_blocks(long long n, int bs) { return static_cast<unsigned>((n + bs - 1) / bs); }
-static inline double m2_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// host seconds of the MSA stage outside its kernels, by part (sarlacc_stage_count "msa_host_<part>_s")
-static void m2_host_time(const char* part, double t0) {
-    std::map<std::string, double>& cn = ctx().counts;
-    const std::string k = std::string("msa_host_") + part + "_s";
-    cn[k] = (cn.count(k) ? cn[k] : 0.0) + (m2_now() - t0);
-}
-
-// One batch of groups (`ids`: indices into the caller's group list) through the v2 kernels.
-// exact_w = false: fast profile capacity (3 maxlen + 64 columns); groups that outgrow it come back flagged.
-// exact_w = true: profiles as wide as the sum of the read lengths, nothing can overflow.
-// Leaves the batch's state (pos, members ...) in the "m2*" workspaces for the row writer.
-struct M2Batch {
-    std::vector<int64_t> ids;      // caller's group indices, by decreasing group size
-    std::vector<size_t> slot;      // position of each in the caller's order (msa2_core)
-    std::vector<M2Group> groups;
-    std::vector<M2Member> members;
-    std::vector<int> member_group;
-    size_t njobs = 0;             // pairwise jobs of the batch (the table itself exists on the device only, k_m2_jobs)
-    std::vector<int32_t> width;   // per group of the batch
-    std::vector<int> ovf;
-    M2Args a{};                   // device pointers
-    int* d_member_group = nullptr;
-    int max_len = 0, max_wcap = 0, max_n = 0;
-    long long ext_n = 0;          // records per plane of the extended library
-    bool alias_tiles = false;     // plane 0 of the library in the pairwise kernel's tile buffer (a call of one batch)
-    MsaJobSummary jsum;           // band classes and cell count of `jobs`
-    hipEvent_t pair_done = nullptr;   // the all-pairs alignments of the batch have finished (m2_prepare -> m2_merge)
-};
 
 // The pairwise job table of a batch (4.4 million jobs, 180 MB at C4) is a function of the group and member tables: it is
 // written on the device (the host would fill it in 30 ms and the copy would hold the stream for 40 more; the host only counts
@@ -1386,164 +1264,14 @@ __global__ __launch_bounds__(256) void k_m2_jobs(const M2Group* __restrict__ gro
     }
 }
 
-// Host tables of a batch: groups and members, and the band classes of the pairwise jobs (4.4 million at C4).  The offsets come
-// from one serial pass over the groups; the members are then filled and the jobs counted by a few threads over disjoint ranges
-// of groups.
-static int m2_plan(M2Batch& B, const int64_t* grp_off, const int32_t* grp, const int64_t* rel, const long long* gsum, const int* gmx,
-                   bool exact_w, int bandwidth) {
-    const size_t ngr = B.ids.size();
-    B.groups.assign(ngr, M2Group{});
-    B.max_len = 0; B.max_wcap = 0; B.max_n = 0;
-    long long map_pos = 0, col_pos = 0, pos_pos = 0, dist_pos = 0, ext_pos = 0, mem_pos = 0, job_pos = 0;
-    for (size_t q = 0; q < ngr; ++q) {
-        const int64_t g = B.ids[q];
-        const int n = static_cast<int>(grp_off[g + 1] - grp_off[g]);
-        M2Group& G = B.groups[q];
-        G.first_member = static_cast<int>(mem_pos);
-        G.n = n;
-        const long long sum = gsum[B.slot[q]];   // sum and maximum of the group's read lengths (msa2_core)
-        const int mx = gmx[B.slot[q]];
-        const long long fast_w = m2_fast_width(n, mx);
-        // (65535 columns is the ceiling of spec v2: positions and columns are 16-bit; only reachable when the sum of
-        // the read lengths exceeds it AND the alignment really is that wide)
-        // (msa2_max_columns: a lower ceiling, for the tests of the hand-over to spec v1)
-        const long long ceiling = option(OPT_MSA2_MAX_COLUMNS) > 0 ? std::min(65535, option(OPT_MSA2_MAX_COLUMNS)) : 65535;
-        G.wcap = static_cast<int>(std::min<long long>(ceiling, std::min<long long>(sum, exact_w ? sum : fast_w)));
-        if (G.wcap < 1) G.wcap = 1;
-        G.pos_base = pos_pos;
-        G.first_job = job_pos;
-        G.dist_base = dist_pos;
-        G.ext_base = ext_pos;
-        G.lmax = mx;
-        G.map0 = map_pos;
-        G.col0 = col_pos;
-        pos_pos += static_cast<long long>(n) * G.wcap;
-        dist_pos += static_cast<long long>(n) * n + n;
-        ext_pos += static_cast<long long>(n) * (n - 1) / 2 * mx;
-        map_pos += static_cast<long long>(std::max(0, n - 1)) * sum;
-        col_pos += sum;
-        mem_pos += n;
-        job_pos += static_cast<long long>(n) * (n - 1) / 2;
-        B.max_len = std::max(B.max_len, mx);
-        B.max_wcap = std::max(B.max_wcap, G.wcap);
-        B.max_n = std::max(B.max_n, n);
-    }
-    B.ext_n = ext_pos;
-    B.members.assign(static_cast<size_t>(mem_pos), M2Member{});
-    B.member_group.assign(static_cast<size_t>(mem_pos), 0);
-    B.njobs = static_cast<size_t>(job_pos);
-    auto fill = [&](size_t q0, size_t q1, MsaJobSummary* sum) {
-        for (size_t q = q0; q < q1; ++q) {
-            const M2Group& G = B.groups[q];
-            const int32_t* mem = grp + grp_off[B.ids[q]];
-            const int n = G.n;
-            M2Member* const M = B.members.data() + G.first_member;
-            long long mp = G.map0, cp = G.col0;
-            for (int a = 0; a < n; ++a) {
-                M2Member& Me = M[a];
-                Me.seq_off = rel[mem[a] - 1];
-                Me.len = static_cast<int>(rel[mem[a]] - rel[mem[a] - 1]);
-                Me.map_base = mp;
-                Me.col_base = cp;
-                Me.ext_base = G.ext_base; Me.first_member = G.first_member; Me.n = n; Me.lmax = G.lmax;
-                mp += static_cast<long long>(std::max(0, n - 1)) * Me.len;
-                cp += Me.len;
-                B.member_group[static_cast<size_t>(G.first_member) + a] = static_cast<int>(q);
-            }
-            // band classes of the group's pairs (rows = b, columns = a: k_m2_jobs).  Where the longest and the shortest read of the
-            // group already fit the narrow class -- nearly every group -- no pair needs a look of its own: the summary's sums
-            // and maxima in closed form, the cell count from a branch-free loop.
-            if (n < 2) continue;
-            int lmin = M[0].len, lmax = M[0].len;
-            for (int a = 1; a < n; ++a) { lmin = std::min(lmin, M[a].len); lmax = std::max(lmax, M[a].len); }
-            const long long widest = static_cast<long long>(lmax - lmin) + 2LL * bandwidth + 1;
-            if (widest <= 256) {
-                sum->wide_listed = true;
-                sum->n[0] += static_cast<size_t>(n) * (n - 1) / 2;
-                sum->band[0] = std::max(sum->band[0], static_cast<int>(widest));
-                const long long base = 2LL * bandwidth + 1;
-                double cells = 0;
-                for (int a = 0; a < n; ++a) {
-                    const int la = M[a].len;
-                    if (a + 1 < n) { sum->cols[0] += static_cast<double>(la) * (n - 1 - a); sum->lc[0] = std::max(sum->lc[0], la); }
-                    if (a > 0) sum->lr[0] = std::max(sum->lr[0], la);
-                    long long acc = 0;
-                    for (int b = a + 1; b < n; ++b) { const long long lb = M[b].len; acc += lb * (base + (lb > la ? lb - la : la - lb)); }
-                    cells += static_cast<double>(acc);
-                }
-                sum->cells += cells;
-                continue;
-            }
-            long long j = G.first_job;
-            for (int a = 0; a < n; ++a)
-                for (int b = a + 1; b < n; ++b, ++j) sum->add(bandwidth, M[b].len, M[a].len, j);
-        }
-    };
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t nthreads = job_pos < 200000 ? 1 : std::max<size_t>(1, std::min<size_t>(hw ? hw : 1, 8));
-    B.jsum = MsaJobSummary{};
-    if (nthreads == 1) fill(0, ngr, &B.jsum);
-    else {
-        // ranges of groups with about the same number of jobs each
-        std::vector<std::thread> pool;
-        std::vector<MsaJobSummary> part(nthreads);
-        size_t q0 = 0;
-        for (size_t t = 0; t < nthreads; ++t) {
-            const long long want = job_pos * static_cast<long long>(t + 1) / static_cast<long long>(nthreads);
-            size_t q1 = q0;
-            while (q1 < ngr && (t + 1 == nthreads || B.groups[q1].first_job + static_cast<long long>(B.groups[q1].n) * (B.groups[q1].n - 1) / 2 <= want)) ++q1;
-            pool.emplace_back(fill, q0, q1, &part[t]);
-            q0 = q1;
-        }
-        for (std::thread& th : pool) th.join();
-        for (const MsaJobSummary& ps : part) B.jsum.merge(ps);
-    }
-    return 0;
-}
-
-// streams of the side-by-side instantiations of k_m2_group (created once per process and device, non-blocking: the
-// caller's stream may be the legacy default one)
-struct M2Streams {
-    std::vector<hipStream_t> st;
-    std::vector<hipEvent_t> join;
-    hipEvent_t fork = nullptr;
-    hipEvent_t pair[2] = {nullptr, nullptr};   // "alignments of the batch in workspace set k are done"
-    int device = -1;
-    int ensure(int n) {
-        if (device != ctx().device) {   // (streams and events belong to the device that was current when they were made)
-            for (hipStream_t x : st) (void)hipStreamDestroy(x);
-            for (hipEvent_t e : join) (void)hipEventDestroy(e);
-            if (fork) (void)hipEventDestroy(fork);
-            for (int k = 0; k < 2; ++k) { if (pair[k]) (void)hipEventDestroy(pair[k]); pair[k] = nullptr; }
-            st.clear(); join.clear(); fork = nullptr;
-            device = ctx().device;
-        }
-        if (!fork) SL_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k)
-            if (!pair[k]) SL_HIP(hipEventCreateWithFlags(&pair[k], hipEventDisableTiming));
-        while (static_cast<int>(st.size()) < n) {
-            hipStream_t x; hipEvent_t e;
-            SL_HIP(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-            SL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            st.push_back(x); join.push_back(e);
-        }
-        return 0;
-    }
-};
-static M2Streams& m2_streams() { static M2Streams m; return m; }
-
 // First half of a batch: tables to the device, workspaces, the all-pairs alignments -- on stream `sp`, which runs ahead of
 // the merging: while the wavefronts of k_m2_group wait for memory (most of their time) the alignments of the NEXT batch
 // keep the vector units busy.  `B.pair_done` fires when the batch's library is complete.
-static int m2_prepare(M2Batch& B, const std::string& pf, const uint8_t* d_seq, double match, double mismatch, double gap_extension,
-                      double gap_opening, int bandwidth, double* cells, bool first_of_call, hipStream_t s) {
+int m2_prepare(M2Batch& B, const std::string& pf, const uint8_t* d_seq, double match, double mismatch, double gap_extension,
+               double gap_opening, int bandwidth, double* cells, bool first_of_call, hipStream_t s) {
     Context& c = ctx();
     const size_t ng = B.groups.size(), nm = B.members.size();
     if (ng == 0) return 0;
-    long long map_n = 0, col_n = 0, pos_n = 0;
-    for (const M2Member& Me : B.members) col_n += Me.len;
-    for (const M2Group& G : B.groups) pos_n += static_cast<long long>(G.n) * G.wcap;
-    if (!B.members.empty()) { const M2Member& L = B.members.back(); const M2Group& G = B.groups[B.member_group.back()]; map_n = L.map_base + static_cast<long long>(std::max(0, G.n - 1)) * L.len; }
     M2Args& a = B.a;
     a = M2Args{};
     M2Group* d_groups; M2Member* d_members; MsaJob* d_jobs; int* d_mg;
@@ -1556,13 +1284,13 @@ static int m2_prepare(M2Batch& B, const std::string& pf, const uint8_t* d_seq, d
     SL_HIP(hipGetLastError());
     B.d_member_group = d_mg;
     uint16_t* d_map; int2* d_stats; double* d_dist; int2* d_joins; m2_mask* d_first; uint16_t* d_col; uint16_t* d_pos; int* d_ovf; int32_t* d_width;
-    SL_TRY(scratch((pf + ".map").c_str(), static_cast<size_t>(map_n) + 1, &d_map));
+    SL_TRY(scratch((pf + ".map").c_str(), static_cast<size_t>(B.map_n) + 1, &d_map));
     SL_TRY(scratch((pf + ".stats").c_str(), B.njobs + 1, &d_stats));
     d_dist = nullptr;   // (the tree kernel keeps its distance matrix in LDS since round 4)
     SL_TRY(scratch((pf + ".joins").c_str(), nm + 1, &d_joins));
     SL_TRY(scratch((pf + ".first").c_str(), nm + 1, &d_first));
-    SL_TRY(scratch((pf + ".col").c_str(), static_cast<size_t>(col_n) + 1, &d_col));
-    SL_TRY(scratch((pf + ".pos").c_str(), static_cast<size_t>(pos_n) + 1, &d_pos));
+    SL_TRY(scratch((pf + ".col").c_str(), static_cast<size_t>(B.col_n) + 1, &d_col));
+    SL_TRY(scratch((pf + ".pos").c_str(), static_cast<size_t>(B.pos_n) + 1, &d_pos));
     SL_TRY(scratch((pf + ".ovf").c_str(), ng, &d_ovf));
     SL_TRY(scratch((pf + ".width").c_str(), ng, &d_width));
     SL_HIP(hipMemsetAsync(d_ovf, 0, sizeof(int) * ng, s));
@@ -1571,7 +1299,7 @@ static int m2_prepare(M2Batch& B, const std::string& pf, const uint8_t* d_seq, d
     a.map = d_map; a.stats = d_stats; a.dist = d_dist; a.joins = d_joins; a.first = d_first;
     a.col = d_col; a.pos = d_pos; a.ovf = d_ovf; a.width = d_width;
 
-    m2_host_time("upload_alloc", th);
+    m2_host_time(M2H_T_UPLOAD_ALLOC, th);
     if (B.alias_tiles && B.ext_n > 0) {   // (before the alignments take their pointer to it)
         void* tb;
         SL_TRY(c.buffer("msa.tb0", static_cast<size_t>(B.ext_n) * 4 + 16, &tb));
@@ -1583,14 +1311,14 @@ static int m2_prepare(M2Batch& B, const std::string& pf, const uint8_t* d_seq, d
     SL_TRY(msa_pairwise_launch(nullptr, B.njobs, d_jobs, d_seq, match, mismatch, gap_extension, gap_opening, bandwidth, 1, nullptr, nullptr,
                                d_map, d_stats, s, &B.jsum, first_of_call));
     SL_TRY(c.stage_end("msa_pairwise", s));
-    m2_host_time("pairwise_launch", th);
+    m2_host_time(M2H_T_PAIRWISE_LAUNCH, th);
     SL_HIP(hipEventRecord(B.pair_done, s));
     return 0;
 }
 
 // Second half: guide trees, the extended library, all the merging, widths back to the host -- on stream `s` (and the streams of
 // the side-by-side instantiations) once the batch's alignments are done.
-static int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStream_t s) {
+int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStream_t s) {
     Context& c = ctx();
     const size_t ng = B.groups.size(), nm = B.members.size();
     if (ng == 0) return 0;
@@ -1604,7 +1332,7 @@ static int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStre
     hipLaunchKernelGGL(k_m2_tree, dim3(static_cast<unsigned>(ng)), dim3(64), 0, s, a);
     if (nm) hipLaunchKernelGGL(k_m2_init, dim3(std::min(2u, std::max(1u, m2_blocks(B.max_len, 256))), static_cast<unsigned>(nm)), dim3(256), 0, s, a, d_mg, static_cast<int>(nm));
     SL_HIP(hipGetLastError());
-    const bool unitw = a.ma <= 1 && a.mm <= 1 && !option(OPT_MSA2_GENERAL_ROWS);
+    const bool unitw = m2_unit_weights(a.ma, a.mm);
     unsigned long long* d_cnt;
     SL_TRY(scratch((pf + ".cnt").c_str(), M2C_N, &d_cnt));
     {
@@ -1653,8 +1381,8 @@ static int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStre
         if (cap > wide_max) {
             const unsigned gx1 = std::max(1u, std::min(8u, m2_blocks(B.max_len, 64 * M2_EXT_WAVES)));
             const size_t lds = static_cast<size_t>(M2_EXT_WAVES) * cn * 128 + static_cast<size_t>(cn) * sizeof(M2XMember);
-            if (unitw) hipLaunchKernelGGL((k_m2_extend<true>), dim3(gx1, static_cast<unsigned>(m1 - m0)), dim3(64 * M2_EXT_WAVES), lds, s, a, d_mg, m0, m1, cn);
-            else hipLaunchKernelGGL((k_m2_extend<false>), dim3(gx1, static_cast<unsigned>(m1 - m0)), dim3(64 * M2_EXT_WAVES), lds, s, a, d_mg, m0, m1, cn);
+            void (*const extend)(M2Args, const int*, int, int, int) = unitw ? k_m2_extend<true> : k_m2_extend<false>;
+            hipLaunchKernelGGL(extend, dim3(gx1, static_cast<unsigned>(m1 - m0)), dim3(64 * M2_EXT_WAVES), lds, s, a, d_mg, m0, m1, cn);
         } else {
             const unsigned gx = std::max(1u, std::min(8u, m2_blocks(B.max_len, 256)));
             hipLaunchKernelGGL(k_m2_extend_unit, dim3(gx, static_cast<unsigned>(m1 - m0)), dim3(64), static_cast<size_t>(cn) * 512, s, a, m0, m1);
@@ -1684,8 +1412,12 @@ static int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStre
         M2Streams& MS = m2_streams();
         SL_TRY(MS.ensure(4));
         SL_HIP(hipEventRecord(MS.fork, s));
-        struct Cls { size_t lo, hi; int nw; const char* tag; int stream; };   // stream: index into MS.st (2 is the alignments' own), -1 = s
-        const Cls cls[3] = {{0, iD, M2_NWD, ".d", 3}, {iD, iC, 8, ".c", 0}, {iC, nmulti, 1, ".a", -1}};
+        // stream: index into MS.st (2 is the alignments' own), -1 = s; kernel: the class's instantiation for any / for unit weights --
+        // the one name that the occupancy query, the grid and the launch below all go by
+        struct Cls { size_t lo, hi; int nw; const char* tag; int stream; void (*kernel[2])(M2Args); };
+        const Cls cls[3] = {{0, iD, M2_NWD, ".d", 3, {k_m2_group<false, M2_NWD, M2_MAXN>, k_m2_group<true, M2_NWD, M2_MAXN>}},
+                            {iD, iC, 8, ".c", 0, {k_m2_group<false, 8, M2_N32>, k_m2_group<true, 8, M2_N32>}},
+                            {iC, nmulti, 1, ".a", -1, {k_m2_group<false, 1, M2_N32>, k_m2_group<true, 1, M2_N32>}}};
         for (int k = 0; k < 3; ++k) {
             if (k == 2) {   // (the side streams have their launches; the caller's stream goes on with the library of the smaller groups)
                 SL_TRY(ext_class(24));
@@ -1699,14 +1431,9 @@ static int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStre
             const long long per_wg = w_rows * (M2_CAP * 12 + 4 * 4 + 8);
             hipStream_t sk = cls[k].stream >= 0 ? MS.st[cls[k].stream] : s;
             if (cls[k].stream >= 0) SL_HIP(hipStreamWaitEvent(sk, MS.fork, 0));
-            const void* fn = unitw ? (k == 0 ? reinterpret_cast<const void*>(&k_m2_group<true, M2_NWD, M2_MAXN>)
-                                      : k == 1 ? reinterpret_cast<const void*>(&k_m2_group<true, 8, M2_N32>)
-                                               : reinterpret_cast<const void*>(&k_m2_group<true, 1, M2_N32>))
-                                   : (k == 0 ? reinterpret_cast<const void*>(&k_m2_group<false, M2_NWD, M2_MAXN>)
-                                      : k == 1 ? reinterpret_cast<const void*>(&k_m2_group<false, 8, M2_N32>)
-                                               : reinterpret_cast<const void*>(&k_m2_group<false, 1, M2_N32>));
+            void (*const kernel)(M2Args) = cls[k].kernel[unitw ? 1 : 0];
             int per_cu = 0;
-            SL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * cls[k].nw, 0));
+            SL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), 64 * cls[k].nw, 0));
             per_cu = std::max(1, std::min(per_cu, 32 / cls[k].nw));
             if (option(OPT_MSA2_WAVES_PER_CU) > 0) per_cu = std::max(1, std::min(per_cu, option(OPT_MSA2_WAVES_PER_CU) / cls[k].nw));
             long long wgs = std::min<long long>(static_cast<long long>(per_cu) * std::max(1, c.num_cu), static_cast<long long>(cls[k].hi - cls[k].lo));
@@ -1726,15 +1453,7 @@ static int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStre
             am.g0 = static_cast<int>(cls[k].lo); am.g1 = static_cast<int>(cls[k].hi);
             am.next = d_next + k;
             const dim3 grid(static_cast<unsigned>(wgs)), block(64 * cls[k].nw);
-            if (unitw) {
-                if (k == 0) hipLaunchKernelGGL((k_m2_group<true, M2_NWD, M2_MAXN>), grid, block, 0, sk, am);
-                else if (k == 1) hipLaunchKernelGGL((k_m2_group<true, 8, M2_N32>), grid, block, 0, sk, am);
-                else hipLaunchKernelGGL((k_m2_group<true, 1, M2_N32>), grid, block, 0, sk, am);
-            } else {
-                if (k == 0) hipLaunchKernelGGL((k_m2_group<false, M2_NWD, M2_MAXN>), grid, block, 0, sk, am);
-                else if (k == 1) hipLaunchKernelGGL((k_m2_group<false, 8, M2_N32>), grid, block, 0, sk, am);
-                else hipLaunchKernelGGL((k_m2_group<false, 1, M2_N32>), grid, block, 0, sk, am);
-            }
+            hipLaunchKernelGGL(kernel, grid, block, 0, sk, am);
             SL_HIP(hipGetLastError());
             if (cls[k].stream >= 0) SL_HIP(hipEventRecord(MS.join[cls[k].stream], sk));
         }
@@ -1767,8 +1486,8 @@ static int m2_merge(M2Batch& B, const std::string& pf, double* counters, hipStre
 }
 
 // rows of the batch's groups (except those sent to the next pass, whose width is 0) at out + off[group of the caller's list]
-static int m2_write_batch(M2Batch& B, const std::string& pf, const std::vector<long long>& off_of_batch_group, void* d_out,
-                          const CodeSpec& code, hipStream_t s) {
+int m2_write_batch(M2Batch& B, const std::string& pf, const std::vector<long long>& off_of_batch_group, void* d_out,
+                   const CodeSpec& code, hipStream_t s) {
     if (B.members.empty()) return 0;
     long long* d_off;
     SL_TRY(upload((pf + ".ooff").c_str(), off_of_batch_group.data(), off_of_batch_group.size(), &d_off, s));
@@ -1788,267 +1507,6 @@ static int m2_write_batch(M2Batch& B, const std::string& pf, const std::vector<l
     return 0;
 }
 
-// spec v2 on the groups `ids` of the caller's list; rows land in *d_rows at off[k] for ids[k] (processing order:
-// the offsets are not cumulative in k), widths in width[k].
-static int msa2_core(const int64_t* grp_off, const int32_t* grp, const std::vector<int64_t>& ids, const uint8_t* d_seq,
-                     const std::vector<int64_t>& rel, double match, double mismatch, double gap_extension, double gap_opening,
-                     int bandwidth, std::vector<int32_t>& width, std::vector<long long>& off, uint8_t** d_rows,
-                     const std::function<int()>* overlap, const CodeSpec& code, hipStream_t s, std::vector<size_t>* gave_up) {
-    Context& c = ctx();
-    const size_t cs = code.want ? 2 : 1;   // bytes per cell of the row buffer (offsets and widths stay in cells)
-    bool waited = false;
-    width.assign(ids.size(), 0);
-    off.assign(ids.size() + 1, 0);
-    *d_rows = nullptr;
-    // row buffer: grown when a batch does not fit (contents are kept)
-    Workspace& rows_ws = c.ws["msa2.rows"];
-    auto rows_reserve = [&](size_t used, size_t need) -> int {
-        if (rows_ws.cap >= need) return 0;
-        const size_t want = std::max(need, rows_ws.cap + rows_ws.cap / 2) + 4096;
-        void* np = nullptr;
-        if (hipMalloc(&np, want) != hipSuccess) {
-            size_t fb = 0, tb = 0;
-            (void)hipGetLastError();
-            (void)hipMemGetInfo(&fb, &tb);
-            size_t held = 0;
-            for (const auto& kv : c.ws) held += kv.second.cap;
-            return fail("sarlacc_amd: cannot allocate %zu bytes of device memory for the alignment rows (%zu free of %zu, the library's workspaces hold %zu)", want, fb, tb, held);
-        }
-        if (rows_ws.ptr) {
-            if (used) SL_HIP(hipMemcpyAsync(np, rows_ws.ptr, used, hipMemcpyDeviceToDevice, s));
-            SL_HIP(hipStreamSynchronize(s));
-            SL_HIP(hipFree(rows_ws.ptr));
-        }
-        rows_ws.ptr = np;
-        rows_ws.cap = want;
-        return 0;
-    };
-    // Batches.  What a batch holds per group is the library (both maps of every pair: 4 (n - 1) bytes per base), the positions /
-    // columns of its profiles and the extended library (12 or 16 bytes per pair and position) -- about 165 GB for C4 (10^5 groups x 10 reads
-    // x 2 kb), sized for an HBM of 288 GB and bounded by a share of what is free now.  A large call is cut into a few
-    // batches that are PIPELINED: the all-pairs alignments of batch k + 1 (vector-unit bound) run on a stream of their
-    // own under the merging of batch k (memory-latency bound); two sets of workspaces alternate.
-    size_t free_b = 0, total_b = 0;
-    SL_HIP(hipMemGetInfo(&free_b, &total_b));
-    // the workspaces an earlier call left are grown in place, not added: everything this stage holds -- the batches' maps, positions,
-    // columns and tables, but also the pairwise kernel's traceback records and move strings, the merging's per-workgroup scratch and
-    // the rows (counting only the first four made the SECOND of two equal calls see half the room and cut itself into 5 batches
-    // where the first took 3)
-    long long reusable = 0;
-    for (const auto& kv : c.ws)
-        if (kv.first.compare(0, 2, "m2") == 0 || kv.first.compare(0, 4, "msa.") == 0 || kv.first.compare(0, 5, "msa2.") == 0)
-            reusable += static_cast<long long>(kv.second.cap);
-    // (msa2_budget_gb: the cap in GB, tests and sweeps; the default leaves the other half of what is free to the traceback records of
-    // the pairwise kernel, the per-workgroup scratch of the merging and the rows)
-    const long long budget_cap = option(OPT_MSA2_BUDGET_GB) > 0 ? static_cast<long long>(option(OPT_MSA2_BUDGET_GB)) << 30 : 96LL << 30;
-    const long long mem_budget = std::max<long long>(1LL << 30, std::min<long long>(budget_cap, (static_cast<long long>(free_b) + reusable) / 2));
-    const long long job_budget = 12000000;
-    double cells = 0, pairs = 0;
-    double counters[M2C_N] = {};
-    const bool unitw_plan = static_cast<int>(match) <= 1 && static_cast<int>(mismatch) <= 1 && !option(OPT_MSA2_GENERAL_ROWS);   // (m2_merge)
-    double second_pass = 0;   // groups whose profiles outgrew the first-pass capacity
-    double nbatches = 0;      // batches of the call (from two on the stage timers of alignments and merging overlap)
-    long long used = 0;
-    M2Streams& MS = m2_streams();
-    SL_TRY(MS.ensure(3));
-    hipStream_t sp = MS.st[2];
-    SL_HIP(hipEventRecord(MS.fork, s));          // whatever the caller queued on `s` (the reads) comes first
-    SL_HIP(hipStreamWaitEvent(sp, MS.fork, 0));
-    bool first = true;
-    // Pass 0: every group with the fast profile capacity.  Pass 1: the groups whose profiles outgrew it (several
-    // unrelated reads in one cluster), with profiles as wide as the sum of the read lengths.
-    std::vector<size_t> todo(ids.size());
-    std::iota(todo.begin(), todo.end(), size_t(0));
-    // sum and maximum of the read lengths of every group, once, by a few threads: the batch sizes below and every batch's plan
-    // start from them (a serial pass over the 10^6 reads of C4 is 5 ms during which the device has nothing to run)
-    std::vector<long long> gsum(ids.size());
-    std::vector<int> gmx(ids.size());
-    {
-        auto lens = [&](size_t q0, size_t q1) {
-            for (size_t q = q0; q < q1; ++q) {
-                const int32_t* mem = grp + grp_off[ids[q]];
-                const long long n = grp_off[ids[q] + 1] - grp_off[ids[q]];
-                long long sum = 0, mx = 0;
-                for (long long a = 0; a < n; ++a) { const long long len = rel[mem[a]] - rel[mem[a] - 1]; sum += len; mx = std::max(mx, len); }
-                gsum[q] = sum; gmx[q] = static_cast<int>(mx);
-            }
-        };
-        const unsigned hw = std::thread::hardware_concurrency();
-        const size_t nt = ids.size() < 20000 ? 1 : std::max<size_t>(1, std::min<size_t>(hw ? hw : 1, 8));
-        if (nt == 1) lens(0, ids.size());
-        else {
-            std::vector<std::thread> th;
-            for (size_t t = 0; t < nt; ++t) th.emplace_back(lens, ids.size() * t / nt, ids.size() * (t + 1) / nt);
-            for (std::thread& x : th) x.join();
-        }
-    }
-    for (int pass = 0; pass < 2 && !todo.empty(); ++pass) {
-        const bool exact_w = pass == 1;
-        // processing order: by decreasing group size -- the workgroups of k_m2_group take the groups in this order, the
-        // longest first
-        std::stable_sort(todo.begin(), todo.end(), [&](size_t x, size_t y) {
-            return grp_off[ids[x] + 1] - grp_off[ids[x]] > grp_off[ids[y] + 1] - grp_off[ids[y]];
-        });
-        std::vector<size_t> again;
-        long long mem_all = 0, jobs_all = 0, ext_all = 0, cells_est = 0;
-        std::vector<long long> cmem(todo.size() + 1, 0), cjobs(todo.size() + 1, 0);   // cumulative over the sorted list
-        for (size_t x = 0; x < todo.size(); ++x) {
-            const size_t q = todo[x];
-            const int64_t g = ids[q];
-            const long long n = grp_off[g + 1] - grp_off[g];
-            const long long sum = gsum[q], mx = gmx[q];
-            const long long wc = exact_w ? sum : std::min(sum, m2_fast_width(n, mx));
-            mem_all += 2 * (n - 1) * sum + 2 * n * wc + 2 * sum + n * (n - 1) / 2 * mx * 4 * m2_ext_planes(unitw_plan);
-            ext_all += n * (n - 1) / 2 * mx * 4 * m2_ext_planes(unitw_plan);
-            cells_est += n * std::min(sum, 2 * mx);   // (rows: about the longest read, some more for clusters of several molecules)
-            mem_all += n * (n - 1) / 2 * ((2 * mx) / 16 + 2) * 4;   // the move strings of the bit-vector pairwise kernel (msa_pairwise.hip)
-            jobs_all += n * (n - 1) / 2;
-            cmem[x + 1] = mem_all; cjobs[x + 1] = jobs_all;
-        }
-        // batches: as many as memory and the job list demand, a few more for the overlap once there is enough work.  (Until round 5
-        // every batch got every nb-th group of the sorted list, "the same mix of sizes" -- and so every batch held some of the
-        // largest groups, whose merging is the longest chain of dependent joins of the call: a 64-read cluster keeps its workgroup
-        // busy for about 2 s, and the merge stage of a call took nb x that -- the same clusters in 1 / 3 / 5 batches: 2.96 / 6.6 /
-        // 9.6 s.  Now the LARGE groups go to the batches in contiguous pieces of the sorted list -- the largest share the first
-        // batch, the longest group of every later batch is shorter than that of the one before -- and only the bulk of
-        // one-wavefront groups is dealt round robin.)
-        // (one batch when everything fits -- then the stage timers do not overlap either; from two on the two workspace
-        // sets share the budget.  Measured at C4 with two pipelined batches: pure groups 5 % faster end to end, clusters
-        // of several molecules unchanged -- the alignments saturate the vector units by themselves.)
-        c.counts["msa2_mem_all_gb"] = static_cast<double>(mem_all) / 1073741824.0;
-        c.counts["msa2_mem_budget_gb"] = static_cast<double>(mem_budget) / 1073741824.0;
-        long long nb = std::max<long long>(1, std::max((mem_all + mem_budget - 1) / mem_budget, (jobs_all + job_budget - 1) / job_budget));
-        // One batch whenever the device holds it: what the stage needs beside a batch's arrays is bounded -- the tile buffer of the
-        // alignments (48 GB at most, and it doubles as plane 0 of the extended library), the per-workgroup scratch of the merging
-        // (16 GB per class at most), the rows.  (Until the library was stored, a batch could have half of what was free and
-        // bench.py's pipeline workload fitted; with it the half-rule cut that call into 4 batches and the merging's launches, each
-        // as long as its longest group, into 4 rounds: 647 ms against 420.)
-        bool one_batch = false;
-        if (option(OPT_MSA2_BUDGET_GB) <= 0 && option(OPT_MSA2_BATCHES) <= 1 && jobs_all <= job_budget) {
-            const long long plane0 = ext_all / m2_ext_planes(unitw_plan);
-            const long long rows_est = 2 * cells_est;
-            const long long extra = std::max<long long>(48LL << 30, plane0) - plane0 + (48LL << 30) + rows_est + (8LL << 30);
-            one_batch = mem_all + extra <= static_cast<long long>(free_b) + reusable;
-            if (one_batch) nb = 1;
-        }
-        const long long want = option(OPT_MSA2_BATCHES) > 0 ? option(OPT_MSA2_BATCHES) : 1;
-        if (!one_batch && std::max(nb, want) > 1) nb = std::max<long long>(want, std::max((2 * mem_all + mem_budget - 1) / mem_budget, (jobs_all + job_budget - 1) / job_budget));
-        nb = std::min<long long>(nb, static_cast<long long>(todo.size()));
-        std::vector<M2Batch> batches(static_cast<size_t>(nb));
-        {
-            // groups of more than M2_NB reads (several wavefronts each, the long chains of joins): contiguous pieces of the sorted
-            // list, by their share of the memory and of the jobs of all such groups; the rest: every nb-th group, so that every
-            // batch has the same bulk of one-wavefront groups to fill the chip beside its large ones
-            size_t nbig = 0;
-            while (nbig < todo.size() && grp_off[ids[todo[nbig]] + 1] - grp_off[ids[todo[nbig]]] > M2_NB) ++nbig;
-            const long long bmem = cmem[nbig], bjobs = cjobs[nbig];
-            size_t k = 0;
-            for (size_t x = 0; x < nbig; ++x) {
-                const double share = std::max(bmem > 0 ? static_cast<double>(cmem[x]) / static_cast<double>(bmem) : 0.0,
-                                              bjobs > 0 ? static_cast<double>(cjobs[x]) / static_cast<double>(bjobs) : 0.0);
-                while (k + 1 < static_cast<size_t>(nb) && share * static_cast<double>(nb) >= static_cast<double>(k + 1)) ++k;
-                batches[k].ids.push_back(ids[todo[x]]);
-                batches[k].slot.push_back(todo[x]);
-            }
-            for (size_t x = nbig; x < todo.size(); ++x) {
-                M2Batch& B = batches[(x - nbig) % static_cast<size_t>(nb)];
-                B.ids.push_back(ids[todo[x]]);
-                B.slot.push_back(todo[x]);
-            }
-            // (a call with fewer groups than batches, or one huge group taking the share of two pieces, leaves a batch without groups)
-            batches.erase(std::remove_if(batches.begin(), batches.end(), [](const M2Batch& B) { return B.ids.empty(); }), batches.end());
-        }
-        nbatches += static_cast<double>(batches.size());
-        const char* const pfs[2] = {"m2a", "m2b"};
-        auto prepare = [&](size_t k) -> int {
-            M2Batch& B = batches[k];
-            double th = m2_now();
-            SL_TRY(m2_plan(B, grp_off, grp, rel.data(), gsum.data(), gmx.data(), exact_w, bandwidth));
-            m2_host_time("plan", th);
-            B.pair_done = MS.pair[k & 1];
-            B.alias_tiles = batches.size() == 1;
-            SL_TRY(m2_prepare(B, pfs[k & 1], d_seq, match, mismatch, gap_extension, gap_opening, bandwidth, &cells, first, sp));
-            pairs += static_cast<double>(B.njobs);
-            if (first && overlap) SL_TRY((*overlap)());
-            first = false;
-            return 0;
-        };
-        SL_TRY(prepare(0));
-        for (size_t k = 0; k < batches.size(); ++k) {
-            M2Batch& B = batches[k];
-            if (k + 1 < batches.size()) SL_TRY(prepare(k + 1));   // (its workspaces: those of batch k - 1, finished and read back)
-            SL_TRY(m2_merge(B, pfs[k & 1], counters, s));
-            double th = m2_now();
-            long long need = used;
-            std::vector<long long> boff(B.groups.size(), 0);
-            std::vector<int32_t> bw = B.width;
-            // The rows of a batch are laid out in the CALLER's group order (the batch itself is ordered by group size): when one
-            // batch holds every group -- the usual case -- the buffer is then already what msa_run hands on, and its gathering
-            // copy (4.6 GB of vote codes at 10^6 reads: 5 ms) is skipped.
-            std::vector<size_t> byslot(B.groups.size());
-            std::iota(byslot.begin(), byslot.end(), size_t(0));
-            std::sort(byslot.begin(), byslot.end(), [&](size_t x, size_t y) { return B.slot[x] < B.slot[y]; });
-            for (size_t q : byslot) {
-                if (B.ovf[q]) {   // profile capacity exceeded: next pass
-                    // (with profiles as wide as 16-bit columns allow and still too narrow: the alignment is wider than 65 535 columns,
-                    // beyond spec v2 -- the caller hands the group to spec v1)
-                    if (exact_w) gave_up->push_back(B.slot[q]); else again.push_back(B.slot[q]);
-                    bw[q] = 0;
-                    continue;
-                }
-                width[B.slot[q]] = bw[q];
-                off[B.slot[q]] = need;
-                boff[q] = need;
-                need += static_cast<long long>(bw[q]) * B.groups[q].n;
-            }
-            SL_TRY(rows_reserve(static_cast<size_t>(used) * cs, (static_cast<size_t>(need) + 1) * cs));
-            SL_HIP(hipMemcpyAsync(B.a.width, bw.data(), sizeof(int32_t) * bw.size(), hipMemcpyHostToDevice, s));
-            B.width = bw;
-            if (code.want && code.ready && !waited) { SL_HIP(hipStreamWaitEvent(s, code.ready, 0)); waited = true; }   // qualities in HBM
-            SL_TRY(m2_write_batch(B, pfs[k & 1], boff, rows_ws.ptr, code, s));
-            SL_HIP(hipStreamSynchronize(s));   // the batch's host vectors and workspaces are reused by the batch after the next
-            m2_host_time("rows", th);
-            used = need;
-        }
-        if (pass == 0) second_pass = static_cast<double>(again.size());
-        todo.swap(again);
-    }
-    SL_HIP(hipStreamSynchronize(sp));
-    if (pairs > 0) {
-        int* d_stuck;
-        int stuck = 0;
-        SL_TRY(scratch("msa.stuck", 1, &d_stuck));
-        SL_HIP(hipMemcpy(&stuck, d_stuck, sizeof stuck, hipMemcpyDeviceToHost));
-        if (stuck) return fail("sarlacc_amd: internal error: an MSA traceback exceeded its step bound");
-    }
-    auto add = [&](const char* name, double v) { c.counts[name] = (c.counts.count(name) ? c.counts[name] : 0.0) + v; };
-    add("msa_pairs", pairs);
-    add("msa_cells", cells);
-    add("msa2_rows", counters[M2C_ROWS]);
-    add("msa2_rows_capped", counters[M2C_ROWS_CAPPED]);
-    add("msa2_entries_filtered", counters[M2C_ENT_FILTERED]);
-    add("msa2_rows_filtered", counters[M2C_ROWS_FILTERED]);
-    add("msa2_entries_kept", counters[M2C_ENT_KEPT]);
-    add("msa2_joins", counters[M2C_JOINS]);
-    add("msa2_joins_chain_in_hbm", counters[M2C_JOINS_HBMQ]);
-    add("msa2_gathers", counters[M2C_GATHERS]);
-    add("msa2_groups_second_pass", second_pass);
-    add("msa2_batches", nbatches);
-    add("msa2_cycles_rows", counters[M2C_CYC_ROWS]);
-    add("msa2_cycles_chain", counters[M2C_CYC_CHAIN]);
-    add("msa2_cycles_walk", counters[M2C_CYC_WALK]);
-    add("msa2_cycles_renumber", counters[M2C_CYC_RENUMBER]);
-    add("msa2_launches", counters[M2C_T_START]);
-    add("msa2_first_exit_s", counters[M2C_T_FIRST_EXIT]);
-    add("msa2_last_exit_s", counters[M2C_T_LAST_EXIT]);
-    add("msa2_exit_s_1wave", counters[M2C_T_EXIT1]);
-    add("msa2_exit_s_4waves", counters[M2C_T_EXIT4]);
-    add("msa2_exit_s_8waves", counters[M2C_T_EXIT8]);
-    if (!rows_ws.ptr) SL_TRY(rows_reserve(0, 16));
-    *d_rows = static_cast<uint8_t*>(rows_ws.ptr);
-    return 0;
-}
-
 __global__ void k_rows_copy(const uint8_t* src, const long long* src_off, uint8_t* dst, const long long* dst_off, const long long* nbytes) {
     const long long g = blockIdx.x;
     const long long n = nbytes[g];
@@ -2057,212 +1515,24 @@ __global__ void k_rows_copy(const uint8_t* src, const long long* src_off, uint8_
     for (long long k = threadIdx.x; k < n; k += blockDim.x) d[k] = s[k];
 }
 
-// Scoring domain of the MSA stage (oracle/oracle.py msa_check_scores states the same rule).  The four
-// scores are truncated toward zero to integers.  With S the largest magnitude among them and L the longest read of the call's
-// groups, the call is accepted when  S * (2 L + 2) < 2^27:
-//   * every finite cell of a pairwise DP is a sum of at most lr + lc <= 2 L scores, so |H|, |E|, |F| <= S (lr + lc);
-//   * the 32-bit kernel (msa_pairwise.hip) stands for "outside the band" by MSA_NEG = -2^28 PLUS what the recurrence adds to it
-//     (a cell beyond the band edge holds a finite value of that size, one penalty is added on the way in), i.e. at most
-//     -2^28 + S (lr + lc + 2).  That has to stay below every finite candidate, which is at least -S (lr + lc + 2):
-//     2 S (lr + lc + 2) < 2^28.  The CPU statement's "outside" is the constant INT_MIN / 4 = -2^29, never added to: the looser of
-//     the two, so the kernel's bound decides;
-//   * no 32-bit sum overflows (2^28 + 2^28 + 2^27 < 2^31), and |score| < 2^27 makes the conversion from double defined
-//     (NaN and infinities fail the comparison and are rejected with the rest).
-static int msa_check_scores(double match, double mismatch, double gap_extension, double gap_opening, int64_t longest) {
-    const double lim = 134217728.0;   // 2^27
-    long long smax = 0;
-    for (const double v : {match, mismatch, gap_extension, gap_opening}) {
-        if (!(std::fabs(v) < lim)) { smax = 1LL << 27; break; }
-        smax = std::max(smax, std::llabs(static_cast<long long>(v)));
-    }
-    if (smax * (2 * static_cast<long long>(longest) + 2) >= (1LL << 27))
-        return fail("sarlacc_amd: MSA scores outside the scoring domain: max |score| * (2 * longest read + 2) must stay below 2^27 "
-                    "(scores %g %g %g %g, longest read %lld)", match, mismatch, gap_extension, gap_opening, static_cast<long long>(longest));
-    return 0;
-}
-
-// Spec v2 with weights other than 1: does a group of n reads, the longest of `longest` bases, under
-// the largest primary weight W = max(match, mismatch, 1) fit the fields its weights are kept in?  With P = floor(n/2) ceil(n/2),
-// the most member pairs (a, b) a join of two profiles can have:
-//   * a library record of (a, p, b) sums the direct weight and one triplet per third read, (n - 1) W at most, into the 16 bits
-//     of its slot (k_m2_extend: w0 | others << 16, wk | qk << 16):                               (n - 1) W <= 65 535;
-//   * a row entry sums one slot of the record of every member pair, P (n - 1) W at most, in a 32-bit int that the noise
-//     filter doubles (2 w >= heaviest):                                                          P (n - 1) W < 2^30
-//     (implied by the first bound, 1 024 * 65 535 < 2^30; stated because the field is a different one);
-//   * a chain sums row entries in 32 unsigned bits ((f << 32) | ~id).  Every position p of a member a lies in ONE column of the
-//     first child, hence in at most one match of a chain, where the pair (a, b) adds one slot of its record:
-//                                                                                         P (n - 1) W longest <= 2^32 - 1.
-// With W = 1 all three hold for every group spec v2 takes (n <= 64, longest <= 65 471: 1 024 * 63 * 65 471 < 2^32), so the
-// unit-weight path never sees the guard act.
-static bool m2_weights_fit(long long n, long long longest, long long W) {
-    if (n < 2) return true;
-    const long long P = (n / 2) * ((n + 1) / 2), rec = (n - 1) * W;
-    if (rec > 65535) return false;
-    return P * rec < (1LL << 30) && P * rec * longest <= 0xFFFFFFFFLL;
-}
-
-// The MSA stage of quick_msa: spec v2 for groups of up to M2_MAXN reads whose profiles fit 65535 columns,
-// spec v1 (msa.hip) for the rest and when spec 1 is selected (sarlacc_set_msa_spec / SARLACC_MSA_SPEC=1).
-int msa_run(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const char* seq, const int64_t* seq_off,
-            int64_t nseq, double match, double mismatch, double gap_extension, double gap_opening, int bandwidth,
-            bool want_rows, int64_t out_cap, MsaResult* res, const std::function<int()>* overlap,
-            const uint8_t* d_seq_resident) {
-    {   // the scoring domain, on every route into the stage (both specs, rows or fused, host or resident reads)
-        int64_t longest = 0;
-        for (int64_t k = grp_off[0]; k < grp_off[ngroups]; ++k)
-            if (grp[k] >= 1 && grp[k] <= nseq) longest = std::max<int64_t>(longest, seq_off[grp[k]] - seq_off[grp[k] - 1]);
-        SL_TRY(msa_check_scores(match, mismatch, gap_extension, gap_opening, longest));
-        Context& c0 = ctx();
-        for (const char* nm : {"msa_pairs_bitvector", "msa_pairs_packed", "msa_pairs_packed_linear", "msa_pairs_int32", "msa_pairs_packed_c4", "msa_pairs_packed_c8",
-                               "msa_pairs_packed_c16", "msa_pairs_int32_c4", "msa_pairs_int32_c8", "msa_pairs_int32_c16", "msa_v1_fallback_weights"})
-            c0.counts[nm] = 0;
-    }
-    if (msa_spec() == 1)
-        return msa1_run(grp_off, grp, ngroups, seq, seq_off, nseq, match, mismatch, gap_extension, gap_opening, bandwidth, want_rows,
-                        out_cap, res, overlap, d_seq_resident);
-    int32_t* width_out = res->width.data();
-    int64_t* out_off = res->out_off.data();
-    res->d_out = nullptr;
-    res->d_members = nullptr;
-    out_off[0] = 0;
-    if (bandwidth < 0) return fail("sarlacc_amd: negative bandwidth");
-    const int64_t nmemb = grp_off[ngroups] - grp_off[0];
-    for (int64_t i = 0; i < nmemb; ++i) {
-        const int32_t v = grp[grp_off[0] + i];
-        if (v < 1 || v > nseq) return fail("sarlacc_amd: group index %d outside 1..%lld", v, static_cast<long long>(nseq));
-    }
-    std::vector<int64_t> rel(static_cast<size_t>(nseq) + 1);
-    for (int64_t i = 0; i <= nseq; ++i) rel[i] = (nseq ? seq_off[i] : 0) - (nseq ? seq_off[0] : 0);
-    // which groups does spec v2 take
-    std::vector<int64_t> v2, v1;
-    const long long wmax = std::max(1LL, std::max(static_cast<long long>(match), static_cast<long long>(mismatch)));   // as truncated
-    double diverted_weights = 0;
-    for (int64_t g = 0; g < ngroups; ++g) {
-        const int64_t n = grp_off[g + 1] - grp_off[g];
-        int64_t mx = 0;
-        for (int64_t a = 0; a < n; ++a) { const int32_t id = grp[grp_off[g] + a]; mx = std::max<int64_t>(mx, rel[id] - rel[id - 1]); }
-        if (mx > 60000) return fail("sarlacc_amd: reads longer than 60000 bases are not supported by the MSA stage");
-        // spec v2: up to M2_MAXN reads, each short enough for 16-bit positions (a profile that outgrows 65 535 COLUMNS sends its group
-        // to spec v1 afterwards: msa2_core's gave_up)
-        // ... and with weights that fit the fields of the library records, the rows and the chain (m2_weights_fit)
-        const bool v2_shape = n <= M2_MAXN && mx + 64 <= 65535;
-        const bool fit = !v2_shape || m2_weights_fit(n, mx, wmax);
-        if (!fit) diverted_weights += 1;
-        if (v2_shape && fit) v2.push_back(g); else v1.push_back(g);
-    }
-    ctx().counts["msa_v1_fallback_weights"] = diverted_weights;
-    SL_TRY(ensure_device());
-    Context& c = ctx();
-    hipStream_t s = nullptr;
-    c.stage_reset("msa_pairwise");
-    c.stage_reset("msa_merge");
-    for (const char* nm : {"msa_host_plan_s", "msa_host_upload_alloc_s", "msa_host_pairwise_launch_s", "msa_host_rows_s", "msa_host_select_s",
-                           "msa_host_total_s"})
-        c.counts[nm] = 0;
-    const double t_run = m2_now();
-    for (const char* nm : {"msa_pairs", "msa_cells", "msa2_rows", "msa2_rows_capped", "msa2_entries_filtered", "msa2_rows_filtered",
-                           "msa2_entries_kept", "msa2_joins", "msa2_joins_chain_in_hbm", "msa2_gathers", "msa2_groups_second_pass", "msa2_batches", "msa2_cycles_rows", "msa2_cycles_chain",
-                           "msa2_cycles_walk", "msa2_cycles_renumber", "msa2_launches", "msa2_first_exit_s", "msa2_last_exit_s",
-                           "msa2_exit_s_1wave", "msa2_exit_s_4waves", "msa2_exit_s_8waves", "msa_pairs_bitvector", "msa_bitvector_tile_bytes",
-                           "msa_bitvector_split", "msa_bitvector_redone"})
-        c.counts[nm] = 0;
-    if (v2.empty())
-        return msa1_run(grp_off, grp, ngroups, seq, seq_off, nseq, match, mismatch, gap_extension, gap_opening, bandwidth, want_rows,
-                        out_cap, res, overlap, d_seq_resident);
-    const int64_t total = rel[nseq];
-    uint8_t* d_seq;
-    if (d_seq_resident) d_seq = const_cast<uint8_t*>(d_seq_resident);
-    else SL_TRY(upload("msa.seq", reinterpret_cast<const uint8_t*>(seq) + (nseq ? seq_off[0] : 0), static_cast<size_t>(total), &d_seq, s));
-    int32_t* d_mem;
-    SL_TRY(upload("msa.mem.all", grp + grp_off[0], static_cast<size_t>(nmemb), &d_mem, s));   // (msa1_run uploads its own "msa.mem")
-    res->d_members = d_mem;
-
-    std::vector<int32_t> w2;
-    std::vector<long long> o2;
-    uint8_t* d_rows2 = nullptr;
-    std::vector<size_t> gave_up;
-    SL_TRY(msa2_core(grp_off, grp, v2, d_seq, rel, match, mismatch, gap_extension, gap_opening, bandwidth, w2, o2, &d_rows2, overlap, res->code, s, &gave_up));
-    if (!gave_up.empty()) {   // alignments wider than 65 535 columns: spec v1 (the list stays in group order)
-        for (size_t q : gave_up) v1.push_back(v2[q]);
-        std::sort(v1.begin(), v1.end());
-    }
-    c.counts["msa_v1_fallback"] = static_cast<double>(v1.size());
-    c.counts["msa_v1_fallback_too_wide"] = static_cast<double>(gave_up.size());
-    // spec v1 part on a compacted group list: more than M2_MAXN reads, reads too long, or dropped by the guard
-    MsaResult r1;
-    std::vector<int64_t> g1off(v1.size() + 1, 0);
-    std::vector<int32_t> g1;
-    if (!v1.empty()) {
-        for (size_t q = 0; q < v1.size(); ++q) {
-            const int64_t g = v1[q];
-            for (int64_t k = grp_off[g]; k < grp_off[g + 1]; ++k) g1.push_back(grp[k]);
-            g1off[q + 1] = static_cast<int64_t>(g1.size());
-        }
-        r1.width.assign(v1.size(), 0);
-        r1.out_off.assign(v1.size() + 1, 0);
-        r1.code = res->code;
-        SL_TRY(msa1_run(g1off.data(), g1.data(), static_cast<int64_t>(v1.size()), seq, seq_off, nseq, match, mismatch, gap_extension,
-                        gap_opening, bandwidth, true, -1, &r1, nullptr, d_seq, true));
-    }
-    // the rows of spec v2 are in processing order, those of spec v1 in a buffer of their own: gather both into one in group order
-    std::vector<long long> src_off(static_cast<size_t>(ngroups)), dst_off(static_cast<size_t>(ngroups)), nbytes(static_cast<size_t>(ngroups));
-    std::vector<char> from1(static_cast<size_t>(ngroups), 0);
-    {
-        size_t a1 = 0, a2 = 0;
-        for (int64_t g = 0; g < ngroups; ++g) {
-            const int64_t n = grp_off[g + 1] - grp_off[g];
-            const bool in2 = a2 < v2.size() && v2[a2] == g;
-            if (a1 < v1.size() && v1[a1] == g) { width_out[g] = r1.width[a1]; src_off[g] = r1.out_off[a1]; from1[g] = 1; ++a1; }
-            else { width_out[g] = w2[a2]; src_off[g] = o2[a2]; }
-            if (in2) ++a2;
-            nbytes[g] = static_cast<long long>(width_out[g]) * n;
-            dst_off[g] = out_off[g];
-            out_off[g + 1] = out_off[g] + nbytes[g];
-        }
-    }
-    if (want_rows && out_cap >= 0 && out_cap < out_off[ngroups]) return fail("sarlacc_amd: MSA output buffer too small (%lld needed)", static_cast<long long>(out_off[ngroups]));
-    // spec v2's buffer already in group order (one batch, no group by spec v1, none that needed the second pass): it IS the result
-    bool in_place = v1.empty();
-    for (int64_t g = 0; g < ngroups && in_place; ++g) in_place = src_off[g] == dst_off[g];
-    if (in_place) {
-        SL_HIP(hipStreamSynchronize(s));
-        if (res->code.want) res->d_codes = reinterpret_cast<uint16_t*>(d_rows2);
-        else res->d_out = d_rows2;
-        m2_host_time("total", t_run);
-        return 0;
-    }
-    // (offsets and sizes so far are in cells; a cell is one character, or one 16-bit vote code)
-    const long long cs = res->code.want ? 2 : 1;
-    uint8_t* d_final;
-    SL_TRY(scratch(res->code.want ? "msa.final16" : "msa.final", static_cast<size_t>(out_off[ngroups] * cs) + 8, &d_final));
-    if (cs > 1)
-        for (int64_t g = 0; g < ngroups; ++g) { src_off[g] *= cs; dst_off[g] *= cs; nbytes[g] *= cs; }
-    // two launches, one per source buffer (groups of the other kind copy nothing)
+// msa_run's final gather into one buffer in group order: two launches, one per source buffer (groups of the other kind copy nothing)
+int msa_rows_gather(const uint8_t* src1, const uint8_t* src2, const std::vector<long long>& src_off, const std::vector<long long>& dst_off,
+                    const std::vector<long long>& nbytes, const std::vector<char>& from1, bool have1, uint8_t* d_final, hipStream_t s) {
+    const size_t ngroups = nbytes.size();
     for (int pass = 0; pass < 2; ++pass) {
         std::vector<long long> nb(nbytes);
-        for (int64_t g = 0; g < ngroups; ++g)
+        for (size_t g = 0; g < ngroups; ++g)
             if ((from1[g] != 0) != (pass == 0)) nb[g] = 0;
         long long *d_so, *d_do, *d_nb;
         SL_TRY(upload(pass == 0 ? "msa.cp.so1" : "msa.cp.so2", src_off.data(), src_off.size(), &d_so, s));
         SL_TRY(upload(pass == 0 ? "msa.cp.do1" : "msa.cp.do2", dst_off.data(), dst_off.size(), &d_do, s));
         SL_TRY(upload(pass == 0 ? "msa.cp.nb1" : "msa.cp.nb2", nb.data(), nb.size(), &d_nb, s));
-        if (pass == 0 && v1.empty()) continue;
-        const uint8_t* src1 = res->code.want ? reinterpret_cast<const uint8_t*>(r1.d_codes) : r1.d_out;
-        hipLaunchKernelGGL(k_rows_copy, dim3(static_cast<unsigned>(ngroups)), dim3(256), 0, s, pass == 0 ? src1 : d_rows2, d_so, d_final, d_do, d_nb);
+        if (pass == 0 && !have1) continue;
+        hipLaunchKernelGGL(k_rows_copy, dim3(static_cast<unsigned>(ngroups)), dim3(256), 0, s, pass == 0 ? src1 : src2, d_so, d_final, d_do, d_nb);
         SL_HIP(hipGetLastError());
     }
-    SL_HIP(hipStreamSynchronize(s));
-    if (res->code.want) res->d_codes = reinterpret_cast<uint16_t*>(d_final);
-    else res->d_out = d_final;
-    m2_host_time("total", t_run);
     return 0;
 }
 
 }  // namespace sarlacc
 
-using namespace sarlacc;
-
-extern "C" int sarlacc_set_msa_spec(int spec) {
-    if (spec != 0 && spec != 1 && spec != 2) return fail("sarlacc_amd: MSA spec must be 1 (centre-star) or 2 (consistency-based progressive), 0 = default");
-    return sarlacc::set_option("msa_spec", spec);
-}

@@ -58,7 +58,7 @@ __host__ __device__ __forceinline__ int msa_pair_band(int bandwidth, int lr, int
 }
 
 // What the launcher needs to know about a job list (band classes: up to 256 / 512 / 1024 diagonals); a caller that builds
-// the list with several threads fills it on the way (msa2.hip), otherwise the launcher walks the list itself.
+// the list with several threads fills it on the way (msa2_host.cpp), otherwise the launcher walks the list itself.
 struct MsaJobSummary {
     size_t n[3] = {0, 0, 0};
     int lr[3] = {0, 0, 0}, lc[3] = {0, 0, 0}, band[3] = {1, 1, 1};
@@ -106,7 +106,7 @@ inline int msa_pairwise_launch(const std::vector<MsaJob>& jobs, const MsaJob* d_
                                out_mode, d_ins, d_aln, d_map, d_stats, s, summary, reset_stuck);
 }
 // (reset_stuck = false: the "traceback exceeded its step bound" flag of earlier launches of the same call is kept, the
-// caller reads it once at the end -- pipelined batches, msa2.hip)
+// caller reads it once at the end -- pipelined batches, msa2_host.cpp)
 
 __device__ __forceinline__ uint8_t dna5_code(uint8_t c) {
     switch (c) {
