@@ -333,6 +333,35 @@ int sarlacc_dev_fastq_format(const uint8_t* d_seq, const uint8_t* d_qual, const 
                              const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
                              int64_t count, uint8_t* d_text, void* stream);
 
+/* Resident read batch -> unaligned BAM records in device memory: the inverse of sarlacc_dev_bam_reads_extract, with the
+ * two-step contract and the argument order of the FASTQ pair above.  Record i is an unmapped, unpaired alignment record
+ * (SAM specification section 4.2) of the L = d_off[i + 1] - d_off[i] bases and qualities of read i:
+ *     block_size (int32, not counting itself) | refID -1 | pos -1 | l_read_name | mapq 0 | bin 4680 (reg2bin(-1, 0), as
+ *     htslib writes an unplaced read) | n_cigar_op 0 | flag 4 | l_seq L | next_refID -1 | next_pos -1 | tlen 0 |
+ *     name NUL | SEQ | QUAL                                  (36 + l_read_name + (L + 1) / 2 + L bytes, no tags)
+ * SEQ holds 4-bit codes through "=ACMGRSVTWYHKDBN", high nibble first, the low nibble of an odd last byte 0; QUAL holds
+ * byte - 33; L = 0 is a record with l_seq 0.  The name is the read's name up to its first space or tab (what samtools
+ * import keeps of a FASTQ name line: a QNAME holds no blanks), '*' where nothing is left; without d_names it is
+ * READ_<first_index + i>.  What BAM cannot hold is refused by step 1, before any byte is written, as "record K: <reason>"
+ * for the lowest such record, K 1-based, within a record in this order: "read name longer than 254 bytes" (after the
+ * cut), "read name holds a byte outside '!'..'~'" (in the kept part), "base cannot be stored in BAM" (any byte that is
+ * not one of the 15 upper-case letters ACMGRSVTWYHKDBN: '=', lower case and '-' are not mapped to N, since
+ * sarlacc_dev_bam_reads_extract could not give them back), "quality byte outside Phred+33" (outside 33..126), "record
+ * larger than 2^31 - 1 bytes".
+ * Step 1 fills d_rec_off with the n + 1 offsets of the records in the whole record stream (no header in it), reports its
+ * size, and fills d_cuts (may be NULL) with 2 n sorted offsets into the same stream, the SEQ start and the QUAL start of
+ * every record: the piece boundaries for sarlacc_dev_bgzf_deflate_cuts.  Step 2 writes the bytes d_rec_off[first] ..
+ * d_rec_off[first + count] of the stream to d_out[0 ..], at any alignment of d_out.  n == 0 and count == 0 succeed
+ * without a launch.  Both calls return when the device has finished.
+ * Out of scope: tags (read groups, MM / ML), aligned records, paired flags, qualities written as the 0xff "missing"
+ * marker; the header and the BGZF container are the caller's (DeviceReads.to_bam). */
+int sarlacc_dev_bam_format_size(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
+                                const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
+                                int64_t* d_rec_off, int64_t* d_cuts, int64_t* total_bytes, void* stream);
+int sarlacc_dev_bam_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
+                           const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
+                           int64_t count, uint8_t* d_out, void* stream);
+
 /* SAM alignment records already in device memory -> ranges (sam2ranges, R/sam2ranges.R:8-95).  d_text holds
  * body lines of a SAM file (no header), LF or CRLF, blank lines skipped; first_line is the 1-based file line
  * number of its first line, used in error messages.  The caller reads the header: ref_names / ref_off (n_ref + 1
@@ -392,7 +421,11 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
  * (0 blocks, 0 bytes).  Errors: a negative size, "unknown BGZF deflate mode M", "BGZF output capacity C is below the
  * bound B".  The call returns when the device has finished; sarlacc_last_kernel_ms is the encode kernel.  Workspace:
  * one 65536-byte slot per block, 1.004 * nbytes rounded up to whole slots, and 16 bytes per block of sizes.
- * Out of scope: LZ77 matching (about 4 % on long reads against 17 % for the per-line tables), BAM output, .gzi / .csi
+ * sarlacc_dev_bgzf_deflate_cuts is the same call for bytes without lines (BAM records), except for where the pieces of
+ * (b) end: at the first position d_cuts[j] - cut_origin that lies at least 64 bytes into the piece, or at the block's
+ * end; newlines play no part.  d_cuts holds n_cuts offsets sorted ascending (NULL with n_cuts == 0); positions <= 0 or
+ * >= nbytes are ignored, and n_cuts == 0 makes mode 0 write the bytes of mode 1.
+ * Out of scope: LZ77 matching (about 4 % on long reads against 17 % for the per-line tables), .gzi / .csi
  * indexes, compressing on the host.
  * BAM (SAM specification section 4.2: the same container around binary records) -> ranges.  d_bam holds nbytes of
  * inflated BAM in device memory whose byte 0 is the start of an alignment record: the caller reads the header
@@ -442,7 +475,7 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
  * in d_off that start at 0, the names and count + 1 offsets in d_names / d_name_off (both NULL: no names).  Every
  * output may have any alignment; nothing outside those ranges is written.  count == 0 and nbytes == 0 succeed without a
  * launch.  The three calls return when the device has finished.
- * Out of scope: tags, BAM output, .bai / .csi random access, CRAM. */
+ * Out of scope: tags, .bai / .csi random access, CRAM. */
 int sarlacc_bgzf_scan(const uint8_t* buf, int64_t nbytes, int64_t max_blocks, int64_t first_block, int64_t* comp_off,
                       int64_t* text_off, int64_t* n_blocks, int64_t* used_bytes, int* last_is_eof);
 int sarlacc_dev_bgzf_inflate(const uint8_t* d_comp, const int64_t* d_comp_off, const int64_t* d_text_off, int64_t n_blocks,
@@ -450,6 +483,9 @@ int sarlacc_dev_bgzf_inflate(const uint8_t* d_comp, const int64_t* d_comp_off, c
 int sarlacc_bgzf_deflate_bound(int64_t nbytes, int64_t* n_blocks, int64_t* comp_capacity);
 int sarlacc_dev_bgzf_deflate(const uint8_t* d_text, int64_t nbytes, int mode, uint8_t* d_comp, int64_t comp_capacity,
                              int64_t* d_comp_off, int64_t* comp_bytes, void* stream);
+int sarlacc_dev_bgzf_deflate_cuts(const uint8_t* d_text, int64_t nbytes, const int64_t* d_cuts, int64_t n_cuts,
+                                  int64_t cut_origin, int mode, uint8_t* d_comp, int64_t comp_capacity,
+                                  int64_t* d_comp_off, int64_t* comp_bytes, void* stream);
 int sarlacc_dev_copy(void* d_dst, const void* d_src, int64_t bytes, void* stream);
 int sarlacc_dev_rfind_byte(const uint8_t* d_text, int64_t nbytes, int value, int64_t* pos, void* stream);
 int sarlacc_dev_bam_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_record, int at_eof, int64_t n_ref,

@@ -148,6 +148,8 @@ def _prototypes():
         "sarlacc_dev_fastq_extract": (i, [p, p, p, p, p, p, p]),
         "sarlacc_dev_fastq_format_size": (i, [p, i64, p, p, i64, p, p, p]),
         "sarlacc_dev_fastq_format": (i, [p, p, p, p, p, i64, p, i64, i64, p, p]),
+        "sarlacc_dev_bam_format_size": (i, [p, p, p, i64, p, p, i64, p, p, p, p]),
+        "sarlacc_dev_bam_format": (i, [p, p, p, p, p, i64, p, i64, i64, p, p]),
         "sarlacc_dev_sam_index": (i, [p, i64, i64, p, p, i64, p, p, p, i64, i, i64, p, p, p, p]),
         "sarlacc_dev_sam_extract": (i, [p, p, p, p, p, p, p, p, p, p]),
         "sarlacc_dev_bam_index": (i, [p, i64, i64, i, i64, p, i, i64, p, p, p, p, p]),
@@ -161,6 +163,7 @@ def _prototypes():
         "sarlacc_dev_bgzf_inflate": (i, [p, p, p, i64, i64, p, i, p]),
         "sarlacc_bgzf_deflate_bound": (i, [i64, p, p]),
         "sarlacc_dev_bgzf_deflate": (i, [p, i64, i, p, i64, p, p, p]),
+        "sarlacc_dev_bgzf_deflate_cuts": (i, [p, i64, p, i64, i64, i, p, i64, p, p, p]),
         "sarlacc_dev_copy": (i, [p, p, i64, p]),
         "sarlacc_dev_rfind_byte": (i, [p, i64, i, p, p]),
         "sarlacc_compute_lev_masked": (i, [p, p, i64, p]),

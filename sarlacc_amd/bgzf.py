@@ -9,7 +9,8 @@ not start with the gzip magic is text and takes the text path untouched.
 
 Compressed output: deflate_device turns text in device memory into BGZF blocks there (sarlacc_dev_bgzf_deflate,
 bgzf_deflate.hip), so that only compressed bytes come back; DeviceReads.to_fastq(compress=True) writes them and
-EOF_BLOCK behind them."""
+EOF_BLOCK behind them.  DeviceReads.to_bam does the same with BAM records, whose fields it hands over as the pieces
+that may get a Huffman table of their own (sarlacc_dev_bgzf_deflate_cuts)."""
 import ctypes as C
 import zlib
 
@@ -154,15 +155,27 @@ def deflate_bound(nbytes):
     return n.value, cap.value
 
 
-def deflate_device(d_text, nbytes, mode=0, out=None):
+def deflate_device(d_text, nbytes, mode=0, out=None, cuts=None, cut_origin=0):
     """Device text -> BGZF blocks in device memory (sarlacc_dev_bgzf_deflate; no end-of-file block): (DevBuffer,
     compressed bytes).  mode 0 takes per block the smallest of one Huffman table, a table per line and stored; 1 leaves
-    the per-line tables out, 2 stores.  `out` is a buffer to reuse, of at least deflate_bound(nbytes)[1] bytes."""
+    the per-line tables out, 2 stores.  `out` is a buffer to reuse, of at least deflate_bound(nbytes)[1] bytes.
+    With `cuts` the pieces that get a table of their own end at the caller's boundaries, not behind newlines
+    (sarlacc_dev_bgzf_deflate_cuts: bytes without lines, BAM records): sorted int64 offsets, either a host sequence,
+    which is uploaded, or (device buffer or address, number of cuts); position cuts[j] - cut_origin of the text."""
     from .resident import DevBuffer
     cap = deflate_bound(nbytes)[1]
     d_comp = out if out is not None else DevBuffer(max(cap, 1))
     total = C.c_int64(0)
-    check(_lib.lib().sarlacc_dev_bgzf_deflate(d_text, int(nbytes), int(mode), d_comp, d_comp.nbytes, None, C.byref(total), None))
+    if cuts is None:
+        check(_lib.lib().sarlacc_dev_bgzf_deflate(d_text, int(nbytes), int(mode), d_comp, d_comp.nbytes, None, C.byref(total), None))
+        return d_comp, total.value
+    if isinstance(cuts, tuple):
+        d_cuts, n_cuts = cuts
+    else:
+        host = np.ascontiguousarray(cuts, dtype=np.int64)
+        d_cuts, n_cuts = (DevBuffer.from_numpy(host) if host.size else None), host.size
+    check(_lib.lib().sarlacc_dev_bgzf_deflate_cuts(d_text, int(nbytes), d_cuts, int(n_cuts), int(cut_origin), int(mode), d_comp,
+                                                   d_comp.nbytes, None, C.byref(total), None))
     return d_comp, total.value
 
 

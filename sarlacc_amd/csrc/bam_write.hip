@@ -1,0 +1,399 @@
+// bam_write.hip -- resident read batch -> unaligned BAM records, on gfx950: the inverse of bam_reads.hip's k_bamr_unpack.
+//
+// Record i is an unmapped, unpaired alignment record (SAM specification section 4.2), L its bases, l_read_name the
+// bytes of its name with the NUL:
+//
+//     block_size (int32, not counting itself) | refID -1 | pos -1 | l_read_name | mapq 0 | bin 4680 | n_cigar_op 0 |
+//     flag 4 | l_seq | next_refID -1 | next_pos -1 | tlen 0 | name NUL | SEQ | QUAL          (36 + l_read_name + (L + 1) / 2 + L bytes)
+//
+// SEQ holds two 4-bit codes per byte through "=ACMGRSVTWYHKDBN", high nibble first, the low nibble of an odd last byte 0;
+// QUAL holds byte - 33; there are no tags.  The name is the read's name up to its first space or tab ('*' where nothing
+// is left), READ_<first_index + i> when the batch has no names.  The stream holds records only: the caller puts the
+// header in front and compresses (bgzf_deflate.hip, which takes the SEQ and QUAL starts this file reports as the ends
+// of its pieces).
+//
+//   k_bamw_size    one wavefront per record: the kept part of the name, then name, bases and qualities scanned 16
+//                  bytes per lane and step; the byte length of the record
+//   (rocPRIM exclusive scan: n + 1 record offsets, the last one is the size of the stream)
+//   k_bamw_cuts    SEQ start and QUAL start of every record in the stream
+//   k_bamw_format  the bytes of a contiguous record range, divided by OUTPUT bytes as k_fqw_format is: a wavefront takes
+//                  tiles of 4 KB, every lane four 16-byte pieces 1 KB apart, aligned in memory.  A tile finds its first
+//                  and last record by binary search in the record offsets, a lane searches between those two.  A piece
+//                  inside SEQ packs 32 bases read with two unaligned 16-byte loads: the letter's low five bits index a
+//                  32-entry table of codes held in eight registers (the 15 letters are distinct in those bits), read
+//                  with v_perm_b32 four letters at a time.  A piece inside QUAL is one unaligned 16-byte load.  A piece
+//                  that holds fixed fields, a name, the first or last bytes of SEQ or QUAL or a record boundary is
+//                  assembled byte by byte in the lane's registers and leaves as one 16-byte store too; only the two
+//                  ends of the range are stored byte by byte.
+//
+// No kernel waits on another workgroup and every loop is bounded by a record's own length or the range.  A batch BAM
+// cannot hold is an error return of the size pass (first_bad: atomicMin on record << 4 | code, on the failure path only,
+// as k_bamr_size reports), before a byte is written.
+//
+// Messages, "record K: <reason>", K 1-based; the lowest record wins, within a record name, SEQ, QUAL:
+//   read name longer than 254 bytes              (after the cut)
+//   read name holds a byte outside '!'..'~'      (in the kept part)
+//   base cannot be stored in BAM                 (anything but the 15 upper-case letters: '=', lower case, '-')
+//   quality byte outside Phred+33                (outside 33..126)
+//   record larger than 2^31 - 1 bytes
+// Out of scope: tags, aligned records, paired flags, qualities written as the 0xff "missing" marker.
+#include "common.hpp"
+#include "devprim.hpp"
+
+#include "../../include/sarlacc_amd.h"
+
+#include <algorithm>
+
+namespace sarlacc {
+namespace {
+
+enum { BAMW_NAME_LONG = 1, BAMW_NAME_BYTE = 2, BAMW_BASE = 3, BAMW_QUAL = 4, BAMW_SIZE = 5 };
+
+constexpr int BW_THREADS = 256;
+constexpr int BW_PIECES = 4;                      // 16-byte pieces per lane and tile
+constexpr int BW_TILE = 64 * 16 * BW_PIECES;      // bytes of the stream per wavefront and step
+constexpr int BW_FIXED = 36;                      // block_size and the fixed fields
+constexpr int BW_NAME_PREFIX = 5;                 // "READ_"
+constexpr int BW_NAME_MAX = 254;                  // l_read_name is a byte and counts the NUL
+constexpr uint32_t BW_BIN = 4680;                 // reg2bin(-1, 0)
+constexpr uint32_t BW_FLAG = 4;                   // unmapped
+
+// code of the letter whose low five bits are i (0: no letter)
+constexpr uint32_t bw_code_of(int i) {
+    const char* letters = "=ACMGRSVTWYHKDBN";
+    for (int c = 1; c < 16; ++c)
+        if ((letters[c] & 31) == i) return static_cast<uint32_t>(c);
+    return 0;
+}
+constexpr uint32_t bw_table_word(int k) {
+    return bw_code_of(4 * k) | (bw_code_of(4 * k + 1) << 8) | (bw_code_of(4 * k + 2) << 16) | (bw_code_of(4 * k + 3) << 24);
+}
+// the table, four entries per register
+constexpr uint32_t BW_T0 = bw_table_word(0), BW_T1 = bw_table_word(1), BW_T2 = bw_table_word(2), BW_T3 = bw_table_word(3),
+                   BW_T4 = bw_table_word(4), BW_T5 = bw_table_word(5), BW_T6 = bw_table_word(6), BW_T7 = bw_table_word(7);
+
+typedef uint32_t __attribute__((ext_vector_type(4))) bw_u32x4;
+typedef bw_u32x4 __attribute__((aligned(1))) bw_u32x4_unaligned;
+
+__device__ __forceinline__ int bw_decimal_width(unsigned long long v) {
+    int w = 1;
+    while (v >= 10) { v /= 10; ++w; }
+    return w;
+}
+
+// codes of the four letters of w, byte by byte; 0 where the low five bits are those of no letter
+__device__ __forceinline__ uint32_t codes4(uint32_t w) {
+    const uint32_t sel = w & 0x07070707u;
+    const uint32_t p0 = __builtin_amdgcn_perm(BW_T1, BW_T0, sel), p1 = __builtin_amdgcn_perm(BW_T3, BW_T2, sel);
+    const uint32_t p2 = __builtin_amdgcn_perm(BW_T5, BW_T4, sel), p3 = __builtin_amdgcn_perm(BW_T7, BW_T6, sel);
+    const uint32_t m3 = ((w >> 3) & 0x01010101u) * 0xffu, m4 = ((w >> 4) & 0x01010101u) * 0xffu;
+    const uint32_t lo = (p1 & m3) | (p0 & ~m3), hi = (p3 & m3) | (p2 & ~m3);
+    return (hi & m4) | (lo & ~m4);
+}
+
+// non-zero iff one of the four bytes of w is not one of the 15 letters (they lie in 0x41 .. 0x59)
+__device__ __forceinline__ uint32_t not_base4(uint32_t w) {
+    const uint32_t c = codes4(w);
+    return ((w & 0xe0e0e0e0u) ^ 0x40404040u) | ((c - 0x01010101u) & ~c & 0x80808080u);
+}
+
+// non-zero iff one of the four bytes of w lies outside 33 .. 126
+__device__ __forceinline__ uint32_t not_phred4(uint32_t w) {
+    const uint32_t low = w & 0x7f7f7f7fu;
+    return (w | ~(low + 0x5f5f5f5fu) | (low + 0x01010101u)) & 0x80808080u;
+}
+
+// two SEQ bytes of the four codes of c: the first code in the high nibble
+__device__ __forceinline__ uint32_t pack4(uint32_t c) {
+    const uint32_t x = (c << 4) | (c >> 8);
+    return (x & 0xffu) | ((x >> 8) & 0xff00u);
+}
+
+// whether one of the n bytes at p is no base (SEQ) / no Phred+33 quality (!SEQ): the whole wavefront, 16 bytes per lane
+// and step, the last bytes one by one
+template <bool SEQ>
+__device__ __forceinline__ bool wave_any_bad(const uint8_t* p, long long n, int lane) {
+    bool hit = false;
+    for (long long q = 16LL * lane; q < n; q += 16 * 64) {
+        if (q + 16 <= n) {
+            const bw_u32x4 v = *reinterpret_cast<const bw_u32x4_unaligned*>(p + q);
+            hit |= SEQ ? (not_base4(v.x) | not_base4(v.y) | not_base4(v.z) | not_base4(v.w)) != 0
+                       : (not_phred4(v.x) | not_phred4(v.y) | not_phred4(v.z) | not_phred4(v.w)) != 0;
+        } else {
+            for (long long j = q; j < n; ++j) hit |= SEQ ? not_base4(p[j] | 0x41414100u) != 0 : p[j] < 33 || p[j] > 126;
+        }
+    }
+    return __ballot(hit) != 0;
+}
+
+__device__ __forceinline__ long long wave_min(long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long t = __shfl_xor(v, o);
+        v = t < v ? t : v;
+    }
+    return v;
+}
+
+// *blank: the first space or tab among the n bytes at p; *other: the first other byte outside '!'..'~' (n: none)
+__device__ __forceinline__ void wave_name_scan(const uint8_t* p, long long n, int lane, long long* blank, long long* other) {
+    long long fb = n, fo = n;
+    for (long long q = 16LL * lane; q < n; q += 16 * 64) {
+        const long long e = q + 16 < n ? q + 16 : n;
+        for (long long j = q; j < e; ++j) {
+            const uint8_t c = p[j];
+            if (c == ' ' || c == '\t') fb = j < fb ? j : fb;
+            else if (c < '!' || c > '~') fo = j < fo ? j : fo;
+        }
+    }
+    *blank = wave_min(fb);
+    *other = wave_min(fo);
+}
+
+// len[r] = bytes of record r, 0 for a refused one (len[n] = 0 for the scan); first_bad: lowest refused record << 4 | why
+__global__ void __launch_bounds__(BW_THREADS) k_bamw_size(const uint8_t* seq, const uint8_t* qual, const int64_t* off,
+                                                          const uint8_t* names, const int64_t* name_off, long long first_index,
+                                                          long long n, long long* len, unsigned long long* first_bad) {
+    const int lane = threadIdx.x & 63;
+    const long long nwaves = static_cast<long long>(gridDim.x) * (BW_THREADS / 64);
+    if (blockIdx.x == 0 && threadIdx.x == 0) len[n] = 0;
+    for (long long r = static_cast<long long>(blockIdx.x) * (BW_THREADS / 64) + (threadIdx.x >> 6); r < n; r += nwaves) {
+        const long long so = off[r], L = off[r + 1] - so;
+        long long l_name;
+        int bad = 0;
+        if (names) {
+            const long long no = name_off[r];
+            long long kept, other;
+            wave_name_scan(names + no, name_off[r + 1] - no, lane, &kept, &other);
+            if (kept > BW_NAME_MAX) bad = BAMW_NAME_LONG;
+            else if (other < kept) bad = BAMW_NAME_BYTE;
+            l_name = (kept > 0 ? kept : 1) + 1;      // '*' for an empty name
+        } else {
+            l_name = BW_NAME_PREFIX + bw_decimal_width(static_cast<unsigned long long>(first_index + r)) + 1;
+        }
+        if (!bad && wave_any_bad<true>(seq + so, L, lane)) bad = BAMW_BASE;
+        if (!bad && wave_any_bad<false>(qual + so, L, lane)) bad = BAMW_QUAL;
+        const long long total = BW_FIXED + l_name + (L + 1) / 2 + L;
+        if (!bad && total > 0x7fffffffLL) bad = BAMW_SIZE;
+        if (lane == 0) {
+            len[r] = bad ? 0 : total;
+            if (bad) atomicMin(first_bad, (static_cast<unsigned long long>(r) << 4) | static_cast<unsigned>(bad));
+        }
+    }
+}
+
+// cuts[2 r], cuts[2 r + 1] = where SEQ and QUAL of record r start in the stream
+__global__ void __launch_bounds__(256) k_bamw_cuts(const int64_t* off, const int64_t* rec_off, long long n, int64_t* cuts) {
+    const long long r = blockIdx.x * 256LL + threadIdx.x;
+    if (r >= n) return;
+    const long long L = off[r + 1] - off[r], ql = rec_off[r + 1] - L;
+    cuts[2 * r] = ql - (L + 1) / 2;
+    cuts[2 * r + 1] = ql;
+}
+
+// what a lane knows about the record it is writing
+struct BwRec {
+    long long r = -1, start = 0, len = 0;    // record, its first byte in the whole stream, its length
+    long long so = 0, sl = 0, no = 0;        // sequence / quality offset and length, name offset
+    int l_name = 0;                          // bytes of the name with its NUL
+    bool star = false;                       // nothing of the name is kept: '*'
+};
+
+struct BwSource {
+    const uint8_t* seq; const uint8_t* qual; const int64_t* off;
+    const uint8_t* names; const int64_t* name_off; long long first_index;
+    const int64_t* rec_off;
+
+    __device__ __forceinline__ void load(BwRec& R, long long r) const {
+        R.r = r;
+        R.start = rec_off[r];
+        R.len = rec_off[r + 1] - R.start;
+        R.so = off[r];
+        R.sl = off[r + 1] - R.so;
+        R.l_name = static_cast<int>(R.len - BW_FIXED - (R.sl + 1) / 2 - R.sl);
+        R.star = false;
+        if (names) {
+            R.no = name_off[r];
+            // one byte kept: the name's own first byte, or '*' where that is a blank or there is none
+            if (R.l_name == 2) R.star = name_off[r + 1] == R.no || names[R.no] == ' ' || names[R.no] == '\t';
+        }
+    }
+
+    // character k of record R's default name
+    __device__ __forceinline__ uint8_t default_name(const BwRec& R, int k) const {
+        if (k < BW_NAME_PREFIX) return static_cast<uint8_t>("READ_"[k]);
+        unsigned long long v = static_cast<unsigned long long>(first_index + R.r);
+        for (int d = R.l_name - 2 - k; d > 0; --d) v /= 10;   // digit k - 5 of l_name - 6, from the left
+        return static_cast<uint8_t>('0' + v % 10);
+    }
+
+    // byte q of record R
+    __device__ __forceinline__ uint8_t byte_at(const BwRec& R, long long q) const {
+        if (q < BW_FIXED) {
+            const int f = static_cast<int>(q >> 2);
+            const uint32_t v = f == 0 ? static_cast<uint32_t>(R.len - 4)
+                             : f == 3 ? static_cast<uint32_t>(R.l_name) | (BW_BIN << 16)      // l_read_name, mapq 0, bin
+                             : f == 4 ? BW_FLAG << 16                                          // n_cigar_op 0, flag
+                             : f == 5 ? static_cast<uint32_t>(R.sl)
+                             : f == 8 ? 0u : 0xffffffffu;                                      // tlen; refID, pos, next_refID, next_pos
+            return static_cast<uint8_t>(v >> (8 * (q & 3)));
+        }
+        q -= BW_FIXED;
+        if (q < R.l_name) {
+            if (q == R.l_name - 1) return 0;
+            if (!names) return default_name(R, static_cast<int>(q));
+            return R.star ? static_cast<uint8_t>('*') : names[R.no + q];
+        }
+        q -= R.l_name;
+        const long long nseq = (R.sl + 1) / 2;
+        if (q < nseq) {
+            uint32_t c = (codes4(seq[R.so + 2 * q]) & 15u) << 4;
+            if (2 * q + 1 < R.sl) c |= codes4(seq[R.so + 2 * q + 1]) & 15u;
+            return static_cast<uint8_t>(c);
+        }
+        return static_cast<uint8_t>(qual[R.so + (q - nseq)] - 33);
+    }
+};
+
+// out[0 .. ) = bytes rec_off[first] .. rec_off[first + count] of the whole stream
+__global__ void __launch_bounds__(BW_THREADS) k_bamw_format(BwSource S, long long first, long long count, uint8_t* out) {
+    const long long base = S.rec_off[first], nbytes = S.rec_off[first + count] - base;
+    const int mis = static_cast<int>(reinterpret_cast<uintptr_t>(out) & 15);   // pieces are aligned in memory, not in the stream
+    const long long ntiles = (nbytes + mis + BW_TILE - 1) / BW_TILE;
+    const int lane = threadIdx.x & 63;
+    const long long wave = blockIdx.x * static_cast<long long>(BW_THREADS / 64) + (threadIdx.x >> 6);
+    const long long nwaves = static_cast<long long>(gridDim.x) * (BW_THREADS / 64);
+    BwRec R;
+    for (long long tile = wave; tile < ntiles; tile += nwaves) {
+        const long long t0 = tile * BW_TILE - mis;
+        const long long tile_lo = t0 > 0 ? t0 : 0, tile_hi = (t0 + BW_TILE < nbytes ? t0 + BW_TILE : nbytes) - 1;
+        // first and last record of the tile (the same in every lane)
+        const long long r_lo = last_not_above(S.rec_off, first, first + count, base + tile_lo);
+        const long long r_hi = S.rec_off[r_lo + 1] > base + tile_hi ? r_lo
+                                                                   : last_not_above(S.rec_off, r_lo, first + count, base + tile_hi);
+#pragma unroll 1
+        for (int k = 0; k < BW_PIECES; ++k) {
+            const long long p0 = t0 + (k * 64 + lane) * 16;
+            const long long v0 = p0 > 0 ? p0 : 0, v1 = p0 + 16 < nbytes ? p0 + 16 : nbytes;   // head and tail of the range
+            if (v0 >= v1) continue;
+            const long long r = last_not_above(S.rec_off, r_lo, r_hi + 1, base + v0);
+            if (r != R.r) S.load(R, r);
+            long long q = base + v0 - R.start;
+            const bool whole = v1 - v0 == 16;
+            const long long sq = BW_FIXED + R.l_name, ql = sq + (R.sl + 1) / 2;
+            if (whole && q >= ql && q + 16 <= R.len) {          // sixteen qualities
+                bw_u32x4 v = *reinterpret_cast<const bw_u32x4_unaligned*>(S.qual + R.so + (q - ql));
+                v -= 0x21212121u;                               // no borrow between the bytes: the size pass refused values below 33
+                *reinterpret_cast<bw_u32x4*>(out + p0) = v;
+                continue;
+            }
+            if (whole && q >= sq && 2 * (q - sq) + 32 <= R.sl) {   // thirty-two bases
+                const uint8_t* b = S.seq + R.so + 2 * (q - sq);
+                const bw_u32x4 a = *reinterpret_cast<const bw_u32x4_unaligned*>(b);
+                const bw_u32x4 c = *reinterpret_cast<const bw_u32x4_unaligned*>(b + 16);
+                bw_u32x4 v;
+                v.x = pack4(codes4(a.x)) | (pack4(codes4(a.y)) << 16);
+                v.y = pack4(codes4(a.z)) | (pack4(codes4(a.w)) << 16);
+                v.z = pack4(codes4(c.x)) | (pack4(codes4(c.y)) << 16);
+                v.w = pack4(codes4(c.z)) | (pack4(codes4(c.w)) << 16);
+                *reinterpret_cast<bw_u32x4*>(out + p0) = v;
+                continue;
+            }
+            // fixed fields, names, the ends of SEQ and QUAL, of records and of the range: byte by byte into the registers
+            const int d0 = static_cast<int>(v0 - p0), d1 = static_cast<int>(v1 - p0);
+            uint64_t lo = 0, hi = 0;
+#pragma unroll 1
+            for (int d = d0; d < d1; ++d, ++q) {
+                if (q >= R.len) { q = 0; S.load(R, R.r + 1); }     // (inside the range: d < d1)
+                const uint64_t c = S.byte_at(R, q);
+                if (d < 8) lo |= c << (8 * d); else hi |= c << (8 * (d - 8));
+            }
+            if (whole) {
+                bw_u32x4 v;
+                v.x = static_cast<uint32_t>(lo); v.y = static_cast<uint32_t>(lo >> 32);
+                v.z = static_cast<uint32_t>(hi); v.w = static_cast<uint32_t>(hi >> 32);
+                *reinterpret_cast<bw_u32x4*>(out + p0) = v;
+            } else {
+#pragma unroll 1
+                for (int d = d0; d < d1; ++d) out[p0 + d] = static_cast<uint8_t>((d < 8 ? lo : hi) >> (8 * (d & 7)));
+            }
+        }
+    }
+}
+
+}  // namespace
+}  // namespace sarlacc
+
+using namespace sarlacc;
+
+extern "C" {
+
+int sarlacc_dev_bam_format_size(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
+                                const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
+                                int64_t* d_rec_off, int64_t* d_cuts, int64_t* total_bytes, void* stream) {
+    if (n < 0 || first_index < 0 || !total_bytes) return fail("sarlacc_amd: bad BAM format request");
+    if ((d_names == nullptr) != (d_name_off == nullptr)) return fail("sarlacc_amd: read names and their offsets go together");
+    SL_TRY(ensure_device());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    *total_bytes = 0;
+    if (n == 0) {
+        SL_HIP(hipMemsetAsync(d_rec_off, 0, sizeof(int64_t), s));
+        SL_HIP(hipStreamSynchronize(s));
+        return 0;
+    }
+    Context& c = ctx();
+    long long* d_len; unsigned long long* d_bad;
+    SL_TRY(scratch("bamw.len", static_cast<size_t>(n) + 1, &d_len));
+    SL_TRY(scratch("bamw.bad", 1, &d_bad));
+    SL_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), s));
+    c.stage_reset("bam_format_size");
+    SL_TRY(c.stage_begin("bam_format_size", s));
+    const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(n, BW_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
+    hipLaunchKernelGGL(k_bamw_size, dim3(grid), dim3(BW_THREADS), 0, s, d_seq, d_qual, d_off, d_names, d_name_off,
+                       static_cast<long long>(first_index), static_cast<long long>(n), d_len, d_bad);
+    SL_HIP(hipGetLastError());
+    SL_TRY(exclusive_scan("bamw.scan", d_len, d_rec_off, static_cast<size_t>(n) + 1, s));
+    if (d_cuts) {
+        hipLaunchKernelGGL(k_bamw_cuts, dim3(nblk(n, 256)), dim3(256), 0, s, d_off, d_rec_off, static_cast<long long>(n), d_cuts);
+        SL_HIP(hipGetLastError());
+    }
+    SL_TRY(c.stage_end("bam_format_size", s));
+    unsigned long long bad = 0;
+    int64_t total = 0;
+    SL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipMemcpyAsync(&total, d_rec_off + n, sizeof total, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipStreamSynchronize(s));
+    if (bad != ~0ull) {
+        const long long k = static_cast<long long>(bad >> 4) + 1;
+        switch (bad & 15u) {
+            case BAMW_NAME_LONG: return fail("record %lld: read name longer than 254 bytes", k);
+            case BAMW_NAME_BYTE: return fail("record %lld: read name holds a byte outside '!'..'~'", k);
+            case BAMW_BASE: return fail("record %lld: base cannot be stored in BAM", k);
+            case BAMW_QUAL: return fail("record %lld: quality byte outside Phred+33", k);
+            default: return fail("record %lld: record larger than 2^31 - 1 bytes", k);
+        }
+    }
+    *total_bytes = total;
+    return 0;
+}
+
+int sarlacc_dev_bam_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
+                           const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
+                           int64_t count, uint8_t* d_out, void* stream) {
+    if (first < 0 || count < 0 || first_index < 0) return fail("sarlacc_amd: bad BAM format request");
+    if ((d_names == nullptr) != (d_name_off == nullptr)) return fail("sarlacc_amd: read names and their offsets go together");
+    if (count == 0) return 0;
+    SL_TRY(ensure_device());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Context& c = ctx();
+    const BwSource src{d_seq, d_qual, d_off, d_names, d_name_off, static_cast<long long>(first_index), d_rec_off};
+    // the size of the range is known on the device only: a resident grid whose wavefronts stride over the tiles
+    c.stage_reset("bam_format");
+    SL_TRY(c.stage_begin("bam_format", s));
+    hipLaunchKernelGGL(k_bamw_format, dim3(static_cast<unsigned>(c.num_cu) * 8), dim3(BW_THREADS), 0, s, src,
+                       static_cast<long long>(first), static_cast<long long>(count), d_out);
+    SL_HIP(hipGetLastError());
+    SL_TRY(c.stage_end("bam_format", s));
+    SL_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+}

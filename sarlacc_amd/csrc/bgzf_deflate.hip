@@ -18,7 +18,9 @@
 //   (b) one dynamic-Huffman deflate block per PIECE.  A piece ends behind a newline (byte 10) or at the block's end;
 //       a newline that would close a piece of fewer than 64 bytes does not close it, so "+\n" goes with the quality
 //       line behind it and a short name line with its sequence.  A line that began in the previous block is simply
-//       the block's first piece.
+//       the block's first piece.  Bytes without lines (BAM records, bam_write.hip) come with the caller's own CUTS
+//       (sarlacc_dev_bgzf_deflate_cuts): a piece then ends at the first cut that lies at least 64 bytes into it, found
+//       by a binary search in the sorted cuts, the same in every lane; newlines play no part.
 //   (c) one stored deflate block: the floor for incompressible bytes, and why everything fits in a slot
 // (b) needs no state per line: the pieces are encoded one after the other straight into the slot, and the attempt is
 // given up before the piece whose bits would bring the running total to the smaller of (a) and (c) -- so 32640 lines
@@ -44,7 +46,7 @@
 // 3 + 14 + 57 + 258 * 7 bits after a full flush.  No spin-wait, no dependence between workgroups, no printf/assert,
 // no racing stores: the same text and mode give the same bytes.
 //
-// Out of scope: LZ77 matching (the measured gain on long reads is the 4 % above: a follow-up of its own), BAM output,
+// Out of scope: LZ77 matching (the measured gain on long reads is the 4 % above: a follow-up of its own),
 // .gzi / .csi indexes, compressing on the host.
 #include "common.hpp"
 #include "crc32.hpp"
@@ -352,9 +354,13 @@ __device__ __forceinline__ void reset_stream(DfShared& sh, DfOut& o, int lane) {
     o.pos = (18 - DF_ORIGIN) * 8;
 }
 
-// mode: 0 = smallest of (a), (b), (c); 1 = (a) or (c); 2 = (c)
+// mode: 0 = smallest of (a), (b), (c); 1 = (a) or (c); 2 = (c).  CUTS: the pieces of (b) end at the caller's cuts
+// (cuts[j] - cut_origin is a position in the whole text), not behind newlines.
+template <bool CUTS>
 __global__ void __launch_bounds__(64) k_bgzf_deflate(const uint8_t* __restrict__ text_all, long long nbytes, long long nblocks,
-                                                     int mode, uint8_t* __restrict__ slots, int64_t* __restrict__ size) {
+                                                     int mode, const int64_t* __restrict__ cuts, long long n_cuts,
+                                                     long long cut_origin, uint8_t* __restrict__ slots,
+                                                     int64_t* __restrict__ size) {
     __shared__ DfShared sh;
     const long long k = blockIdx.x;
     if (k >= nblocks) return;
@@ -391,12 +397,26 @@ __global__ void __launch_bounds__(64) k_bgzf_deflate(const uint8_t* __restrict__
         bool won = true;
         int b = 0;
         while (b < n) {
-            // the piece ends behind the first newline at b + DF_MIN_PIECE - 1 or later
             int e = n;
-            for (int i0 = b + DF_MIN_PIECE - 1; i0 < n; i0 += 64) {
-                const int i = i0 + lane;
-                const unsigned long long nl = __ballot(i < n && text[i] == 10);
-                if (nl) { e = i0 + __ffsll(static_cast<long long>(nl)); break; }
+            if constexpr (CUTS) {
+                // the piece ends at the first cut at b + DF_MIN_PIECE or later (the same search in every lane)
+                const long long want = cut_origin + k * DF_BLOCK + b + DF_MIN_PIECE;
+                long long lo = 0, hi = n_cuts;      // cuts[j] < want for j < lo, >= want for j >= hi
+                while (lo < hi) {
+                    const long long mid = (lo + hi) >> 1;
+                    if (cuts[mid] < want) lo = mid + 1; else hi = mid;
+                }
+                if (lo < n_cuts) {
+                    const long long at = cuts[lo] - cut_origin - k * DF_BLOCK;
+                    if (at < n) e = static_cast<int>(at);
+                }
+            } else {
+                // the piece ends behind the first newline at b + DF_MIN_PIECE - 1 or later
+                for (int i0 = b + DF_MIN_PIECE - 1; i0 < n; i0 += 64) {
+                    const int i = i0 + lane;
+                    const unsigned long long nl = __ballot(i < n && text[i] == 10);
+                    if (nl) { e = i0 + __ffsll(static_cast<long long>(nl)); break; }
+                }
             }
             const int bits = prepare_piece(sh, text, b, e, &hclen, &nruns, lane);
             if (out.pos - start_pos + bits >= best) { won = false; break; }
@@ -459,14 +479,7 @@ __global__ void __launch_bounds__(256) k_bgzf_pack(const uint8_t* __restrict__ s
     }
 }
 
-}  // namespace
-}  // namespace sarlacc
-
-using namespace sarlacc;
-
-extern "C" {
-
-int sarlacc_bgzf_deflate_bound(int64_t nbytes, int64_t* n_blocks, int64_t* comp_capacity) {
+int bgzf_deflate_bound(int64_t nbytes, int64_t* n_blocks, int64_t* comp_capacity) {
     if (nbytes < 0) return fail("sarlacc_amd: negative text size");
     const int64_t n = (nbytes + DF_BLOCK - 1) / DF_BLOCK;
     if (n_blocks) *n_blocks = n;
@@ -474,18 +487,19 @@ int sarlacc_bgzf_deflate_bound(int64_t nbytes, int64_t* n_blocks, int64_t* comp_
     return 0;
 }
 
-int sarlacc_dev_bgzf_deflate(const uint8_t* d_text, int64_t nbytes, int mode, uint8_t* d_comp, int64_t comp_capacity,
-                             int64_t* d_comp_off, int64_t* comp_bytes, void* stream) {
+// both entry points; use_cuts: the pieces end at d_cuts (which may be NULL for n_cuts == 0), not behind newlines
+int bgzf_deflate(const uint8_t* d_text, int64_t nbytes, bool use_cuts, const int64_t* d_cuts, int64_t n_cuts, int64_t cut_origin,
+                 int mode, uint8_t* d_comp, int64_t comp_capacity, int64_t* d_comp_off, int64_t* comp_bytes, hipStream_t s) {
     int64_t n_blocks = 0, need = 0;
-    SL_TRY(sarlacc_bgzf_deflate_bound(nbytes, &n_blocks, &need));
+    SL_TRY(bgzf_deflate_bound(nbytes, &n_blocks, &need));
     if (mode < 0 || mode > 2) return fail("sarlacc_amd: unknown BGZF deflate mode %d", mode);
+    if (n_cuts < 0 || (n_cuts > 0 && !d_cuts)) return fail("sarlacc_amd: bad BGZF deflate cuts");
     if (comp_capacity < need)
         return fail("sarlacc_amd: BGZF output capacity %lld is below the bound %lld", static_cast<long long>(comp_capacity),
                     static_cast<long long>(need));
     if (!comp_bytes) return fail("sarlacc_amd: bad BGZF deflate request");
     *comp_bytes = 0;
     SL_TRY(ensure_device());
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (nbytes == 0) {
         if (d_comp_off) {
             SL_HIP(hipMemsetAsync(d_comp_off, 0, sizeof(int64_t), s));
@@ -501,8 +515,9 @@ int sarlacc_dev_bgzf_deflate(const uint8_t* d_text, int64_t nbytes, int mode, ui
     SL_HIP(hipMemsetAsync(d_size + n_blocks, 0, sizeof(int64_t), s));
     Context& c = ctx();
     SL_HIP(hipEventRecord(c.ev_start, s));
-    hipLaunchKernelGGL(k_bgzf_deflate, dim3(static_cast<unsigned>(n_blocks)), dim3(64), 0, s, d_text, static_cast<long long>(nbytes),
-                       static_cast<long long>(n_blocks), mode, d_slots, d_size);
+    const auto kernel = use_cuts ? k_bgzf_deflate<true> : k_bgzf_deflate<false>;
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_blocks)), dim3(64), 0, s, d_text, static_cast<long long>(nbytes), static_cast<long long>(n_blocks), mode, d_cuts,
+                       static_cast<long long>(n_cuts), static_cast<long long>(cut_origin), d_slots, d_size);
     SL_HIP(hipGetLastError());
     SL_HIP(hipEventRecord(c.ev_stop, s));
     c.timed = true;
@@ -515,5 +530,29 @@ int sarlacc_dev_bgzf_deflate(const uint8_t* d_text, int64_t nbytes, int mode, ui
     SL_HIP(hipStreamSynchronize(s));
     *comp_bytes = total;
     return 0;
+}
+
+}  // namespace
+}  // namespace sarlacc
+
+using namespace sarlacc;
+
+extern "C" {
+
+int sarlacc_bgzf_deflate_bound(int64_t nbytes, int64_t* n_blocks, int64_t* comp_capacity) {
+    return bgzf_deflate_bound(nbytes, n_blocks, comp_capacity);
+}
+
+int sarlacc_dev_bgzf_deflate(const uint8_t* d_text, int64_t nbytes, int mode, uint8_t* d_comp, int64_t comp_capacity,
+                             int64_t* d_comp_off, int64_t* comp_bytes, void* stream) {
+    return bgzf_deflate(d_text, nbytes, false, nullptr, 0, 0, mode, d_comp, comp_capacity, d_comp_off, comp_bytes,
+                        static_cast<hipStream_t>(stream));
+}
+
+int sarlacc_dev_bgzf_deflate_cuts(const uint8_t* d_text, int64_t nbytes, const int64_t* d_cuts, int64_t n_cuts,
+                                  int64_t cut_origin, int mode, uint8_t* d_comp, int64_t comp_capacity,
+                                  int64_t* d_comp_off, int64_t* comp_bytes, void* stream) {
+    return bgzf_deflate(d_text, nbytes, true, d_cuts, n_cuts, cut_origin, mode, d_comp, comp_capacity, d_comp_off, comp_bytes,
+                        static_cast<hipStream_t>(stream));
 }
 }

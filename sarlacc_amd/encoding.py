@@ -63,6 +63,15 @@ def encoding_for_qual_type(qual_type="phred"):
     return hits[0], {"phred": phred_encoding, "solexa": solexa_encoding, "illumina": illumina_encoding}[hits[0]]()
 
 
+def encoding_name(enc):
+    """'phred', 'solexa' or 'illumina' for the table of that quality class, otherwise a description of the table."""
+    for name, make in (("phred", phred_encoding), ("solexa", solexa_encoding), ("illumina", illumina_encoding)):
+        ref = make()
+        if enc.names == ref.names and np.array_equal(enc.errors, ref.errors):
+            return name
+    return "a custom table of %d values from byte %d on" % (len(enc), enc.names[0])
+
+
 def as_encoding(enc):
     if isinstance(enc, Encoding):
         return enc

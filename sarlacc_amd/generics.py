@@ -101,6 +101,18 @@ def write_fastq(path, reads, append=False, compress=False):
             fh.write(b"@" + name.encode() + b"\n" + s.encode() + b"\n+\n" + q.encode() + b"\n")
 
 
+def write_bam(path, reads, header=None):
+    """Reads -> unaligned BAM (DeviceReads.to_bam, whose byte count is returned): records packed and deflated on the
+    device; host Reads are uploaded for it, as write_fastq(compress=True) does.  Names are cut at their first space or
+    tab (READ_<i> where there are none); a batch whose encoding is not Phred+33 is refused."""
+    from .resident import DeviceReads
+    if isinstance(reads, DeviceReads):
+        return reads.to_bam(path, header=header)
+    dev = DeviceReads.upload(reads)
+    dev.names = list(reads.names) if reads.names else None
+    return dev.to_bam(path, header=header)
+
+
 # ---------------------------------------------------------------------------
 # adaptorAlign (R/adaptorAlign.R)
 

@@ -50,6 +50,19 @@ class DevBuffer:
             pass
 
 
+def _record_ranges(ro, block_bytes):
+    """The record ranges [(first, last)] a writer formats at a time, from the n + 1 record offsets `ro`: the largest run
+    of whole records whose bytes fit in `block_bytes` (None: everything), a single record larger than that in a range of
+    its own size."""
+    n = len(ro) - 1
+    ranges, first = [], 0
+    while first < n:
+        last = n if block_bytes is None else max(int(np.searchsorted(ro, ro[first] + int(block_bytes), side="right")) - 1, first + 1)
+        ranges.append((first, last))
+        first = last
+    return ranges
+
+
 class DeviceReads:
     """seq / qual / offsets in HBM + the host copy of the offsets."""
 
@@ -309,12 +322,7 @@ class DeviceReads:
             name_len = 6 + np.searchsorted(10 ** np.arange(1, 19, dtype=np.int64), np.arange(1, n + 1, dtype=np.int64), side="right")
         ro = np.zeros(n + 1, np.int64)
         np.cumsum(name_len + 2 * np.diff(self.off_host) + 6, out=ro[1:])
-        ranges, first = [], 0
-        while first < n:
-            last = n if block_bytes is None else max(int(np.searchsorted(ro, ro[first] + int(block_bytes), side="right")) - 1, first + 1)
-            ranges.append((first, last))
-            first = last
-        return names, noff, rec_off, ro, ranges
+        return names, noff, rec_off, ro, _record_ranges(ro, block_bytes)
 
     def _fastq_blocks(self, plan):
         """Generator over the blocks of a _fastq_plan, formatted on the device (sarlacc_dev_fastq_format): each a uint8
@@ -384,6 +392,67 @@ class DeviceReads:
                 fh.write(blk)
                 written += blk.size
         return written
+
+    def _bam_plan(self, block_bytes):
+        """The size pass of the device BAM writer (sarlacc_dev_bam_format_size; refuses what BAM cannot hold) and the
+        record ranges of _record_ranges over the record offsets it leaves, which come to the host: the kept part of a
+        name is decided on the device.  (names, name offsets, record offsets, cuts) stay on the device."""
+        n = len(self)
+        ss = self._name_set()
+        names = noff = None
+        if ss is not None:
+            names, noff = DevBuffer.from_numpy(ss.chars if ss.chars.size else np.zeros(1, np.uint8)), DevBuffer.from_numpy(ss.off)
+        rec_off, cuts, total = DevBuffer(8 * (n + 1)), DevBuffer(max(16 * n, 8)), C.c_int64(0)
+        check(_lib.lib().sarlacc_dev_bam_format_size(self.seq, self.qual, self.off, n, names, noff, 1, rec_off, cuts,
+                                                     C.byref(total), None))
+        ro = rec_off.to_numpy(np.int64, n + 1)
+        return names, noff, rec_off, cuts, ro, _record_ranges(ro, block_bytes)
+
+    def to_bam(self, path, header=None, block_bytes=256 << 20):
+        """Writes the batch to `path` as unaligned BAM (uBAM: what basecallers write and every long-read mapper and
+        samtools take; from_bam reads it back) and returns the bytes written.  Record i is an unmapped, unpaired record
+        (flag 4, no reference, no CIGAR, no tags) of read i: SEQ packed and QUAL turned into Phred values on the device
+        (sarlacc_dev_bam_format).  Its name is the read's name up to the first space or tab, as samtools import keeps it
+        ('*' where nothing is left; READ_1, READ_2, ... without `.names`).  The records are formatted in ranges of whole
+        records of at most `block_bytes`, as to_fastq plans its blocks; every range is deflated where it lies into BGZF
+        blocks of its own (bgzf.deflate_device with the SEQ and QUAL starts as piece boundaries, so packed bases and
+        qualities get a Huffman table each where that is smaller), only the compressed bytes are downloaded, into one
+        reused page-locked buffer, and written with one write().  Records may straddle the BGZF blocks of a range.
+        `header` is the header text (default sam.UNALIGNED_HEADER), written as given into BGZF blocks of its own in
+        front of the records; one with @SQ lines is refused.  The 28-byte end-of-file block ends the file; an empty batch
+        is header + end-of-file block.  There is no append: a BAM file has one header.
+        Refused before the file is opened, so that it keeps what it held: an encoding other than Phred+33 (BAM stores
+        Phred values), and "record K: <reason>" for the lowest record BAM cannot hold -- a kept name above 254 bytes or
+        with a byte outside '!'..'~', a base that is not one of ACMGRSVTWYHKDBN, a quality byte outside 33..126.
+        Not done here: tags, aligned records, @SQ headers, paired flags, indexes."""
+        from . import bgzf, sam
+        from .encoding import encoding_name
+        if block_bytes is not None and int(block_bytes) < 1:
+            raise ValueError("'block_bytes' must be a positive integer")
+        kind = encoding_name(self._encoding())
+        if kind != "phred":
+            raise _lib.SarlaccError("BAM stores Phred values: the batch's quality encoding is %s, not Phred+33" % kind)
+        head = np.frombuffer(sam.bam_header_bytes(header), np.uint8)
+        names, noff, rec_off, cuts, ro, ranges = self._bam_plan(block_bytes)
+        largest = max([head.size] + [int(ro[b] - ro[a]) for a, b in ranges])
+        cap = bgzf.deflate_bound(largest)[1]
+        d_rec, d_comp, host = DevBuffer(largest), DevBuffer(cap), _lib.host_array(cap, np.uint8)
+        lib, written = _lib.lib(), 0
+        with open(path, "wb") as fh:
+            check(lib.sarlacc_dev_upload(d_rec, head, head.size))
+            _, nbytes = bgzf.deflate_device(d_rec, head.size, out=d_comp)
+            check(lib.sarlacc_dev_download(host, d_comp, nbytes))
+            fh.write(host[:nbytes])
+            written += nbytes
+            for a, b in ranges:
+                check(lib.sarlacc_dev_bam_format(self.seq, self.qual, self.off, names, noff, 1, rec_off, a, b - a, d_rec, None))
+                _, nbytes = bgzf.deflate_device(d_rec, int(ro[b] - ro[a]), out=d_comp, cuts=(cuts.ptr.value + 16 * a, 2 * (b - a)),
+                                                cut_origin=int(ro[a]))
+                check(lib.sarlacc_dev_download(host, d_comp, nbytes))
+                fh.write(host[:nbytes])
+                written += nbytes
+            fh.write(bgzf.EOF_BLOCK)
+        return written + len(bgzf.EOF_BLOCK)
 
     def _like(self, off_host):
         total = int(off_host[-1])

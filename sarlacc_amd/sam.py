@@ -250,6 +250,18 @@ def _bgzf_parts(path, block_bytes, restricted, use_minq, thr):
 
 
 BAM_MAGIC = b"BAM\1"
+UNALIGNED_HEADER = "@HD\tVN:1.6\tSO:unsorted\n"
+
+
+def bam_header_bytes(text=None):
+    """The header of an unaligned BAM file (SAM specification section 4.2): magic, l_text, the text as given (str or
+    bytes; None: UNALIGNED_HEADER) and n_ref = 0.  A text with @SQ lines is refused: the file lists no reference, and
+    the records DeviceReads.to_bam writes name none."""
+    raw = UNALIGNED_HEADER if text is None else text
+    raw = raw.encode() if isinstance(raw, str) else bytes(raw)
+    if any(line.startswith(b"@SQ") for line in raw.split(b"\n")):
+        raise SarlaccError("BAM header: @SQ lines in the header of an unaligned BAM file (its records name no reference)")
+    return BAM_MAGIC + len(raw).to_bytes(4, "little") + raw + (0).to_bytes(4, "little")
 
 
 def is_bam(path):
