@@ -14,10 +14,9 @@
 //   (rocPRIM exclusive scans over the records: read index, base offset, name offset; k_bamr_reads: read -> record)
 //   k_bamr_offsets  d_off / d_name_off of a range of reads, starting at 0
 //   k_bamr_unpack   the hot path, divided by OUTPUT bases as k_fqw_format is, not by records (reads run from 200 bases to
-//                   100 kb in one batch): a wavefront takes tiles of 4 096 bases, every lane four pieces of 16 bases 1 KB
-//                   apart, aligned in memory, so each store instruction of the wavefront writes 1 KB of consecutive
-//                   bytes to seq and 1 KB to qual.  A tile finds its first and last record by binary search in the base
-//                   offsets of the records (dropped records have length 0 there), a lane searches between those two.
+//                   100 kb in one batch): a body of out_tiles.hpp's walk_out_tiles over the base offsets of the records
+//                   (dropped records have length 0 there), which hands it pieces of 16 bases aligned in memory, so each
+//                   store instruction of the wavefront writes 1 KB of consecutive bytes to seq and 1 KB to qual.
 //                   A piece inside one read is one unaligned 8-byte load of packed codes (a ninth byte when the piece
 //                   starts at an odd base), the nibbles put in base order, the whole 64-bit word bit-reversed for a
 //                   reversed read -- which reverses the bases and complements each --, four v_perm_b32 table look-ups
@@ -35,8 +34,7 @@
 //   seq      SEQ holds '='                                (kept records)
 //   qual     quality value above 93                       (kept records)
 #include "bam_rec.hpp"
-#include "common.hpp"
-#include "devprim.hpp"
+#include "out_tiles.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
@@ -47,44 +45,20 @@ namespace {
 
 enum { BAMR_LAYOUT = 1, BAMR_SEQ = 2, BAMR_QUAL = 3 };
 
-constexpr int BR_THREADS = 256;
-constexpr int BR_PIECES = 4;                      // 16-base pieces per lane and tile
-constexpr int BR_TILE = 64 * 16 * BR_PIECES;      // bases per wavefront and step
-// "=ACMGRSVTWYHKDBN", four letters per register
-constexpr uint32_t BR_T0 = 0x4d43413du, BR_T1 = 0x56535247u, BR_T2 = 0x48595754u, BR_T3 = 0x4e42444bu;
-
-typedef uint32_t __attribute__((ext_vector_type(4))) br_u32x4;
-typedef br_u32x4 __attribute__((aligned(1))) br_u32x4_unaligned;
+constexpr int BR_TILE = 64 * 16 * OT_PIECES;      // bases per wavefront and step
 
 // non-zero iff one of the eight nibbles of w is 0
 __device__ __forceinline__ uint32_t zero_nibble8(uint32_t w) { return (w - 0x11111111u) & ~w & 0x88888888u; }
 // non-zero iff one of the four bytes of w is above 93
 __device__ __forceinline__ uint32_t above93_4(uint32_t w) { return (((w & 0x7f7f7f7fu) + 0x22222222u) | w) & 0x80808080u; }
 
-// whether one of the n bytes at p holds a zero nibble (SEQ) / a value above 93 (!SEQ): the whole wavefront, 16 bytes per
-// lane and step, the last bytes one by one
-template <bool SEQ>
-__device__ __forceinline__ bool wave_any_bad(const uint8_t* p, long long n, int lane) {
-    bool hit = false;
-    for (long long q = 16LL * lane; q < n; q += 16 * 64) {
-        if (q + 16 <= n) {
-            const br_u32x4 v = *reinterpret_cast<const br_u32x4_unaligned*>(p + q);
-            hit |= SEQ ? (zero_nibble8(v.x) | zero_nibble8(v.y) | zero_nibble8(v.z) | zero_nibble8(v.w)) != 0
-                       : (above93_4(v.x) | above93_4(v.y) | above93_4(v.z) | above93_4(v.w)) != 0;
-        } else {
-            for (long long j = q; j < n; ++j) hit |= SEQ ? (p[j] & 15) == 0 || (p[j] >> 4) == 0 : p[j] > 93;
-        }
-    }
-    return __ballot(hit) != 0;
-}
-
 // keep[k], bases[k] = l_seq and name_len[k] of a kept record, 0 of a dropped one
-__global__ void __launch_bounds__(BR_THREADS) k_bamr_size(const uint8_t* bam, const long long* rec_off, long long nrec,
+__global__ void __launch_bounds__(OT_THREADS) k_bamr_size(const uint8_t* bam, const long long* rec_off, long long nrec,
                                                           unsigned exclude, int* keep, long long* bases, long long* name_len,
                                                           unsigned long long* first_bad) {
     const int lane = threadIdx.x & 63;
-    const long long nwaves = static_cast<long long>(gridDim.x) * (BR_THREADS / 64);
-    for (long long k = static_cast<long long>(blockIdx.x) * (BR_THREADS / 64) + (threadIdx.x >> 6); k < nrec; k += nwaves) {
+    const long long nwaves = static_cast<long long>(gridDim.x) * (OT_THREADS / 64);
+    for (long long k = static_cast<long long>(blockIdx.x) * (OT_THREADS / 64) + (threadIdx.x >> 6); k < nrec; k += nwaves) {
         const uint8_t* rec = bam + rec_off[k];    // block_size >= 32 and wholly in the buffer: the locator checked
         BamFixed F;
         int kept = 0, bad = 0;
@@ -94,10 +68,12 @@ __global__ void __launch_bounds__(BR_THREADS) k_bamr_size(const uint8_t* bam, co
             kept = 1;
             const uint8_t* seq = rec + 36 + F.l_name + 4 * F.n_cig;
             const uint8_t* qual = seq + (F.l_seq + 1) / 2;
-            bool eq = wave_any_bad<true>(seq, F.l_seq / 2, lane);
+            bool eq = wave_any_bad(seq, F.l_seq / 2, lane, [](uint32_t w) { return zero_nibble8(w); },
+                                   [](uint8_t c) { return (c & 15) == 0 || (c >> 4) == 0; });
             if ((F.l_seq & 1) && (seq[F.l_seq / 2] >> 4) == 0) eq = true;      // the last byte of an odd read holds one base
             if (eq) bad = BAMR_SEQ;
-            else if (F.l_seq > 0 && qual[0] != 0xff && wave_any_bad<false>(qual, F.l_seq, lane)) bad = BAMR_QUAL;
+            else if (F.l_seq > 0 && qual[0] != 0xff && wave_any_bad(qual, F.l_seq, lane, [](uint32_t w) { return above93_4(w); },
+                                                                    [](uint8_t c) { return c > 93; })) bad = BAMR_QUAL;
         }
         if (bad) kept = 0;
         if (lane == 0) {
@@ -139,7 +115,7 @@ __device__ __forceinline__ uint32_t letters4(uint32_t x) {
     uint32_t t = (x | (x << 8)) & 0x00ff00ffu;
     t = (t | (t << 4)) & 0x0f0f0f0fu;                        // one code per byte
     const uint32_t sel = t & 0x07070707u;
-    const uint32_t lo = __builtin_amdgcn_perm(BR_T1, BR_T0, sel), hi = __builtin_amdgcn_perm(BR_T3, BR_T2, sel);
+    const uint32_t lo = __builtin_amdgcn_perm(BAM_LETTERS1, BAM_LETTERS0, sel), hi = __builtin_amdgcn_perm(BAM_LETTERS3, BAM_LETTERS2, sel);
     const uint32_t m = ((t >> 3) & 0x01010101u) * 0xffu;     // bytes whose code is 8 or above
     return (hi & m) | (lo & ~m);
 }
@@ -166,12 +142,12 @@ struct BrSource {
         uint32_t c = R.seq[i >> 1];
         c = (i & 1) ? c & 15u : c >> 4;
         if (R.rev) c = __brev(c) >> 28;
-        *s = static_cast<uint8_t>((c < 8 ? (static_cast<uint64_t>(BR_T1) << 32 | BR_T0) : (static_cast<uint64_t>(BR_T3) << 32 | BR_T2)) >> (8 * (c & 7)));
+        *s = static_cast<uint8_t>((c < 8 ? (static_cast<uint64_t>(BAM_LETTERS1) << 32 | BAM_LETTERS0) : (static_cast<uint64_t>(BAM_LETTERS3) << 32 | BAM_LETTERS2)) >> (8 * (c & 7)));
         *q = R.missing ? static_cast<uint8_t>(fill) : static_cast<uint8_t>(R.qual[i] + 33);
     }
 
     // bases j .. j + 16 of the read (all inside it) and their qualities
-    __device__ __forceinline__ void piece(const BrRead& R, long long j, br_u32x4* S, br_u32x4* Q) const {
+    __device__ __forceinline__ void piece(const BrRead& R, long long j, u32x4* S, u32x4* Q) const {
         const long long s = R.rev ? R.len - 16 - j : j;      // the stored bases s .. s + 16
         const uint8_t* p = R.seq + (s >> 1);
         uint64_t w;
@@ -185,54 +161,37 @@ struct BrSource {
         S->z = letters4(static_cast<uint32_t>(n >> 32) & 0xffffu);
         S->w = letters4(static_cast<uint32_t>(n >> 48));
         if (R.missing) {
-            *Q = br_u32x4{fill, fill, fill, fill};
+            *Q = u32x4{fill, fill, fill, fill};
             return;
         }
-        br_u32x4 v = *reinterpret_cast<const br_u32x4_unaligned*>(R.qual + s);
+        u32x4 v = *reinterpret_cast<const u32x4_unaligned*>(R.qual + s);
         v += 0x21212121u;                  // no carry between the bytes: the size pass refused values above 93
-        if (R.rev) v = br_u32x4{__builtin_bswap32(v.w), __builtin_bswap32(v.z), __builtin_bswap32(v.y), __builtin_bswap32(v.x)};
+        if (R.rev) v = u32x4{__builtin_bswap32(v.w), __builtin_bswap32(v.z), __builtin_bswap32(v.y), __builtin_bswap32(v.x)};
         *Q = v;
     }
 };
 
 // seq[0 .. ) and qual[0 .. ) = the bases base_off[a] .. base_off[e] of the buffer: the reads of the records a .. e
-__global__ void __launch_bounds__(BR_THREADS) k_bamr_unpack(BrSource S, long long a, long long e, uint8_t* seq, uint8_t* qual) {
-    const long long base = S.base_off[a], nbases = S.base_off[e] - base;
-    const int mis = static_cast<int>(reinterpret_cast<uintptr_t>(seq) & 15);   // pieces are aligned in memory, not in the range
-    const long long ntiles = (nbases + mis + BR_TILE - 1) / BR_TILE;
-    const int lane = threadIdx.x & 63;
-    const long long wave = blockIdx.x * static_cast<long long>(BR_THREADS / 64) + (threadIdx.x >> 6);
-    const long long nwaves = static_cast<long long>(gridDim.x) * (BR_THREADS / 64);
+__global__ void __launch_bounds__(OT_THREADS) k_bamr_unpack(BrSource S, long long a, long long e, uint8_t* seq, uint8_t* qual) {
     BrRead R;
-    for (long long tile = wave; tile < ntiles; tile += nwaves) {
-        const long long t0 = tile * BR_TILE - mis;
-        const long long tile_lo = t0 > 0 ? t0 : 0, tile_hi = (t0 + BR_TILE < nbases ? t0 + BR_TILE : nbases) - 1;
-        // first and last record of the tile (the same in every lane)
-        const long long k_lo = last_not_above(S.base_off, a, e, base + tile_lo);
-        const long long k_hi = S.base_off[k_lo + 1] > base + tile_hi ? k_lo : last_not_above(S.base_off, k_lo, e, base + tile_hi);
-#pragma unroll 1
-        for (int i = 0; i < BR_PIECES; ++i) {
-            const long long p0 = t0 + (i * 64 + lane) * 16;
-            const long long v0 = p0 > 0 ? p0 : 0, v1 = p0 + 16 < nbases ? p0 + 16 : nbases;   // head and tail of the range
-            if (v0 >= v1) continue;
-            const long long k = last_not_above(S.base_off, k_lo, k_hi + 1, base + v0);
-            if (k != R.k) S.load(R, k);
-            const long long j = base + v0 - R.b0;
-            if (v1 - v0 == 16 && j + 16 <= R.len) {
-                br_u32x4 s, q;
-                S.piece(R, j, &s, &q);
-                *reinterpret_cast<br_u32x4*>(seq + p0) = s;
-                *reinterpret_cast<br_u32x4_unaligned*>(qual + p0) = q;     // (aligned as well where qual is aligned like seq)
-                continue;
-            }
-            // the ends of reads and of the range: base by base
-#pragma unroll 1
-            for (long long p = v0; p < v1; ++p) {
-                if (base + p >= R.b0 + R.len) S.load(R, last_not_above(S.base_off, R.k, k_hi + 1, base + p));
-                S.one(R, base + p - R.b0, seq + p, qual + p);
-            }
+    walk_out_tiles<OT_THREADS / 64, OT_PIECES>(S.base_off, a, e, seq,
+                                               [&](long long base, long long p0, long long v0, long long v1, long long k, long long k_hi) {
+        if (k != R.k) S.load(R, k);
+        const long long j = base + v0 - R.b0;
+        if (v1 - v0 == 16 && j + 16 <= R.len) {
+            u32x4 s, q;
+            S.piece(R, j, &s, &q);
+            *reinterpret_cast<u32x4*>(seq + p0) = s;
+            *reinterpret_cast<u32x4_unaligned*>(qual + p0) = q;     // (aligned as well where qual is aligned like seq)
+            return;
         }
-    }
+        // the ends of reads and of the range: base by base
+#pragma unroll 1
+        for (long long p = v0; p < v1; ++p) {
+            if (base + p >= R.b0 + R.len) S.load(R, last_not_above(S.base_off, R.k, k_hi + 1, base + p));
+            S.one(R, base + p - R.b0, seq + p, qual + p);
+        }
+    });
 }
 
 // names[0 .. ) = the names of the records a .. e, sixteen lanes per record
@@ -342,9 +301,9 @@ int sarlacc_dev_bam_reads_index(const uint8_t* d_bam, int64_t nbytes, int64_t fi
         SL_HIP(hipMemsetAsync(d_bases + nrec, 0, sizeof(long long), s));
         SL_HIP(hipMemsetAsync(d_nlen + nrec, 0, sizeof(long long), s));
         SL_HIP(hipMemcpyAsync(L.d_off + nrec, &L.end, sizeof(long long), hipMemcpyHostToDevice, s));
-        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nrec, BR_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
+        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nrec, OT_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
         SL_TRY(c.stage_begin("bam_reads_size", s));
-        hipLaunchKernelGGL(k_bamr_size, dim3(grid), dim3(BR_THREADS), 0, s, d_bam, L.d_off, nrec, static_cast<unsigned>(exclude_flags),
+        hipLaunchKernelGGL(k_bamr_size, dim3(grid), dim3(OT_THREADS), 0, s, d_bam, L.d_off, nrec, static_cast<unsigned>(exclude_flags),
                            d_keep, d_bases, d_nlen, d_bad);
         SL_HIP(hipGetLastError());
         SL_TRY(exclusive_scan("bamr.scan", d_keep, d_roff, static_cast<size_t>(nrec) + 1, s));
@@ -413,8 +372,8 @@ int sarlacc_dev_bam_reads_extract(const uint8_t* d_bam, int64_t first, int64_t c
     if (sp.bases > 0) {
         const BrSource src{d_bam, X.rec_off, X.base_off, static_cast<uint32_t>(missing_qual + 33) * 0x01010101u};
         const long long ntiles = (sp.bases + 15 + BR_TILE - 1) / BR_TILE;
-        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(ntiles, BR_THREADS / 64), static_cast<long long>(c.num_cu) * 8));
-        hipLaunchKernelGGL(k_bamr_unpack, dim3(grid), dim3(BR_THREADS), 0, s, src, sp.a, sp.e, d_seq, d_qual);
+        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(ntiles, OT_THREADS / 64), static_cast<long long>(c.num_cu) * 8));
+        hipLaunchKernelGGL(k_bamr_unpack, dim3(grid), dim3(OT_THREADS), 0, s, src, sp.a, sp.e, d_seq, d_qual);
         SL_HIP(hipGetLastError());
     }
     if (d_names && sp.name_bytes > 0) {

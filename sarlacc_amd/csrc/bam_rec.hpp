@@ -1,5 +1,6 @@
-// bam_rec.hpp -- what the two BAM paths share (bam.hip: records -> ranges, bam_reads.hip: records -> reads): the
-// unaligned field readers, the layout predicate every record has to pass, and the locator (implemented in bam.hip).
+// bam_rec.hpp -- what the BAM paths share (bam.hip: records -> ranges, bam_reads.hip: records -> reads, bam_write.hip:
+// reads -> records): SEQ's alphabet in both directions, the unaligned field readers, the layout predicate every record
+// has to pass, and the locator (implemented in bam.hip).
 #pragma once
 
 #include "common.hpp"
@@ -7,6 +8,30 @@
 namespace sarlacc {
 
 constexpr int BAM_TILE = 16384;                  // 64 KB of LDS: two workgroups per CU
+
+// SEQ's alphabet, code -> letter, and its two register tables (each byte-indexed by v_perm_b32, lowest byte first):
+// BAM_LETTERS<k> holds the letters of the codes 4 k .. 4 k + 3 (bam_reads.hip), BAM_CODES<k> the codes of the letters
+// whose low five bits are 4 k .. 4 k + 3, 0 where there is none (bam_write.hip; the 15 letters are distinct in those bits
+// and '=' is never written).
+constexpr char BAM_ALPHABET[] = "=ACMGRSVTWYHKDBN";
+constexpr uint32_t bam_letters_word(int k) {
+    return static_cast<uint32_t>(BAM_ALPHABET[4 * k]) | (static_cast<uint32_t>(BAM_ALPHABET[4 * k + 1]) << 8) |
+           (static_cast<uint32_t>(BAM_ALPHABET[4 * k + 2]) << 16) | (static_cast<uint32_t>(BAM_ALPHABET[4 * k + 3]) << 24);
+}
+constexpr uint32_t bam_code_of(int low5) {
+    for (int c = 1; c < 16; ++c)
+        if ((BAM_ALPHABET[c] & 31) == low5) return static_cast<uint32_t>(c);
+    return 0;
+}
+constexpr uint32_t bam_codes_word(int k) {
+    return bam_code_of(4 * k) | (bam_code_of(4 * k + 1) << 8) | (bam_code_of(4 * k + 2) << 16) | (bam_code_of(4 * k + 3) << 24);
+}
+constexpr uint32_t BAM_LETTERS0 = bam_letters_word(0), BAM_LETTERS1 = bam_letters_word(1), BAM_LETTERS2 = bam_letters_word(2),
+                   BAM_LETTERS3 = bam_letters_word(3);
+constexpr uint32_t BAM_CODES0 = bam_codes_word(0), BAM_CODES1 = bam_codes_word(1), BAM_CODES2 = bam_codes_word(2),
+                   BAM_CODES3 = bam_codes_word(3), BAM_CODES4 = bam_codes_word(4), BAM_CODES5 = bam_codes_word(5),
+                   BAM_CODES6 = bam_codes_word(6), BAM_CODES7 = bam_codes_word(7);
+static_assert(BAM_LETTERS0 == 0x4d43413du && BAM_LETTERS3 == 0x4e42444bu, "BAM_LETTERS: lowest byte first");
 
 __device__ __forceinline__ unsigned rd_u32(const uint8_t* p) {
     unsigned v;

@@ -16,12 +16,11 @@
 //                  bytes per lane and step; the byte length of the record
 //   (rocPRIM exclusive scan: n + 1 record offsets, the last one is the size of the stream)
 //   k_bamw_cuts    SEQ start and QUAL start of every record in the stream
-//   k_bamw_format  the bytes of a contiguous record range, divided by OUTPUT bytes as k_fqw_format is: a wavefront takes
-//                  tiles of 4 KB, every lane four 16-byte pieces 1 KB apart, aligned in memory.  A tile finds its first
-//                  and last record by binary search in the record offsets, a lane searches between those two.  A piece
+//   k_bamw_format  the bytes of a contiguous record range, divided by OUTPUT bytes as k_fqw_format is: the walk
+//                  out_tiles.hpp describes (this kernel's own copy of it), 16-byte pieces aligned in memory.  A piece
 //                  inside SEQ packs 32 bases read with two unaligned 16-byte loads: the letter's low five bits index a
-//                  32-entry table of codes held in eight registers (the 15 letters are distinct in those bits), read
-//                  with v_perm_b32 four letters at a time.  A piece inside QUAL is one unaligned 16-byte load.  A piece
+//                  32-entry table of codes held in eight registers (bam_rec.hpp; the 15 letters are distinct in those
+//                  bits), read with v_perm_b32 four letters at a time.  A piece inside QUAL is one unaligned 16-byte load.  A piece
 //                  that holds fixed fields, a name, the first or last bytes of SEQ or QUAL or a record boundary is
 //                  assembled byte by byte in the lane's registers and leaves as one 16-byte store too; only the two
 //                  ends of the range are stored byte by byte.
@@ -37,8 +36,8 @@
 //   quality byte outside Phred+33                (outside 33..126)
 //   record larger than 2^31 - 1 bytes
 // Out of scope: tags, aligned records, paired flags, qualities written as the 0xff "missing" marker.
-#include "common.hpp"
-#include "devprim.hpp"
+#include "bam_rec.hpp"
+#include "out_tiles.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
@@ -49,43 +48,17 @@ namespace {
 
 enum { BAMW_NAME_LONG = 1, BAMW_NAME_BYTE = 2, BAMW_BASE = 3, BAMW_QUAL = 4, BAMW_SIZE = 5 };
 
-constexpr int BW_THREADS = 256;
-constexpr int BW_PIECES = 4;                      // 16-byte pieces per lane and tile
-constexpr int BW_TILE = 64 * 16 * BW_PIECES;      // bytes of the stream per wavefront and step
 constexpr int BW_FIXED = 36;                      // block_size and the fixed fields
-constexpr int BW_NAME_PREFIX = 5;                 // "READ_"
 constexpr int BW_NAME_MAX = 254;                  // l_read_name is a byte and counts the NUL
 constexpr uint32_t BW_BIN = 4680;                 // reg2bin(-1, 0)
 constexpr uint32_t BW_FLAG = 4;                   // unmapped
 
-// code of the letter whose low five bits are i (0: no letter)
-constexpr uint32_t bw_code_of(int i) {
-    const char* letters = "=ACMGRSVTWYHKDBN";
-    for (int c = 1; c < 16; ++c)
-        if ((letters[c] & 31) == i) return static_cast<uint32_t>(c);
-    return 0;
-}
-constexpr uint32_t bw_table_word(int k) {
-    return bw_code_of(4 * k) | (bw_code_of(4 * k + 1) << 8) | (bw_code_of(4 * k + 2) << 16) | (bw_code_of(4 * k + 3) << 24);
-}
-// the table, four entries per register
-constexpr uint32_t BW_T0 = bw_table_word(0), BW_T1 = bw_table_word(1), BW_T2 = bw_table_word(2), BW_T3 = bw_table_word(3),
-                   BW_T4 = bw_table_word(4), BW_T5 = bw_table_word(5), BW_T6 = bw_table_word(6), BW_T7 = bw_table_word(7);
-
-typedef uint32_t __attribute__((ext_vector_type(4))) bw_u32x4;
-typedef bw_u32x4 __attribute__((aligned(1))) bw_u32x4_unaligned;
-
-__device__ __forceinline__ int bw_decimal_width(unsigned long long v) {
-    int w = 1;
-    while (v >= 10) { v /= 10; ++w; }
-    return w;
-}
-
-// codes of the four letters of w, byte by byte; 0 where the low five bits are those of no letter
+// codes of the four letters of w, byte by byte (bam_rec.hpp's table of codes); 0 where the low five bits are those of
+// no letter
 __device__ __forceinline__ uint32_t codes4(uint32_t w) {
     const uint32_t sel = w & 0x07070707u;
-    const uint32_t p0 = __builtin_amdgcn_perm(BW_T1, BW_T0, sel), p1 = __builtin_amdgcn_perm(BW_T3, BW_T2, sel);
-    const uint32_t p2 = __builtin_amdgcn_perm(BW_T5, BW_T4, sel), p3 = __builtin_amdgcn_perm(BW_T7, BW_T6, sel);
+    const uint32_t p0 = __builtin_amdgcn_perm(BAM_CODES1, BAM_CODES0, sel), p1 = __builtin_amdgcn_perm(BAM_CODES3, BAM_CODES2, sel);
+    const uint32_t p2 = __builtin_amdgcn_perm(BAM_CODES5, BAM_CODES4, sel), p3 = __builtin_amdgcn_perm(BAM_CODES7, BAM_CODES6, sel);
     const uint32_t m3 = ((w >> 3) & 0x01010101u) * 0xffu, m4 = ((w >> 4) & 0x01010101u) * 0xffu;
     const uint32_t lo = (p1 & m3) | (p0 & ~m3), hi = (p3 & m3) | (p2 & ~m3);
     return (hi & m4) | (lo & ~m4);
@@ -107,23 +80,6 @@ __device__ __forceinline__ uint32_t not_phred4(uint32_t w) {
 __device__ __forceinline__ uint32_t pack4(uint32_t c) {
     const uint32_t x = (c << 4) | (c >> 8);
     return (x & 0xffu) | ((x >> 8) & 0xff00u);
-}
-
-// whether one of the n bytes at p is no base (SEQ) / no Phred+33 quality (!SEQ): the whole wavefront, 16 bytes per lane
-// and step, the last bytes one by one
-template <bool SEQ>
-__device__ __forceinline__ bool wave_any_bad(const uint8_t* p, long long n, int lane) {
-    bool hit = false;
-    for (long long q = 16LL * lane; q < n; q += 16 * 64) {
-        if (q + 16 <= n) {
-            const bw_u32x4 v = *reinterpret_cast<const bw_u32x4_unaligned*>(p + q);
-            hit |= SEQ ? (not_base4(v.x) | not_base4(v.y) | not_base4(v.z) | not_base4(v.w)) != 0
-                       : (not_phred4(v.x) | not_phred4(v.y) | not_phred4(v.z) | not_phred4(v.w)) != 0;
-        } else {
-            for (long long j = q; j < n; ++j) hit |= SEQ ? not_base4(p[j] | 0x41414100u) != 0 : p[j] < 33 || p[j] > 126;
-        }
-    }
-    return __ballot(hit) != 0;
 }
 
 __device__ __forceinline__ long long wave_min(long long v) {
@@ -150,13 +106,13 @@ __device__ __forceinline__ void wave_name_scan(const uint8_t* p, long long n, in
 }
 
 // len[r] = bytes of record r, 0 for a refused one (len[n] = 0 for the scan); first_bad: lowest refused record << 4 | why
-__global__ void __launch_bounds__(BW_THREADS) k_bamw_size(const uint8_t* seq, const uint8_t* qual, const int64_t* off,
+__global__ void __launch_bounds__(OT_THREADS) k_bamw_size(const uint8_t* seq, const uint8_t* qual, const int64_t* off,
                                                           const uint8_t* names, const int64_t* name_off, long long first_index,
                                                           long long n, long long* len, unsigned long long* first_bad) {
     const int lane = threadIdx.x & 63;
-    const long long nwaves = static_cast<long long>(gridDim.x) * (BW_THREADS / 64);
+    const long long nwaves = static_cast<long long>(gridDim.x) * (OT_THREADS / 64);
     if (blockIdx.x == 0 && threadIdx.x == 0) len[n] = 0;
-    for (long long r = static_cast<long long>(blockIdx.x) * (BW_THREADS / 64) + (threadIdx.x >> 6); r < n; r += nwaves) {
+    for (long long r = static_cast<long long>(blockIdx.x) * (OT_THREADS / 64) + (threadIdx.x >> 6); r < n; r += nwaves) {
         const long long so = off[r], L = off[r + 1] - so;
         long long l_name;
         int bad = 0;
@@ -168,10 +124,12 @@ __global__ void __launch_bounds__(BW_THREADS) k_bamw_size(const uint8_t* seq, co
             else if (other < kept) bad = BAMW_NAME_BYTE;
             l_name = (kept > 0 ? kept : 1) + 1;      // '*' for an empty name
         } else {
-            l_name = BW_NAME_PREFIX + bw_decimal_width(static_cast<unsigned long long>(first_index + r)) + 1;
+            l_name = NAME_PREFIX + decimal_width(static_cast<unsigned long long>(first_index + r)) + 1;
         }
-        if (!bad && wave_any_bad<true>(seq + so, L, lane)) bad = BAMW_BASE;
-        if (!bad && wave_any_bad<false>(qual + so, L, lane)) bad = BAMW_QUAL;
+        if (!bad && wave_any_bad(seq + so, L, lane, [](uint32_t w) { return not_base4(w); },
+                                 [](uint8_t c) { return not_base4(c | 0x41414100u) != 0; })) bad = BAMW_BASE;
+        if (!bad && wave_any_bad(qual + so, L, lane, [](uint32_t w) { return not_phred4(w); },
+                                 [](uint8_t c) { return c < 33 || c > 126; })) bad = BAMW_QUAL;
         const long long total = BW_FIXED + l_name + (L + 1) / 2 + L;
         if (!bad && total > 0x7fffffffLL) bad = BAMW_SIZE;
         if (lane == 0) {
@@ -218,14 +176,6 @@ struct BwSource {
         }
     }
 
-    // character k of record R's default name
-    __device__ __forceinline__ uint8_t default_name(const BwRec& R, int k) const {
-        if (k < BW_NAME_PREFIX) return static_cast<uint8_t>("READ_"[k]);
-        unsigned long long v = static_cast<unsigned long long>(first_index + R.r);
-        for (int d = R.l_name - 2 - k; d > 0; --d) v /= 10;   // digit k - 5 of l_name - 6, from the left
-        return static_cast<uint8_t>('0' + v % 10);
-    }
-
     // byte q of record R
     __device__ __forceinline__ uint8_t byte_at(const BwRec& R, long long q) const {
         if (q < BW_FIXED) {
@@ -240,7 +190,7 @@ struct BwSource {
         q -= BW_FIXED;
         if (q < R.l_name) {
             if (q == R.l_name - 1) return 0;
-            if (!names) return default_name(R, static_cast<int>(q));
+            if (!names) return default_name_char(static_cast<unsigned long long>(first_index + R.r), R.l_name - 1, static_cast<int>(q));
             return R.star ? static_cast<uint8_t>('*') : names[R.no + q];
         }
         q -= R.l_name;
@@ -254,14 +204,17 @@ struct BwSource {
     }
 };
 
-// out[0 .. ) = bytes rec_off[first] .. rec_off[first + count] of the whole stream
-__global__ void __launch_bounds__(BW_THREADS) k_bamw_format(BwSource S, long long first, long long count, uint8_t* out) {
+// out[0 .. ) = bytes rec_off[first] .. rec_off[first + count] of the whole stream.  This kernel keeps its own copy of
+// walk_out_tiles and of OutPiece (out_tiles.hpp; change them together): as a body of the shared walk it left its
+// occupancy step or ran 2 - 5 % longer on 200-base reads (profiles/io_tile_walk_device_code.txt, io_tile_walk_speed.txt).
+__global__ void __launch_bounds__(OT_THREADS) k_bamw_format(BwSource S, long long first, long long count, uint8_t* out) {
+    constexpr int BW_TILE = 64 * 16 * OT_PIECES;      // bytes of the stream per wavefront and step
     const long long base = S.rec_off[first], nbytes = S.rec_off[first + count] - base;
     const int mis = static_cast<int>(reinterpret_cast<uintptr_t>(out) & 15);   // pieces are aligned in memory, not in the stream
     const long long ntiles = (nbytes + mis + BW_TILE - 1) / BW_TILE;
     const int lane = threadIdx.x & 63;
-    const long long wave = blockIdx.x * static_cast<long long>(BW_THREADS / 64) + (threadIdx.x >> 6);
-    const long long nwaves = static_cast<long long>(gridDim.x) * (BW_THREADS / 64);
+    const long long wave = blockIdx.x * static_cast<long long>(OT_THREADS / 64) + (threadIdx.x >> 6);
+    const long long nwaves = static_cast<long long>(gridDim.x) * (OT_THREADS / 64);
     BwRec R;
     for (long long tile = wave; tile < ntiles; tile += nwaves) {
         const long long t0 = tile * BW_TILE - mis;
@@ -271,7 +224,7 @@ __global__ void __launch_bounds__(BW_THREADS) k_bamw_format(BwSource S, long lon
         const long long r_hi = S.rec_off[r_lo + 1] > base + tile_hi ? r_lo
                                                                    : last_not_above(S.rec_off, r_lo, first + count, base + tile_hi);
 #pragma unroll 1
-        for (int k = 0; k < BW_PIECES; ++k) {
+        for (int k = 0; k < OT_PIECES; ++k) {
             const long long p0 = t0 + (k * 64 + lane) * 16;
             const long long v0 = p0 > 0 ? p0 : 0, v1 = p0 + 16 < nbytes ? p0 + 16 : nbytes;   // head and tail of the range
             if (v0 >= v1) continue;
@@ -281,21 +234,21 @@ __global__ void __launch_bounds__(BW_THREADS) k_bamw_format(BwSource S, long lon
             const bool whole = v1 - v0 == 16;
             const long long sq = BW_FIXED + R.l_name, ql = sq + (R.sl + 1) / 2;
             if (whole && q >= ql && q + 16 <= R.len) {          // sixteen qualities
-                bw_u32x4 v = *reinterpret_cast<const bw_u32x4_unaligned*>(S.qual + R.so + (q - ql));
+                u32x4 v = *reinterpret_cast<const u32x4_unaligned*>(S.qual + R.so + (q - ql));
                 v -= 0x21212121u;                               // no borrow between the bytes: the size pass refused values below 33
-                *reinterpret_cast<bw_u32x4*>(out + p0) = v;
+                *reinterpret_cast<u32x4*>(out + p0) = v;
                 continue;
             }
             if (whole && q >= sq && 2 * (q - sq) + 32 <= R.sl) {   // thirty-two bases
                 const uint8_t* b = S.seq + R.so + 2 * (q - sq);
-                const bw_u32x4 a = *reinterpret_cast<const bw_u32x4_unaligned*>(b);
-                const bw_u32x4 c = *reinterpret_cast<const bw_u32x4_unaligned*>(b + 16);
-                bw_u32x4 v;
+                const u32x4 a = *reinterpret_cast<const u32x4_unaligned*>(b);
+                const u32x4 c = *reinterpret_cast<const u32x4_unaligned*>(b + 16);
+                u32x4 v;
                 v.x = pack4(codes4(a.x)) | (pack4(codes4(a.y)) << 16);
                 v.y = pack4(codes4(a.z)) | (pack4(codes4(a.w)) << 16);
                 v.z = pack4(codes4(c.x)) | (pack4(codes4(c.y)) << 16);
                 v.w = pack4(codes4(c.z)) | (pack4(codes4(c.w)) << 16);
-                *reinterpret_cast<bw_u32x4*>(out + p0) = v;
+                *reinterpret_cast<u32x4*>(out + p0) = v;
                 continue;
             }
             // fixed fields, names, the ends of SEQ and QUAL, of records and of the range: byte by byte into the registers
@@ -308,10 +261,10 @@ __global__ void __launch_bounds__(BW_THREADS) k_bamw_format(BwSource S, long lon
                 if (d < 8) lo |= c << (8 * d); else hi |= c << (8 * (d - 8));
             }
             if (whole) {
-                bw_u32x4 v;
+                u32x4 v;
                 v.x = static_cast<uint32_t>(lo); v.y = static_cast<uint32_t>(lo >> 32);
                 v.z = static_cast<uint32_t>(hi); v.w = static_cast<uint32_t>(hi >> 32);
-                *reinterpret_cast<bw_u32x4*>(out + p0) = v;
+                *reinterpret_cast<u32x4*>(out + p0) = v;
             } else {
 #pragma unroll 1
                 for (int d = d0; d < d1; ++d) out[p0 + d] = static_cast<uint8_t>((d < 8 ? lo : hi) >> (8 * (d & 7)));
@@ -330,70 +283,37 @@ extern "C" {
 int sarlacc_dev_bam_format_size(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
                                 const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
                                 int64_t* d_rec_off, int64_t* d_cuts, int64_t* total_bytes, void* stream) {
-    if (n < 0 || first_index < 0 || !total_bytes) return fail("sarlacc_amd: bad BAM format request");
-    if ((d_names == nullptr) != (d_name_off == nullptr)) return fail("sarlacc_amd: read names and their offsets go together");
-    SL_TRY(ensure_device());
     hipStream_t s = static_cast<hipStream_t>(stream);
-    *total_bytes = 0;
-    if (n == 0) {
-        SL_HIP(hipMemsetAsync(d_rec_off, 0, sizeof(int64_t), s));
-        SL_HIP(hipStreamSynchronize(s));
-        return 0;
-    }
-    Context& c = ctx();
-    long long* d_len; unsigned long long* d_bad;
-    SL_TRY(scratch("bamw.len", static_cast<size_t>(n) + 1, &d_len));
-    SL_TRY(scratch("bamw.bad", 1, &d_bad));
-    SL_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), s));
-    c.stage_reset("bam_format_size");
-    SL_TRY(c.stage_begin("bam_format_size", s));
-    const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(n, BW_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
-    hipLaunchKernelGGL(k_bamw_size, dim3(grid), dim3(BW_THREADS), 0, s, d_seq, d_qual, d_off, d_names, d_name_off,
-                       static_cast<long long>(first_index), static_cast<long long>(n), d_len, d_bad);
-    SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan("bamw.scan", d_len, d_rec_off, static_cast<size_t>(n) + 1, s));
-    if (d_cuts) {
-        hipLaunchKernelGGL(k_bamw_cuts, dim3(nblk(n, 256)), dim3(256), 0, s, d_off, d_rec_off, static_cast<long long>(n), d_cuts);
-        SL_HIP(hipGetLastError());
-    }
-    SL_TRY(c.stage_end("bam_format_size", s));
-    unsigned long long bad = 0;
-    int64_t total = 0;
-    SL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipMemcpyAsync(&total, d_rec_off + n, sizeof total, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipStreamSynchronize(s));
-    if (bad != ~0ull) {
-        const long long k = static_cast<long long>(bad >> 4) + 1;
-        switch (bad & 15u) {
-            case BAMW_NAME_LONG: return fail("record %lld: read name longer than 254 bytes", k);
-            case BAMW_NAME_BYTE: return fail("record %lld: read name holds a byte outside '!'..'~'", k);
-            case BAMW_BASE: return fail("record %lld: base cannot be stored in BAM", k);
-            case BAMW_QUAL: return fail("record %lld: quality byte outside Phred+33", k);
-            default: return fail("record %lld: record larger than 2^31 - 1 bytes", k);
-        }
-    }
-    *total_bytes = total;
-    return 0;
+    return format_size_pass("BAM", "bamw", "bam_format_size", n, d_names, d_name_off, first_index, d_rec_off, total_bytes, s,
+        [&](Context& c, long long* d_len, unsigned long long* d_bad) {
+            const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(n, OT_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
+            hipLaunchKernelGGL(k_bamw_size, dim3(grid), dim3(OT_THREADS), 0, s, d_seq, d_qual, d_off, d_names, d_name_off,
+                               static_cast<long long>(first_index), static_cast<long long>(n), d_len, d_bad);
+        },
+        [&] {
+            if (d_cuts) hipLaunchKernelGGL(k_bamw_cuts, dim3(nblk(n, 256)), dim3(256), 0, s, d_off, d_rec_off, static_cast<long long>(n), d_cuts);
+        },
+        [](unsigned long long bad) {
+            const long long k = static_cast<long long>(bad >> 4) + 1;
+            switch (bad & 15u) {
+                case BAMW_NAME_LONG: return fail("record %lld: read name longer than 254 bytes", k);
+                case BAMW_NAME_BYTE: return fail("record %lld: read name holds a byte outside '!'..'~'", k);
+                case BAMW_BASE: return fail("record %lld: base cannot be stored in BAM", k);
+                case BAMW_QUAL: return fail("record %lld: quality byte outside Phred+33", k);
+                default: return fail("record %lld: record larger than 2^31 - 1 bytes", k);
+            }
+        });
 }
 
 int sarlacc_dev_bam_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
                            const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
                            int64_t count, uint8_t* d_out, void* stream) {
-    if (first < 0 || count < 0 || first_index < 0) return fail("sarlacc_amd: bad BAM format request");
-    if ((d_names == nullptr) != (d_name_off == nullptr)) return fail("sarlacc_amd: read names and their offsets go together");
-    if (count == 0) return 0;
-    SL_TRY(ensure_device());
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Context& c = ctx();
-    const BwSource src{d_seq, d_qual, d_off, d_names, d_name_off, static_cast<long long>(first_index), d_rec_off};
-    // the size of the range is known on the device only: a resident grid whose wavefronts stride over the tiles
-    c.stage_reset("bam_format");
-    SL_TRY(c.stage_begin("bam_format", s));
-    hipLaunchKernelGGL(k_bamw_format, dim3(static_cast<unsigned>(c.num_cu) * 8), dim3(BW_THREADS), 0, s, src,
-                       static_cast<long long>(first), static_cast<long long>(count), d_out);
-    SL_HIP(hipGetLastError());
-    SL_TRY(c.stage_end("bam_format", s));
-    SL_HIP(hipStreamSynchronize(s));
-    return 0;
+    return format_range("BAM", "bam_format", d_names, d_name_off, first_index, first, count, s, [&](dim3 grid) {
+        const BwSource src{d_seq, d_qual, d_off, d_names, d_name_off, static_cast<long long>(first_index), d_rec_off};
+        hipLaunchKernelGGL(k_bamw_format, grid, dim3(OT_THREADS), 0, s, src, static_cast<long long>(first),
+                           static_cast<long long>(count), d_out);
+    });
 }
 }
+

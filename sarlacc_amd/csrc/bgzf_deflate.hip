@@ -50,7 +50,7 @@
 // .gzi / .csi indexes, compressing on the host.
 #include "common.hpp"
 #include "crc32.hpp"
-#include "devprim.hpp"
+#include "out_tiles.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
@@ -66,9 +66,6 @@ constexpr int DF_STAGE = 160;            // words of the staging window
 constexpr int DF_FLUSH = 64;             // full words that trigger a flush
 constexpr int DF_NLEN = 258;             // lengths a table header codes: 257 literal/length codes and one distance code
 constexpr int DF_ORIGIN = 16;            // slot byte of the staging window's bit 0 (the payload starts at byte 18)
-
-typedef uint32_t __attribute__((ext_vector_type(4))) df_u32x4;
-typedef df_u32x4 __attribute__((aligned(1))) df_u32x4_unaligned;
 
 __constant__ uint8_t c_df_clen_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
@@ -244,9 +241,9 @@ __device__ void flush(DfShared& sh, DfOut& o, bool all, int lane) {
         const int a = g * 4;
         if (a >= o.wbase && a + 4 <= wend) {
             const uint32_t* p = &sh.stage[a - o.wbase];
-            df_u32x4 v;
+            u32x4 v;
             v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3];
-            *reinterpret_cast<df_u32x4*>(o.words + a) = v;
+            *reinterpret_cast<u32x4*>(o.words + a) = v;
         } else {
             for (int j = 0; j < 4; ++j)
                 if (a + j >= o.wbase && a + j < wend) o.words[a + j] = sh.stage[a + j - o.wbase];
@@ -469,7 +466,7 @@ __global__ void __launch_bounds__(256) k_bgzf_pack(const uint8_t* __restrict__ s
         if (v0 >= v1) continue;
         long long k = last_not_above(off, 0, nblocks, v0);
         if (v1 - v0 == 16 && v1 <= off[k + 1]) {
-            *reinterpret_cast<df_u32x4*>(comp + v0) = *reinterpret_cast<const df_u32x4_unaligned*>(slots + k * DF_SLOT + (v0 - off[k]));
+            *reinterpret_cast<u32x4*>(comp + v0) = *reinterpret_cast<const u32x4_unaligned*>(slots + k * DF_SLOT + (v0 - off[k]));
             continue;
         }
         for (long long q = v0; q < v1; ++q) {

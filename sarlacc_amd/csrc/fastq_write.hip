@@ -12,38 +12,21 @@
 //   (rocPRIM exclusive scan: n + 1 record offsets, the last one is the size of the text)
 //   k_fqw_format  the text of a contiguous record range                               (reads seq, qual, names once; writes the text once)
 //
-// k_fqw_format divides the work by OUTPUT bytes, not by records (reads run from 0 to tens of kilobases in one batch):
-// a wavefront takes tiles of 4 KB of the text, every lane four 16-byte pieces of it, 1 KB apart, so that each of the
-// wavefront's store instructions writes 1 KB of consecutive, 16-byte aligned addresses.  A tile finds its first and last
-// record by binary search in the record offsets; a lane searches only between those two (no search at all where the tile
-// lies inside one record).  A piece that lies inside one name, sequence or quality string is one unaligned 16-byte load --
+// k_fqw_format divides the work by OUTPUT bytes, not by records: it is a body of out_tiles.hpp's walk_out_tiles, which
+// hands it 16-byte pieces of the text, aligned in memory, with the record each starts in.
+// A piece that lies inside one name, sequence or quality string is one unaligned 16-byte load --
 // source and destination are misaligned against each other by a different amount for every record and string, so the
 // loads are the unaligned side --; a piece that holds a separator, the digits of a default name, a string's first or last
 // bytes or the ends of the text is put together byte by byte.
 //
 // Compressed output is bgzf_deflate.hip's, on the text this file leaves in device memory.
 // Out of scope: multi-line FASTQ, a repeated name on the '+' line.
-#include "common.hpp"
-#include "devprim.hpp"
+#include "out_tiles.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
 namespace sarlacc {
 namespace {
-
-constexpr int FW_THREADS = 256;
-constexpr int FW_PIECES = 4;                      // 16-byte pieces per lane and tile
-constexpr int FW_TILE = 64 * 16 * FW_PIECES;      // bytes of text per wavefront and step
-constexpr int FW_NAME_PREFIX = 5;                 // "READ_"
-
-typedef uint32_t __attribute__((ext_vector_type(4))) fw_u32x4;
-typedef fw_u32x4 __attribute__((aligned(1))) fw_u32x4_unaligned;
-
-__device__ __forceinline__ int decimal_width(unsigned long long v) {
-    int w = 1;
-    while (v >= 10) { v /= 10; ++w; }
-    return w;
-}
 
 // non-zero iff one of the four bytes of w is '\n' or '\r'
 __device__ __forceinline__ uint32_t line_break4(uint32_t w) {
@@ -59,7 +42,7 @@ __global__ void __launch_bounds__(256) k_fqw_size(const int64_t* off, const uint
     const long long nthreads = static_cast<long long>(gridDim.x) * blockDim.x;
     for (long long r = tid; r < n; r += nthreads) {
         const long long nl = names ? name_off[r + 1] - name_off[r]
-                                   : FW_NAME_PREFIX + decimal_width(static_cast<unsigned long long>(first_index + r));
+                                   : NAME_PREFIX + decimal_width(static_cast<unsigned long long>(first_index + r));
         len[r] = nl + 2 * (off[r + 1] - off[r]) + 6;
     }
     if (tid == 0) len[n] = 0;
@@ -69,7 +52,7 @@ __global__ void __launch_bounds__(256) k_fqw_size(const int64_t* off, const uint
     for (long long p = nb0 + 16 * tid; p < nb1; p += 16 * nthreads) {
         const int k = static_cast<int>(nb1 - p < 16 ? nb1 - p : 16);
         if (k == 16) {
-            const fw_u32x4 v = *reinterpret_cast<const fw_u32x4_unaligned*>(names + p);
+            const u32x4 v = *reinterpret_cast<const u32x4_unaligned*>(names + p);
             if (!(line_break4(v.x) | line_break4(v.y) | line_break4(v.z) | line_break4(v.w))) continue;
         }
         for (int j = 0; j < k; ++j) {
@@ -96,14 +79,8 @@ __device__ __forceinline__ uint64_t byte_mask(int a, int b) {
     return (b - a == 8 ? ~0ull : (1ull << (8 * (b - a))) - 1) << (8 * a);
 }
 
-// the 16 bytes a lane puts together before it stores them
-struct FwPiece {
-    uint64_t lo = 0, hi = 0;
-
-    __device__ __forceinline__ void put(int d, uint8_t c) {
-        if (d < 8) lo |= static_cast<uint64_t>(c) << (8 * d); else hi |= static_cast<uint64_t>(c) << (8 * (d - 8));
-    }
-
+// OutPiece, and whole strings into it
+struct FwPiece : OutPiece {
     // bytes [d, d + m) = bytes [x, x + m) of the string s of len bytes.  One unaligned 16-byte load that stays inside the
     // string, shifted to its place; a string shorter than that byte by byte.
     __device__ __forceinline__ void put_string(int d, int m, const uint8_t* s, long long len, long long x) {
@@ -114,7 +91,7 @@ struct FwPiece {
         long long y = x - d;
         y = y < 0 ? 0 : y;
         y = y > len - 16 ? len - 16 : y;
-        const fw_u32x4 v = *reinterpret_cast<const fw_u32x4_unaligned*>(s + y);
+        const u32x4 v = *reinterpret_cast<const u32x4_unaligned*>(s + y);
         uint64_t a = v.x | static_cast<uint64_t>(v.y) << 32, b = v.z | static_cast<uint64_t>(v.w) << 32;
         const int up = d - static_cast<int>(x - y);   // bytes towards the end of the piece, -15 .. 15
         if (up >= 8) { b = a << (8 * (up - 8)); a = 0; }
@@ -139,14 +116,6 @@ struct FwSource {
         R.sl = off[r + 1] - R.so;
         if (names) { R.no = name_off[r]; R.nl = name_off[r + 1] - R.no; }
         else R.nl = R.len - 2 * R.sl - 6;
-    }
-
-    // character k of record R's default name
-    __device__ __forceinline__ uint8_t default_name(const FwRec& R, long long k) const {
-        if (k < FW_NAME_PREFIX) return static_cast<uint8_t>("READ_"[k]);
-        unsigned long long v = static_cast<unsigned long long>(first_index + R.r);
-        for (long long d = R.nl - 1 - k; d > 0; --d) v /= 10;   // digit k - 5 of nl - 5, from the left
-        return static_cast<uint8_t>('0' + v % 10);
     }
 
     // the string 16 consecutive bytes of record R from byte q lie in, or null
@@ -174,7 +143,7 @@ struct FwSource {
             if (a >= e) continue;
             const int dd = d + static_cast<int>(a - q), mm = static_cast<int>(e - a);
             if (k == 0 && !names) {
-                for (int c = 0; c < mm; ++c) P.put(dd + c, default_name(R, a - name + c));
+                for (int c = 0; c < mm; ++c) P.put(dd + c, default_name_char(static_cast<unsigned long long>(first_index + R.r), R.nl, a - name + c));
             } else {
                 P.put_string(dd, mm, k == 0 ? names + R.no : (k == 1 ? seq : qual) + R.so, len[k], a - begin[k]);
             }
@@ -183,57 +152,31 @@ struct FwSource {
 };
 
 // text[0 .. ) = bytes rec_off[first] .. rec_off[first + count] of the whole text
-__global__ void __launch_bounds__(FW_THREADS) k_fqw_format(FwSource S, long long first, long long count, uint8_t* text) {
-    const long long base = S.rec_off[first], nbytes = S.rec_off[first + count] - base;
-    const int mis = static_cast<int>(reinterpret_cast<uintptr_t>(text) & 15);   // pieces are aligned in memory, not in the text
-    const long long ntiles = (nbytes + mis + FW_TILE - 1) / FW_TILE;
-    const int lane = threadIdx.x & 63;
-    const long long wave = blockIdx.x * static_cast<long long>(FW_THREADS / 64) + (threadIdx.x >> 6);
-    const long long nwaves = static_cast<long long>(gridDim.x) * (FW_THREADS / 64);
+__global__ void __launch_bounds__(OT_THREADS) k_fqw_format(FwSource S, long long first, long long count, uint8_t* text) {
     FwRec R;
-    for (long long tile = wave; tile < ntiles; tile += nwaves) {
-        const long long t0 = tile * FW_TILE - mis;
-        const long long tile_lo = t0 > 0 ? t0 : 0, tile_hi = (t0 + FW_TILE < nbytes ? t0 + FW_TILE : nbytes) - 1;
-        // first and last record of the tile (the same in every lane)
-        const long long r_lo = last_not_above(S.rec_off, first, first + count, base + tile_lo);
-        const long long r_hi = S.rec_off[r_lo + 1] > base + tile_hi ? r_lo
-                                                                   : last_not_above(S.rec_off, r_lo, first + count, base + tile_hi);
-#pragma unroll 1
-        for (int k = 0; k < FW_PIECES; ++k) {
-            const long long p0 = t0 + (k * 64 + lane) * 16;
-            const long long v0 = p0 > 0 ? p0 : 0, v1 = p0 + 16 < nbytes ? p0 + 16 : nbytes;   // head and tail of the text
-            if (v0 >= v1) continue;
-            const long long r = last_not_above(S.rec_off, r_lo, r_hi + 1, base + v0);
-            if (r != R.r) S.load(R, r);
-            long long q = base + v0 - R.start;
-            const bool whole = v1 - v0 == 16;
-            const uint8_t* src = whole ? S.inside(R, q) : nullptr;
-            if (src) {
-                *reinterpret_cast<fw_u32x4*>(text + p0) = *reinterpret_cast<const fw_u32x4_unaligned*>(src);
-                continue;
-            }
-            // separators, default names, the ends of strings, of records and of the text: record by record
-            const int d0 = static_cast<int>(v0 - p0), d1 = static_cast<int>(v1 - p0);
-            FwPiece P;
-#pragma unroll 1
-            for (int d = d0; d < d1;) {
-                if (q >= R.len) { q = 0; S.load(R, R.r + 1); }
-                const int m = static_cast<int>(R.len - q < d1 - d ? R.len - q : d1 - d);
-                S.part(P, d, m, R, q);
-                d += m;
-                q += m;
-            }
-            if (whole) {
-                fw_u32x4 v;
-                v.x = static_cast<uint32_t>(P.lo); v.y = static_cast<uint32_t>(P.lo >> 32);
-                v.z = static_cast<uint32_t>(P.hi); v.w = static_cast<uint32_t>(P.hi >> 32);
-                *reinterpret_cast<fw_u32x4*>(text + p0) = v;
-            } else {
-#pragma unroll 1
-                for (int d = d0; d < d1; ++d) text[p0 + d] = static_cast<uint8_t>((d < 8 ? P.lo : P.hi) >> (8 * (d & 7)));
-            }
+    walk_out_tiles<OT_THREADS / 64, OT_PIECES>(S.rec_off, first, first + count, text,
+                                               [&](long long base, long long p0, long long v0, long long v1, long long r, long long) {
+        if (r != R.r) S.load(R, r);
+        long long q = base + v0 - R.start;
+        const bool whole = v1 - v0 == 16;
+        const uint8_t* src = whole ? S.inside(R, q) : nullptr;
+        if (src) {
+            *reinterpret_cast<u32x4*>(text + p0) = *reinterpret_cast<const u32x4_unaligned*>(src);
+            return;
         }
-    }
+        // separators, default names, the ends of strings, of records and of the text: record by record
+        const int d0 = static_cast<int>(v0 - p0), d1 = static_cast<int>(v1 - p0);
+        FwPiece P;
+#pragma unroll 1
+        for (int d = d0; d < d1;) {
+            if (q >= R.len) { q = 0; S.load(R, R.r + 1); }
+            const int m = static_cast<int>(R.len - q < d1 - d ? R.len - q : d1 - d);
+            S.part(P, d, m, R, q);
+            d += m;
+            q += m;
+        }
+        P.store(text + p0, d0, d1, whole);
+    });
 }
 
 }  // namespace
@@ -245,56 +188,24 @@ extern "C" {
 
 int sarlacc_dev_fastq_format_size(const int64_t* d_off, int64_t n, const uint8_t* d_names, const int64_t* d_name_off,
                                   int64_t first_index, int64_t* d_rec_off, int64_t* total_bytes, void* stream) {
-    if (n < 0 || first_index < 0 || !total_bytes) return fail("sarlacc_amd: bad FASTQ format request");
-    if ((d_names == nullptr) != (d_name_off == nullptr)) return fail("sarlacc_amd: read names and their offsets go together");
-    SL_TRY(ensure_device());
     hipStream_t s = static_cast<hipStream_t>(stream);
-    *total_bytes = 0;
-    if (n == 0) {
-        SL_HIP(hipMemsetAsync(d_rec_off, 0, sizeof(int64_t), s));
-        SL_HIP(hipStreamSynchronize(s));
-        return 0;
-    }
-    Context& c = ctx();
-    long long* d_len; unsigned long long* d_bad;
-    SL_TRY(scratch("fqw.len", static_cast<size_t>(n) + 1, &d_len));
-    SL_TRY(scratch("fqw.bad", 1, &d_bad));
-    SL_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), s));
-    c.stage_reset("fastq_size");
-    SL_TRY(c.stage_begin("fastq_size", s));
-    hipLaunchKernelGGL(k_fqw_size, dim3(nblk(n, 256)), dim3(256), 0, s, d_off, d_names, d_name_off,
-                       static_cast<long long>(first_index), static_cast<long long>(n), d_len, d_bad);
-    SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan("fqw.scan", d_len, d_rec_off, static_cast<size_t>(n) + 1, s));
-    SL_TRY(c.stage_end("fastq_size", s));
-    unsigned long long bad = 0;
-    int64_t total = 0;
-    SL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipMemcpyAsync(&total, d_rec_off + n, sizeof total, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipStreamSynchronize(s));
-    if (bad != ~0ull) return fail("record %lld: read name holds a line break", static_cast<long long>(bad) + 1);
-    *total_bytes = total;
-    return 0;
+    return format_size_pass("FASTQ", "fqw", "fastq_size", n, d_names, d_name_off, first_index, d_rec_off, total_bytes, s,
+        [&](Context&, long long* d_len, unsigned long long* d_bad) {
+            hipLaunchKernelGGL(k_fqw_size, dim3(nblk(n, 256)), dim3(256), 0, s, d_off, d_names, d_name_off,
+                               static_cast<long long>(first_index), static_cast<long long>(n), d_len, d_bad);
+        },
+        [] {},
+        [](unsigned long long bad) { return fail("record %lld: read name holds a line break", static_cast<long long>(bad) + 1); });
 }
 
 int sarlacc_dev_fastq_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
                              const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
                              int64_t count, uint8_t* d_text, void* stream) {
-    if (first < 0 || count < 0 || first_index < 0) return fail("sarlacc_amd: bad FASTQ format request");
-    if ((d_names == nullptr) != (d_name_off == nullptr)) return fail("sarlacc_amd: read names and their offsets go together");
-    if (count == 0) return 0;
-    SL_TRY(ensure_device());
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Context& c = ctx();
-    const FwSource src{d_seq, d_qual, d_off, d_names, d_name_off, static_cast<long long>(first_index), d_rec_off};
-    // the size of the range is known on the device only: a resident grid whose wavefronts stride over the tiles
-    c.stage_reset("fastq_format");
-    SL_TRY(c.stage_begin("fastq_format", s));
-    hipLaunchKernelGGL(k_fqw_format, dim3(static_cast<unsigned>(c.num_cu) * 8), dim3(FW_THREADS), 0, s, src,
-                       static_cast<long long>(first), static_cast<long long>(count), d_text);
-    SL_HIP(hipGetLastError());
-    SL_TRY(c.stage_end("fastq_format", s));
-    SL_HIP(hipStreamSynchronize(s));
-    return 0;
+    return format_range("FASTQ", "fastq_format", d_names, d_name_off, first_index, first, count, s, [&](dim3 grid) {
+        const FwSource src{d_seq, d_qual, d_off, d_names, d_name_off, static_cast<long long>(first_index), d_rec_off};
+        hipLaunchKernelGGL(k_fqw_format, grid, dim3(OT_THREADS), 0, s, src, static_cast<long long>(first),
+                           static_cast<long long>(count), d_text);
+    });
 }
 }

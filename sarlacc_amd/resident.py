@@ -2,6 +2,7 @@
 once and stay in HBM while they are windowed, shuffled and aligned many times -- the access
 pattern of tuneAlignment / getAdaptorThresholds (/root/reference/R/tuneAlignment.R,
 R/getAdaptorThresholds.R).  No torch needed: allocation and copies go through the C ABI."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -63,6 +64,12 @@ def _record_ranges(ro, block_bytes):
     return ranges
 
 
+# What a writer needs to format any record range of a batch (DeviceReads._write_plan): the library's range formatter,
+# the device buffers of names, name offsets, n + 1 record offsets and (BAM) cuts, the host copy `ro` of the record
+# offsets and the record ranges [(first, last)] of the blocks.
+WritePlan = collections.namedtuple("WritePlan", "format names noff rec_off cuts ro ranges")
+
+
 class DeviceReads:
     """seq / qual / offsets in HBM + the host copy of the offsets."""
 
@@ -108,15 +115,41 @@ class DeviceReads:
     def _from_device_text(cls, text_ptr, nbytes, encoding):
         nrec, tb, tn = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(_lib.lib().sarlacc_dev_fastq_index(text_ptr, int(nbytes), C.byref(nrec), C.byref(tb), C.byref(tn), None))
-        n = nrec.value
-        seq, qual = DevBuffer(max(tb.value, 1)), DevBuffer(max(tb.value, 1))
-        off, names, noff = DevBuffer(8 * (n + 1)), DevBuffer(max(tn.value, 1)), DevBuffer(8 * (n + 1))
-        check(_lib.lib().sarlacc_dev_fastq_extract(text_ptr, seq, qual, off, names, noff, None))
+        return cls._extracted(nrec.value, tb.value, tn.value, encoding,
+                              lambda *bufs: check(_lib.lib().sarlacc_dev_fastq_extract(text_ptr, *bufs, None)))
+
+    @classmethod
+    def _extracted(cls, n, bases, name_bytes, encoding, extract):
+        """A resident batch of n reads with `bases` bases and `name_bytes` bytes of names, once
+        extract(seq, qual, off, names, name_off) has filled its device buffers; `.names` is a StrList over the names."""
+        seq, qual = DevBuffer(max(bases, 1)), DevBuffer(max(bases, 1))
+        off, names, noff = DevBuffer(8 * (n + 1)), DevBuffer(max(name_bytes, 1)), DevBuffer(8 * (n + 1))
+        extract(seq, qual, off, names, noff)
         out = cls(seq, qual, off, off.to_numpy(np.int64, n + 1), encoding)
         from .strset import StrList
-        nraw = names.to_numpy(np.uint8, tn.value)
+        nraw = names.to_numpy(np.uint8, name_bytes)
         out.names = StrList(StringSet(nraw if nraw.size else np.zeros(1, np.uint8), noff.to_numpy(np.int64, n + 1)))   # decoded on demand
         return out
+
+    @classmethod
+    def _text_chunks(cls, address, nbytes, number, eof, encoding):
+        """Generator over the chunks of at most `number` records in the nbytes of FASTQ text at the device address:
+        where the text ends inside a chunk and more follows (not eof) the chunk is left for the next buffer.  Returns
+        the bytes used."""
+        pos = 0
+        while pos < nbytes:
+            nrec, used = C.c_int64(0), C.c_int64(0)
+            here = address + pos
+            check(_lib.lib().sarlacc_dev_fastq_split(here, nbytes - pos, number, C.byref(nrec), C.byref(used), None))
+            if nrec.value < number and not eof:
+                break                           # the chunk continues in the next buffer
+            if nrec.value < number:
+                used.value = nbytes - pos       # last chunk: may end without a newline, or in blank lines
+            chunk = cls._from_device_text(here, used.value, encoding)
+            pos += used.value
+            if len(chunk):
+                yield chunk
+        return pos
 
     @classmethod
     def stream_fastq(cls, path, number, encoding=None, block_bytes=256 << 20):
@@ -148,19 +181,7 @@ class DeviceReads:
                 if text.size == 0:
                     break
                 d_text = DevBuffer.from_numpy(text)
-                pos = 0
-                while pos < text.size:
-                    nrec, used = C.c_int64(0), C.c_int64(0)
-                    here = d_text.ptr.value + pos
-                    check(_lib.lib().sarlacc_dev_fastq_split(here, text.size - pos, number, C.byref(nrec), C.byref(used), None))
-                    if nrec.value < number and not eof:
-                        break                           # the chunk continues in the next block
-                    if nrec.value < number:
-                        used.value = text.size - pos    # last chunk: may end without a newline, or in blank lines
-                    chunk = cls._from_device_text(here, used.value, encoding)
-                    pos += used.value
-                    if len(chunk):
-                        yield chunk
+                pos = yield from cls._text_chunks(d_text.ptr.value, text.size, number, eof, encoding)
                 carry = text[pos:].copy()
 
     @classmethod
@@ -173,19 +194,7 @@ class DeviceReads:
             d_text, nbytes, eof = stream.next(carry)
             if d_text is None or nbytes == 0:
                 break
-            pos = 0
-            while pos < nbytes:
-                nrec, used = C.c_int64(0), C.c_int64(0)
-                here = d_text.ptr.value + pos
-                check(_lib.lib().sarlacc_dev_fastq_split(here, nbytes - pos, number, C.byref(nrec), C.byref(used), None))
-                if nrec.value < number and not eof:
-                    break                           # the chunk continues in the next blocks
-                if nrec.value < number:
-                    used.value = nbytes - pos
-                chunk = cls._from_device_text(here, used.value, encoding)
-                pos += used.value
-                if len(chunk):
-                    yield chunk
+            pos = yield from cls._text_chunks(d_text.ptr.value, nbytes, number, eof, encoding)
             carry = (d_text, pos, nbytes - pos) if pos < nbytes else None
 
     @classmethod
@@ -261,18 +270,14 @@ class DeviceReads:
         tb, tn, nxt = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         if count:
             check(lib.sarlacc_dev_bam_reads_range(first, count, C.byref(tb), C.byref(tn), C.byref(nxt)))
-        seq, qual = DevBuffer(max(tb.value, 1)), DevBuffer(max(tb.value, 1))
-        off, names, noff = DevBuffer(8 * (count + 1)), DevBuffer(max(tn.value, 1)), DevBuffer(8 * (count + 1))
-        if count:
-            check(lib.sarlacc_dev_bam_reads_extract(d_bam, first, count, missing_qual, seq, qual, off, names, noff, None))
-            off_host, noff_host = off.to_numpy(np.int64, count + 1), noff.to_numpy(np.int64, count + 1)
-        else:
-            off_host, noff_host = np.zeros(1, np.int64), np.zeros(1, np.int64)
-            check(lib.sarlacc_dev_upload(off, off_host, 8))
-        out = cls(seq, qual, off, off_host, phred_encoding())
-        from .strset import StrList
-        nraw = names.to_numpy(np.uint8, tn.value)
-        out.names = StrList(StringSet(nraw if nraw.size else np.zeros(1, np.uint8), noff_host))   # decoded on demand
+
+        def extract(seq, qual, off, names, noff):
+            if count:
+                check(lib.sarlacc_dev_bam_reads_extract(d_bam, first, count, missing_qual, seq, qual, off, names, noff, None))
+            else:       # no reads: offsets that start at 0
+                for buf in (off, noff):
+                    check(lib.sarlacc_dev_upload(buf, np.zeros(1, np.int64), 8))
+        out = cls._extracted(count, tb.value, tn.value, phred_encoding(), extract)
         return (out, nxt.value) if with_next else out
 
     def __len__(self):
@@ -304,39 +309,63 @@ class DeviceReads:
             raise _lib.SarlaccError("%d read names for %d reads" % (len(ss), len(self)))
         return ss
 
-    def _fastq_plan(self, block_bytes):
-        """The size pass of the device FASTQ writer (sarlacc_dev_fastq_format_size; refuses names with a line break) and
-        the record ranges of the blocks: the largest run of whole records whose text fits in `block_bytes` (None:
-        everything), a single record larger than that in a block of its own size."""
+    def _write_plan(self, block_bytes, bam=False):
+        """The size pass of the device FASTQ writer (sarlacc_dev_fastq_format_size; refuses names with a line break) or,
+        with `bam`, of the device BAM writer (sarlacc_dev_bam_format_size; refuses what BAM cannot hold, and leaves the
+        SEQ and QUAL starts as `cuts`), and the record ranges of _record_ranges over the n + 1 record offsets `ro`.  The
+        host knows every length of a FASTQ record and computes `ro` itself; the kept part of a BAM name is decided on
+        the device, so there `ro` is downloaded.  Names, name offsets, record offsets and cuts stay on the device."""
         n = len(self)
         ss = self._name_set()
-        names = noff = None
-        if ss is not None:
-            names, noff = DevBuffer.from_numpy(ss.chars), DevBuffer.from_numpy(ss.off)
+        names = noff = cuts = None
+        if ss is not None:      # (names that are all empty: the library tells "no names" by a null pointer)
+            names, noff = DevBuffer.from_numpy(ss.chars if ss.chars.size else np.zeros(1, np.uint8)), DevBuffer.from_numpy(ss.off)
         rec_off, total = DevBuffer(8 * (n + 1)), C.c_int64(0)
-        check(_lib.lib().sarlacc_dev_fastq_format_size(self.off, n, names, noff, 1, rec_off, C.byref(total), None))
-        # the host knows every length too: it plans the ranges itself
-        if ss is not None:
-            name_len = np.diff(ss.off)
-        else:   # READ_<k>, k = 1 .. n
-            name_len = 6 + np.searchsorted(10 ** np.arange(1, 19, dtype=np.int64), np.arange(1, n + 1, dtype=np.int64), side="right")
-        ro = np.zeros(n + 1, np.int64)
-        np.cumsum(name_len + 2 * np.diff(self.off_host) + 6, out=ro[1:])
-        return names, noff, rec_off, ro, _record_ranges(ro, block_bytes)
+        if bam:
+            cuts = DevBuffer(max(16 * n, 8))
+            check(_lib.lib().sarlacc_dev_bam_format_size(self.seq, self.qual, self.off, n, names, noff, 1, rec_off, cuts,
+                                                         C.byref(total), None))
+            ro = rec_off.to_numpy(np.int64, n + 1)
+        else:
+            check(_lib.lib().sarlacc_dev_fastq_format_size(self.off, n, names, noff, 1, rec_off, C.byref(total), None))
+            if ss is not None:
+                name_len = np.diff(ss.off)
+            else:   # READ_<k>, k = 1 .. n
+                name_len = 6 + np.searchsorted(10 ** np.arange(1, 19, dtype=np.int64), np.arange(1, n + 1, dtype=np.int64), side="right")
+            ro = np.zeros(n + 1, np.int64)
+            np.cumsum(name_len + 2 * np.diff(self.off_host) + 6, out=ro[1:])
+        format_range = _lib.lib().sarlacc_dev_bam_format if bam else _lib.lib().sarlacc_dev_fastq_format
+        return WritePlan(format_range, names, noff, rec_off, cuts, ro, _record_ranges(ro, block_bytes))
 
-    def _fastq_blocks(self, plan):
-        """Generator over the blocks of a _fastq_plan, formatted on the device (sarlacc_dev_fastq_format): each a uint8
-        view of ONE reused page-locked buffer, valid until the next block is asked for."""
-        names, noff, rec_off, ro, ranges = plan
-        if not ranges:
+    def _blocks(self, plan, compress=False, head=None):
+        """Generator over the blocks of a WritePlan: `head` (bytes that go in front as a block of their own), then every
+        record range, formatted on the device (plan.format).  With `compress` a block is deflated where it lies into
+        BGZF blocks (bgzf.deflate_device, with the plan's cuts as piece boundaries where it has them) and only the
+        compressed bytes are downloaded.  Each block is a uint8 view of ONE reused page-locked buffer, valid until the
+        next block is asked for."""
+        from . import bgzf
+        sizes = [int(plan.ro[b] - plan.ro[a]) for a, b in plan.ranges]
+        largest = max(sizes + [0 if head is None else head.size])
+        if not largest:
             return
-        largest = max(int(ro[b] - ro[a]) for a, b in ranges)
-        d_text, host = DevBuffer(largest), _lib.host_array(largest, np.uint8)
-        for a, b in ranges:
-            nbytes = int(ro[b] - ro[a])
-            check(_lib.lib().sarlacc_dev_fastq_format(self.seq, self.qual, self.off, names, noff, 1, rec_off, a, b - a, d_text, None))
-            check(_lib.lib().sarlacc_dev_download(host, d_text, nbytes))
-            yield host[:nbytes]
+        cap = bgzf.deflate_bound(largest)[1] if compress else largest
+        d_raw, host = DevBuffer(largest), _lib.host_array(cap, np.uint8)
+        d_out = DevBuffer(cap) if compress else d_raw
+
+        def block(nbytes, **cuts):
+            if compress:
+                nbytes = bgzf.deflate_device(d_raw, nbytes, out=d_out, **cuts)[1]
+            check(_lib.lib().sarlacc_dev_download(host, d_out, nbytes))
+            return host[:nbytes]
+        if head is not None:
+            check(_lib.lib().sarlacc_dev_upload(d_raw, head, head.size))
+            yield block(head.size)
+        for (a, b), nbytes in zip(plan.ranges, sizes):
+            check(plan.format(self.seq, self.qual, self.off, plan.names, plan.noff, 1, plan.rec_off, a, b - a, d_raw, None))
+            if plan.cuts is None:
+                yield block(nbytes)
+            else:
+                yield block(nbytes, cuts=(plan.cuts.ptr.value + 16 * a, 2 * (b - a)), cut_origin=int(plan.ro[a]))
 
     def fastq_text(self, block_bytes=None):
         """The batch as 4-line FASTQ text (bytes), formatted on the device: record i is
@@ -348,23 +377,7 @@ class DeviceReads:
         download buffer, a copy per block, the joined result) and, with block_bytes=None, once on the device: this is for
         batches whose text fits comfortably; to_fastq is the bounded route.  Not done here: gzip output, multi-line FASTQ, a
         repeated name on the '+' line."""
-        return b"".join(blk.tobytes() for blk in self._fastq_blocks(self._fastq_plan(block_bytes)))
-
-    def _fastq_bgzf_blocks(self, plan, mode=0):
-        """_fastq_blocks, compressed: every block of text is formatted as there, deflated where it lies into BGZF blocks
-        (bgzf.deflate_device) and only the compressed bytes are downloaded, again into ONE reused page-locked buffer."""
-        from . import bgzf
-        names, noff, rec_off, ro, ranges = plan
-        if not ranges:
-            return
-        largest = max(int(ro[b] - ro[a]) for a, b in ranges)
-        cap = bgzf.deflate_bound(largest)[1]
-        d_text, d_comp, host = DevBuffer(largest), DevBuffer(cap), _lib.host_array(cap, np.uint8)
-        for a, b in ranges:
-            check(_lib.lib().sarlacc_dev_fastq_format(self.seq, self.qual, self.off, names, noff, 1, rec_off, a, b - a, d_text, None))
-            _, nbytes = bgzf.deflate_device(d_text, int(ro[b] - ro[a]), mode, out=d_comp)
-            check(_lib.lib().sarlacc_dev_download(host, d_comp, nbytes))
-            yield host[:nbytes]
+        return b"".join(blk.tobytes() for blk in self._blocks(self._write_plan(block_bytes)))
 
     def to_fastq(self, path, append=False, block_bytes=256 << 20, compress=False):
         """Writes fastq_text() to `path` (after what is there with append=True) and returns the bytes written.  The
@@ -378,35 +391,20 @@ class DeviceReads:
         last of them -- alone for an empty batch.  The count returned is that of the file's new bytes.  append=True leaves
         the end-of-file block of what was there in the middle, an empty member that BGZF permits.  Compression is never
         inferred from the name of the file."""
-        plan = self._fastq_plan(block_bytes)
-        written = 0
-        with open(path, "ab" if append else "wb") as fh:
-            if compress:
-                from .bgzf import EOF_BLOCK
-                for blk in self._fastq_bgzf_blocks(plan):
-                    fh.write(blk)
-                    written += blk.size
-                fh.write(EOF_BLOCK)
-                return written + len(EOF_BLOCK)
-            for blk in self._fastq_blocks(plan):
+        from .bgzf import EOF_BLOCK
+        return self._write_blocks(path, "ab" if append else "wb", self._blocks(self._write_plan(block_bytes), compress),
+                                  EOF_BLOCK if compress else b"")
+
+    @staticmethod
+    def _write_blocks(path, mode, blocks, end):
+        """Opens the file, writes the blocks with one write() each and `end` behind them; the bytes written."""
+        written = len(end)
+        with open(path, mode) as fh:
+            for blk in blocks:
                 fh.write(blk)
                 written += blk.size
+            fh.write(end)
         return written
-
-    def _bam_plan(self, block_bytes):
-        """The size pass of the device BAM writer (sarlacc_dev_bam_format_size; refuses what BAM cannot hold) and the
-        record ranges of _record_ranges over the record offsets it leaves, which come to the host: the kept part of a
-        name is decided on the device.  (names, name offsets, record offsets, cuts) stay on the device."""
-        n = len(self)
-        ss = self._name_set()
-        names = noff = None
-        if ss is not None:
-            names, noff = DevBuffer.from_numpy(ss.chars if ss.chars.size else np.zeros(1, np.uint8)), DevBuffer.from_numpy(ss.off)
-        rec_off, cuts, total = DevBuffer(8 * (n + 1)), DevBuffer(max(16 * n, 8)), C.c_int64(0)
-        check(_lib.lib().sarlacc_dev_bam_format_size(self.seq, self.qual, self.off, n, names, noff, 1, rec_off, cuts,
-                                                     C.byref(total), None))
-        ro = rec_off.to_numpy(np.int64, n + 1)
-        return names, noff, rec_off, cuts, ro, _record_ranges(ro, block_bytes)
 
     def to_bam(self, path, header=None, block_bytes=256 << 20):
         """Writes the batch to `path` as unaligned BAM (uBAM: what basecallers write and every long-read mapper and
@@ -433,26 +431,8 @@ class DeviceReads:
         if kind != "phred":
             raise _lib.SarlaccError("BAM stores Phred values: the batch's quality encoding is %s, not Phred+33" % kind)
         head = np.frombuffer(sam.bam_header_bytes(header), np.uint8)
-        names, noff, rec_off, cuts, ro, ranges = self._bam_plan(block_bytes)
-        largest = max([head.size] + [int(ro[b] - ro[a]) for a, b in ranges])
-        cap = bgzf.deflate_bound(largest)[1]
-        d_rec, d_comp, host = DevBuffer(largest), DevBuffer(cap), _lib.host_array(cap, np.uint8)
-        lib, written = _lib.lib(), 0
-        with open(path, "wb") as fh:
-            check(lib.sarlacc_dev_upload(d_rec, head, head.size))
-            _, nbytes = bgzf.deflate_device(d_rec, head.size, out=d_comp)
-            check(lib.sarlacc_dev_download(host, d_comp, nbytes))
-            fh.write(host[:nbytes])
-            written += nbytes
-            for a, b in ranges:
-                check(lib.sarlacc_dev_bam_format(self.seq, self.qual, self.off, names, noff, 1, rec_off, a, b - a, d_rec, None))
-                _, nbytes = bgzf.deflate_device(d_rec, int(ro[b] - ro[a]), out=d_comp, cuts=(cuts.ptr.value + 16 * a, 2 * (b - a)),
-                                                cut_origin=int(ro[a]))
-                check(lib.sarlacc_dev_download(host, d_comp, nbytes))
-                fh.write(host[:nbytes])
-                written += nbytes
-            fh.write(bgzf.EOF_BLOCK)
-        return written + len(bgzf.EOF_BLOCK)
+        plan = self._write_plan(block_bytes, bam=True)
+        return self._write_blocks(path, "wb", self._blocks(plan, compress=True, head=head), bgzf.EOF_BLOCK)
 
     def _like(self, off_host):
         total = int(off_host[-1])

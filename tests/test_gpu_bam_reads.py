@@ -119,6 +119,17 @@ def test_code_and_quality_domain(tmp_path):
     refused(tmp_path, file_of(good + [RC.read_record(b"late", 0, [1] * 20, [0] * 19 + [255])]), 13, RC.QUAL_HIGH)
 
 
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 1025])
+def test_domain_scan_at_its_step_edges(tmp_path, n):
+    """The size pass scans n bytes 16 per lane and 1 024 per wavefront step, the rest byte by byte: a bad last byte among
+    n bytes of SEQ (2 n bases, the code 0 in its low nibble) and of QUAL, and the same records without it are reads."""
+    good = RC.read_record(b"g", 0, [1, 2, 4, 8] * 3, [30] * 12)
+    seq_ok, qual_ok = RC.read_record(b"s", 0, [15] * (2 * n), [7] * (2 * n)), RC.read_record(b"q", 0, [2] * n, [93] * n)
+    both(tmp_path, file_of([good, seq_ok, qual_ok]), RC.reads(HEAD + good + seq_ok + qual_ok))
+    refused(tmp_path, file_of([good, RC.read_record(b"s", 0, [15] * (2 * n - 1) + [0], [7] * (2 * n))]), 2, RC.SEQ_EQ)
+    refused(tmp_path, file_of([good, RC.read_record(b"q", 0, [2] * n, [93] * (n - 1) + [94])]), 2, RC.QUAL_HIGH)
+
+
 def test_flags(tmp_path):
     rng = np.random.default_rng(3)
     flags = [0, 4, 16, 0x100, 0x800, 0x910, 77, 141] * 4

@@ -202,6 +202,17 @@ def test_quality_bytes_outside_phred33(q):
         assert _refused([(b"n", b"G" * length, qual)]) == (1, Bw.QUAL)
 
 
+@pytest.mark.parametrize("length", [15, 16, 17, 1025])
+def test_domain_scan_at_its_step_edges(length):
+    """The lengths around the 16 bytes of a lane and one past the 1 024 of a wavefront step that the two tests above
+    leave out between them: a bad last base, a bad last quality, and the record without them."""
+    seq, qual = b"ACGT" * (length // 4) + b"N" * (length % 4), b"!" + b"~" * (length - 1)
+    assert _refused([GOOD, (b"n", seq[:-1] + b"=", qual)]) == (2, Bw.BASE)
+    assert _refused([GOOD, (b"n", seq, qual[:-1] + b"\x7f")]) == (2, Bw.QUAL)
+    batch = ([b"n"], [seq], [qual])
+    assert first_difference(sized(batch).format(), Bw.expected_records(*batch)) is None
+
+
 def test_names_at_the_limits():
     assert _refused([(b"n" * 255, b"A", b"I")]) == (1, Bw.NAME_LONG)
     assert _refused([(b"n" * 254 + b"x comment", b"A", b"I")]) == (1, Bw.NAME_LONG)

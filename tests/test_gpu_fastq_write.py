@@ -51,23 +51,25 @@ def resident(reads):
     return dev
 
 
-def abi_text(dev, first_index, first=0, count=None, shift=0):
-    """Default-name text of records [first, first + count) straight through the C ABI, written `shift` bytes into a buffer
-    (so that the destination is not 16-byte aligned); also returns the record offsets."""
+def abi_text(dev, first_index, first=0, count=None, shift=0, names=(None, None)):
+    """Text of records [first, first + count) straight through the C ABI, written `shift` bytes into a buffer (so that the
+    destination is not 16-byte aligned), with default names or with `names` (device buffers of the name bytes and their
+    offsets); also returns the record offsets."""
     from sarlacc_amd import _lib
     from sarlacc_amd._lib import check
     from sarlacc_amd.resident import DevBuffer
     lib, n = _lib.lib(), len(dev)
     count = n - first if count is None else count
     rec_off, total = DevBuffer(8 * (n + 1)), C.c_int64(-1)
-    check(lib.sarlacc_dev_fastq_format_size(dev.off.ptr, C.c_int64(n), None, None, C.c_int64(first_index), rec_off.ptr,
+    names, name_off = (b and b.ptr for b in names)
+    check(lib.sarlacc_dev_fastq_format_size(dev.off.ptr, C.c_int64(n), names, name_off, C.c_int64(first_index), rec_off.ptr,
                                             C.byref(total), None))
     ro = rec_off.to_numpy(np.int64, n + 1)
     assert total.value == ro[-1]
     nbytes = int(ro[first + count] - ro[first])
     guard = np.full(nbytes + shift + 32, 0xEE, np.uint8)
     d_text = DevBuffer.from_numpy(guard)
-    check(lib.sarlacc_dev_fastq_format(dev.seq.ptr, dev.qual.ptr, dev.off.ptr, None, None, C.c_int64(first_index), rec_off.ptr,
+    check(lib.sarlacc_dev_fastq_format(dev.seq.ptr, dev.qual.ptr, dev.off.ptr, names, name_off, C.c_int64(first_index), rec_off.ptr,
                                        C.c_int64(first), C.c_int64(count), C.c_void_p(d_text.ptr.value + shift), None))
     got = d_text.to_numpy(np.uint8, guard.size)
     assert (got[:shift] == 0xEE).all() and (got[shift + nbytes:] == 0xEE).all(), "bytes written outside the range"
@@ -121,6 +123,30 @@ def test_default_names(tmp_path):
     # a range of records, into a destination that is not 16-byte aligned
     got, _ = abi_text(dev, start, first=1, count=700, shift=5)
     assert got == literal[int(ro[1]):int(ro[701])]
+
+
+def test_given_names_at_every_record_boundary_and_misalignment(tmp_path):
+    """40 records of 0 - 70 bases with given names of 0 - 40 bytes, through the C ABI into a guarded buffer: the whole
+    batch at every misalignment 0 .. 15 of the destination, and split at every record boundary with both parts misaligned
+    (with default names a piece never lies inside a name, and only test_default_names misaligns the destination).  The
+    expected bytes are the host writer's."""
+    from sarlacc_amd import generics as G
+    from sarlacc_amd.resident import DevBuffer, DeviceReads
+    from sarlacc_amd.strset import StringSet
+    rng = np.random.default_rng(23)
+    lengths, name_lengths = rng.integers(0, 71, 40), rng.integers(0, 41, 40)
+    lengths[[3, 20]], name_lengths[[3, 21]] = (0, 70), (0, 40)
+    names, seqs, quals = draw(rng, lengths, name_lengths)
+    reads = G.Reads(seqs, quals, names)
+    want = host_text(tmp_path, reads)
+    ss = StringSet.from_strings(names)
+    dev, given = DeviceReads.upload(reads), (DevBuffer.from_numpy(ss.chars), DevBuffer.from_numpy(ss.off))
+    for shift in range(16):
+        assert abi_text(dev, 1, shift=shift, names=given)[0] == want, "misaligned by %d" % shift
+    for k in range(1, 40):
+        got = abi_text(dev, 1, 0, k, shift=k % 16, names=given)[0] + abi_text(dev, 1, k, 40 - k, shift=(3 * k) % 16, names=given)[0]
+        assert got == want, "split at record %d" % k
+    assert b"".join(abi_text(dev, 1, k, 1, shift=(5 * k) % 16, names=given)[0] for k in range(40)) == want
 
 
 def test_round_trip(tmp_path):
@@ -268,7 +294,8 @@ def test_host_plan_agrees_with_the_size_pass(mixed):
     rng = np.random.default_rng(21)
     _, seqs, quals = draw(rng, rng.integers(0, 41, 1005))
     for dev in (resident(reads), DeviceReads.upload(G.Reads(seqs, quals))):
-        _, _, rec_off, ro, ranges = dev._fastq_plan(100000)
+        plan = dev._write_plan(100000)
+        rec_off, ro, ranges = plan.rec_off, plan.ro, plan.ranges
         assert np.array_equal(rec_off.to_numpy(np.int64, len(dev) + 1), ro)
         assert ranges[0][0] == 0 and ranges[-1][1] == len(dev) and all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
         assert all(ro[b] - ro[a] <= 100000 or b == a + 1 for a, b in ranges)

@@ -84,13 +84,13 @@ def one_length(args, L):
     tag = "%d-base reads" % L
 
     # f: the size pass, the format pass, the copy of the same bytes
-    names, noff, rec_off, cuts, ro, _ = reads._bam_plan(None)
-    total = int(ro[-1])
+    plan = reads._write_plan(None, bam=True)
+    names, noff, rec_off, cuts, total = plan.names, plan.noff, plan.rec_off, plan.cuts, int(plan.ro[-1])
     say(out, "%s: %d reads, %.3f GB of bases and qualities -> %.3f GB of records" % (tag, n, 2 * reads.total / 1e9, total / 1e9))
     d_rec, d_copy = DevBuffer(total), DevBuffer(total)
     size_ms, format_ms, copy_ms = [], [], []
     for _ in range(3):
-        reads._bam_plan(None)
+        reads._write_plan(None, bam=True)
         size_ms.append(_lib.stage_ms("bam_format_size"))
         check(lib.sarlacc_dev_bam_format(reads.seq, reads.qual, reads.off, names, noff, 1, rec_off, 0, n, d_rec, None))
         format_ms.append(_lib.stage_ms("bam_format"))
