@@ -58,7 +58,9 @@ int64_t sarlacc_workspace_report(char* buf, int64_t cap);
  * <0 if it never ran. */
 double sarlacc_stage_ms(const char* name);
 /* Work counters of the last call that set them (for rooflines): "msa_pairs", "msa_cells" (banded DP
- * cells of the pairwise alignments), "consensus_cells" (rows x width); <0 if unset. */
+ * cells of the pairwise alignments), "consensus_cells" (rows x width); "consensus_route" (the kernels the vote ran:
+ * 0 k_consensus<false>, 1 k_consensus<true>, 2 k_consensus_q4, 3 k_consensus_qf then k_consensus_q4 on the groups it
+ * flagged, 4 k_consensus_code) and "consensus_vote_passes" (1 + the runs repeated for a longer boundary list); <0 if unset. */
 double sarlacc_stage_count(const char* name);
 /* Duration in ms of the DP kernel launches recorded by the last
  * sarlacc_dev_* align call (HIP events on the launch stream; a panel call: the sum over its DP launches); <0 if none. */

@@ -18,70 +18,17 @@
 //
 // This is the one streaming, HBM-bound stage of the path: 2 B in per alignment
 // cell (gapped base + quality), 2 B out per kept column.
-#include "msa_common.hpp"
-
-#include "../../include/sarlacc_amd.h"
+//
+// This file: the kernels and the two functions that launch them (at its end).  ConsArgs, the kernels' constants and the
+// launch plan are in consensus.hpp; which kernels a call runs, its tables, scratch, results, errors and the C entry
+// points are in consensus_host.cpp.
+#include "consensus.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <limits>
 
 namespace sarlacc {
-
-struct ConsArgs {
-    const uint8_t* aln;
-    const int64_t* aln_off;    // per row
-    const int64_t* grp_rows;   // [ngroups+1]
-    long long ngroups;
-    const uint8_t* qual;       // quality mode only
-    const int64_t* qual_off;   // per row (same row numbering as aln), or per read when row_read is set
-    const int32_t* row_read;   // optional: 1-based read id of every row (qualities stay in read order)
-    const double* right;       // [navail] log1p(-e)
-    const double* wrong;       // [navail] log(e/3)
-    const double* vec;         // k_consensus_q4: [(5 * navail + 1)][4] per-(read character, quality) additions to the A,C,G,T scores
-    int qoffset, navail, max_rows;
-    double mincov, pseudo, ln10;
-    const int64_t* out_off;    // [ngroups] start of the group's output (= offset of its first row)
-    uint8_t* cons;
-    uint8_t* phred;
-    double* lerr;              // optional
-    int32_t* cons_len;         // [ngroups]
-    int8_t* row_status;        // quality: 0 ok, 1 bad quality char, 2 shorter, 3 longer
-    unsigned long long* first_bad_char;  // basic: min byte index of an unknown character
-    // near-boundary columns to be resolved on the host
-    int* fix_count;
-    int fix_cap;
-    long long* fix_pos;        // output byte index
-    double* fix_val;           // 4 per entry: sorted scores (quality) or {max,total,0,0} (basic)
-    int* fix_grp;              // k_consensus_qf: group of the entry (entries of groups handed to the generic kernel are void)
-    // k_consensus_qf (fast path) and its hand-over to k_consensus_q4
-    const double* strip;       // [(navail + 1)][QF_STRIP][QF_SLOTS]: per quality the strip (w w w r w w w), replicated; last row zeros
-    int* gflag;                // per group: 1 = the fast kernel met something it does not handle; the generic kernel redoes the group
-    int only_flagged;          // k_consensus_q4: skip groups whose flag is 0
-    long long aln_bytes, qual_bytes;   // sizes of the two buffers (the fast kernel reads whole dwords)
-    // k_consensus_code: the rows as 16-bit vote codes written by the MSA stage (CodeSpec, common.hpp)
-    const uint16_t* codes;     // same offsets as aln, in cells
-    const double* strip8;      // [(navail + 1)][CODE_STRIP][QF_SLOTS]: (w w w r w w w w) per quality, zero row last
-    int* code_bad;             // smallest row with a quality below the encoding (INT_MAX: none)
-};
-
-__host__ __device__ __forceinline__ double r_log1pexp(double x) {
-    // R nmath log1pexp: x <= 18 -> log1p(exp x); 18 < x <= 33.3 -> x + exp(-x); else x
-    if (x <= 18.) return log1p(exp(x));
-    if (x > 33.3) return x;
-    return x + exp(-x);
-}
-
-// The reference's log error of a column from its four scores in ascending order: a running log-sum-exp, less the
-// largest score.  Host and device compile the same source, each against its own libm.
-__host__ __device__ __forceinline__ double log_error(double a, double b, double c, double d) {
-    double denom = a;
-    denom += r_log1pexp(b - denom);
-    denom += r_log1pexp(c - denom);
-    const double err3 = denom;
-    denom += r_log1pexp(d - denom);
-    return err3 - denom;
-}
 
 // ascending sort of four scores (5 compare-exchanges)
 __device__ __forceinline__ void sort4(double& a, double& b, double& c, double& d) {
@@ -290,8 +237,6 @@ __device__ __forceinline__ double fast_log1pexp(double x) {
     return static_cast<double>(__logf(1.0f + y));
 }
 
-constexpr int Q4_RB = 5;   // rows fetched per batch
-
 __global__ void __launch_bounds__(256, 4) k_consensus_q4(const ConsArgs A) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int nvec = 5 * A.navail + 1;
@@ -484,11 +429,6 @@ __global__ void __launch_bounds__(256, 4) k_consensus_q4(const ConsArgs A) {
 // back to back; anything else (N or other characters, a quality outside the table, quality strings
 // shorter or longer than their rows, the last bytes of a buffer) sets the group's flag and the group is
 // redone by k_consensus_q4 -- detection costs a few SWAR operations per dword and is exact.
-constexpr int QF_SLOTS = 16;
-constexpr int QF_STRIP = 7;
-constexpr int QF_ROWB = QF_STRIP * QF_SLOTS * 8;   // 896 bytes per quality value
-constexpr int QF_RB = 6;                           // rows per batch: two scans of three packed counts
-constexpr int QF_THREADS = 1024;
 
 // The results of the kept columns of a lane in k_consensus_qf / k_consensus_code (accumulators in code order A, C, T, G),
 // written from output position obase + o on: the first maximum in the order A, C, G, T (std::max_element) and the
@@ -717,8 +657,6 @@ __global__ void __launch_bounds__(QF_THREADS) k_consensus_qf(const ConsArgs A) {
 // 8-byte LDS reads at immediate offsets, four additions in row order; per row and lane one 8-byte load of four
 // codes, independent of everything else, so the next batch of rows is always in flight.  Same sums in the same
 // order as the other kernels.
-constexpr int QC_RB = 5;
-constexpr int QC_ROWB = CODE_STRIP * QF_SLOTS * 8;   // 1024 bytes per quality value
 typedef unsigned long long __attribute__((aligned(1))) cons_u64_unaligned;
 
 // The rows of one 256-column step: per row and lane one 8-byte load of four codes, requested one batch of rows
@@ -834,453 +772,38 @@ __global__ void k_consensus_compact(const uint8_t* cons, const uint8_t* phred, c
 }
 
 // ---------------------------------------------------------------------------
-// LDS table of k_consensus_qf (width QF_STRIP) and k_consensus_code (CODE_STRIP): per quality the strip (w w w r w ...)
-// of log(e/3) and log1p(-e), every double replicated for QF_SLOTS lanes; a zero row last
-static int upload_strip(const char* name, int width, const std::vector<double>& right, const std::vector<double>& wrong,
-                        const double** dev, hipStream_t s) {
-    const size_t n = right.size();
-    std::vector<double> strip((n + 1) * width * QF_SLOTS, 0.0);
-    for (size_t k = 0; k < n; ++k)
-        for (int i = 0; i < width; ++i)
-            for (int sl = 0; sl < QF_SLOTS; ++sl) strip[(k * width + i) * QF_SLOTS + sl] = (i == 3) ? right[k] : wrong[k];
-    double* d;
-    SL_TRY(upload(name, strip.data(), strip.size(), &d, s));
-    *dev = d;
+// One launch of the plan: the LDS attribute, the geometry and the launch all go by the one kernel name.
+static int launch(void (*kernel)(const ConsArgs), const ConsLaunch& l, const ConsArgs& a, hipStream_t s) {
+    if (l.raise_lds)   // dynamic LDS beyond the default 64 KB
+        SL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(l.lds)));
+    hipLaunchKernelGGL(kernel, dim3(l.grid), dim3(l.block), l.lds, s, a);
+    SL_HIP(hipGetLastError());
     return 0;
 }
 
-// The row table of the alignments in a.aln: row offsets from the first row (rel, one entry past the last row, which is
-// the rows' byte count), first row of every group (grows, ngroups + 1 entries) and output offset of every group.
-static int upload_rows(ConsArgs& a, const std::vector<int64_t>& rel, const int64_t* grows, int64_t ngroups,
-                       const std::vector<int64_t>& out_off, int max_rows, hipStream_t s) {
-    int64_t* d_aoff; int64_t* d_grows; int64_t* d_ooff;
-    SL_TRY(upload("cons.aoff", rel.data(), rel.size(), &d_aoff, s));
-    SL_TRY(upload("cons.grows", grows, static_cast<size_t>(ngroups) + 1, &d_grows, s));
-    SL_TRY(upload("cons.ooff", out_off.data(), out_off.size(), &d_ooff, s));
-    a.aln_off = d_aoff; a.grp_rows = d_grows; a.out_off = d_ooff; a.max_rows = max_rows; a.aln_bytes = rel.back();
-    return 0;
-}
-
-template <typename K>
-static hipError_t allow_lds(K* kernel, size_t bytes) {   // dynamic LDS beyond the default 64 KB
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-}
-
-static char phred_char(double le) {
-    const double q = std::min(std::round(-10 * le / std::log(10)), 93.0);
-    return static_cast<char>(static_cast<int>(q) + 33);
-}
-
-// Device part of the consensus: `a` arrives with the alignment rows, their offsets, the group
-// table, the output offsets and (quality mode) the quality strings already in HBM; this adds
-// the tables and scratch, launches the vote and resolves results and errors on the host.
-// aln_host (optional) is the host copy of the rows, used only to quote an unknown character.
-static int consensus_core(bool quality, ConsArgs a, int64_t ngroups, int64_t ng_eval, int64_t rows_eval, int64_t total,
-                          const std::vector<int64_t>& out_off, const char* aln_host, int struct_err_kind,
-                          double min_cov, double pseudo, const double* enc_errors, const char* enc_names, int enc_n,
-                          char* cons, char* phred, int64_t* cons_off, double* lerr, hipStream_t s, int64_t cons_cap = -1) {
-    Context& c = ctx();
-    int64_t* d_ooff = const_cast<int64_t*>(a.out_off);
-    std::vector<double> right, wrong;
-    if (quality) {
-        double* d_r; double* d_w;
-        right.resize(enc_n);
-        wrong.resize(enc_n);
-        for (int k = 0; k < enc_n; ++k) {  // (src/create_consensus.cpp:14,:218-226)
-            double e = enc_errors[k];
-            if (e > 0.99999999) e = 0.99999999;
-            else if (e < 0.00000001) e = 0.00000001;
-            right[k] = std::log1p(-e);
-            wrong[k] = std::log(e / 3);
-        }
-        SL_TRY(upload("cons.right", right.data(), right.size(), &d_r, s));
-        SL_TRY(upload("cons.wrong", wrong.data(), wrong.size(), &d_w, s));
-        a.right = d_r; a.wrong = d_w;
-        // k_consensus_q4: what a cell adds to (A, C, G, T) by read character (A, C, G, T, other) and
-        // quality; the last entry (gap, N, no quality left) adds nothing
-        std::vector<double> vec(static_cast<size_t>(5 * enc_n + 1) * 4, 0.0);
-        for (int code = 0; code < 5; ++code)
-            for (int k = 0; k < enc_n; ++k)
-                for (int bidx = 0; bidx < 4; ++bidx)
-                    vec[(static_cast<size_t>(code) * enc_n + k) * 4 + bidx] = (bidx == code) ? right[k] : wrong[k];
-        double* d_vec;
-        SL_TRY(upload("cons.vec", vec.data(), vec.size(), &d_vec, s));
-        a.vec = d_vec;
-        a.qoffset = static_cast<int>(enc_names[0]); a.navail = enc_n;
-        SL_TRY(upload_strip("cons.strip", QF_STRIP, right, wrong, &a.strip, s));                        // k_consensus_qf
-        if (a.codes) SL_TRY(upload_strip("cons.strip8", CODE_STRIP, right, wrong, &a.strip8, s));   // k_consensus_code
-    }
-    a.ngroups = ng_eval;
-    a.mincov = min_cov; a.pseudo = pseudo; a.ln10 = std::log(10);
-    const int max_rows = a.max_rows;
-
-    uint8_t* d_cons; uint8_t* d_phred; double* d_lerr = nullptr; int32_t* d_len; int8_t* d_status;
-    unsigned long long* d_badchar; int* d_fixn; long long* d_fixpos = nullptr; double* d_fixval = nullptr;
-    int fix_cap = 4096;
-    SL_TRY(scratch("cons.out", static_cast<size_t>(total), &d_cons));
-    SL_TRY(scratch("cons.phred", static_cast<size_t>(total), &d_phred));
-    if (lerr) SL_TRY(scratch("cons.lerr", static_cast<size_t>(total), &d_lerr));
-    SL_TRY(scratch("cons.len", static_cast<size_t>(ngroups), &d_len));
-    SL_TRY(scratch("cons.status", static_cast<size_t>(std::max<int64_t>(rows_eval, 1)), &d_status));
-    SL_TRY(scratch("cons.badchar", 1, &d_badchar));
-    SL_TRY(scratch("cons.fixn", 1, &d_fixn));
-    SL_HIP(hipMemsetAsync(d_status, 0, static_cast<size_t>(std::max<int64_t>(rows_eval, 1)), s));
-    SL_HIP(hipMemsetAsync(d_badchar, 0xff, sizeof(unsigned long long), s));
-    a.cons = d_cons; a.phred = d_phred; a.lerr = d_lerr; a.cons_len = d_len; a.row_status = d_status;
-    a.first_bad_char = d_badchar; a.fix_count = d_fixn;
-    int* d_fixgrp = nullptr; int* d_gflag;
-    SL_TRY(scratch("cons.gflag", static_cast<size_t>(std::max<int64_t>(ngroups, 1)), &d_gflag));
-    a.gflag = d_gflag; a.only_flagged = 0;
-    // the boundary list: fix_cap empty entries (no group recorded)
-    const auto fix_list = [&]() -> int {
-        SL_TRY(scratch("cons.fixpos", static_cast<size_t>(fix_cap), &d_fixpos));
-        SL_TRY(scratch("cons.fixval", 4 * static_cast<size_t>(fix_cap), &d_fixval));
-        SL_TRY(scratch("cons.fixgrp", static_cast<size_t>(fix_cap), &d_fixgrp));
-        SL_HIP(hipMemsetAsync(d_fixn, 0, sizeof(int), s));
-        SL_HIP(hipMemsetAsync(d_fixgrp, 0xff, sizeof(int) * static_cast<size_t>(fix_cap), s));
-        a.fix_cap = fix_cap; a.fix_pos = d_fixpos; a.fix_val = d_fixval; a.fix_grp = d_fixgrp;
-        return 0;
-    };
-    SL_TRY(fix_list());
-    const size_t lds = (quality ? 2 * sizeof(double) * enc_n : 0) + (2 * sizeof(long long) + 3 * sizeof(int)) * static_cast<size_t>(max_rows) + 16;
-    const int grid = static_cast<int>(std::min<int64_t>(ng_eval, static_cast<int64_t>(c.num_cu) * 32));
-    // quality vote without the per-column log errors: 4 columns per lane, 4 alignments per workgroup
-    const size_t lds4 = sizeof(double) * 4 * (5 * static_cast<size_t>(enc_n) + 1) + 4 * (2 * sizeof(long long) + 3 * sizeof(int)) * static_cast<size_t>(max_rows) + 16;
-    const bool q4 = quality && !lerr && lds4 <= 48 * 1024;
-    // the vote's launches: run again when the boundary list was too short
-    const auto vote = [&]() -> int {
-        if (a.codes) {
-            // rows written as vote codes by the MSA stage: nothing to decode
-            const size_t ldsc = static_cast<size_t>(enc_n + 1) * QC_ROWB;
-            SL_HIP(allow_lds(&k_consensus_code, ldsc));
-            const int gridc = static_cast<int>(std::min<int64_t>((ng_eval + QF_THREADS / 64 - 1) / (QF_THREADS / 64), c.num_cu));
-            hipLaunchKernelGGL(k_consensus_code, dim3(gridc), dim3(QF_THREADS), ldsc, s, a);
-        } else if (q4) {
+int launch_vote(const ConsPlan& plan, const ConsArgs& a, hipStream_t s) {
+    switch (plan.route) {
+        case CONS_BASIC: return launch(k_consensus<false>, plan.vote, a, s);
+        case CONS_GENERIC: return launch(k_consensus<true>, plan.vote, a, s);
+        case CONS_Q4: return launch(k_consensus_q4, plan.vote, a, s);
+        case CONS_QF_Q4: {
             // clean groups on the fast kernel (one 1024-thread workgroup per CU around a ~85 KB strip table in LDS);
             // whatever it flags is redone by the generic kernel
-            const size_t ldsf = static_cast<size_t>(enc_n + 1) * QF_ROWB;
-            // (its byte-parallel index arithmetic -- QOFF4, QZERO4, KHI -- takes the first name and first name + enc_n as
-            // bytes 0..255: a table whose names start at or above byte 128, a negative signed char, goes to k_consensus_q4)
-            const bool qf = a.aln_bytes > 0 && a.qual_bytes > 0 && enc_n <= 127 && a.qoffset >= 0 && a.qoffset + enc_n <= 255 &&
-                            ldsf <= 150 * 1024 && !option(OPT_CONSENSUS_GENERIC);
-            if (qf) {
-                SL_HIP(allow_lds(&k_consensus_qf, ldsf));
-                const int gridf = static_cast<int>(std::min<int64_t>((ng_eval + QF_THREADS / 64 - 1) / (QF_THREADS / 64), c.num_cu));
-                hipLaunchKernelGGL(k_consensus_qf, dim3(gridf), dim3(QF_THREADS), ldsf, s, a);
-                SL_HIP(hipGetLastError());
-                a.only_flagged = 1;
-            }
-            const int grid4 = static_cast<int>(std::min<int64_t>((ng_eval + 3) / 4, static_cast<int64_t>(c.num_cu) * 64));
-            hipLaunchKernelGGL(k_consensus_q4, dim3(grid4), dim3(256), lds4, s, a);
-        } else {
-            if (lds > 48 * 1024)   // alignments of thousands of rows: more than the default 64 KB of dynamic LDS
-                SL_HIP(quality ? allow_lds(&k_consensus<true>, lds) : allow_lds(&k_consensus<false>, lds));
-            if (quality) hipLaunchKernelGGL(k_consensus<true>, dim3(grid), dim3(64), lds, s, a);
-            else hipLaunchKernelGGL(k_consensus<false>, dim3(grid), dim3(64), lds, s, a);
+            SL_TRY(launch(k_consensus_qf, plan.qf, a, s));
+            ConsArgs flagged = a;
+            flagged.only_flagged = 1;
+            return launch(k_consensus_q4, plan.vote, flagged, s);
         }
-        SL_HIP(hipGetLastError());
-        return 0;
-    };
-
-    if (ng_eval > 0) {
-        if (lds > 160 * 1024) return fail("sarlacc_amd: alignment with %d rows does not fit the consensus kernel", max_rows);
-        SL_HIP(hipEventRecord(c.ev_start, s));
-        c.counts["consensus_cells"] = static_cast<double>(total);
-        c.stage_reset("consensus");
-        SL_TRY(c.stage_begin("consensus", s));
-        SL_TRY(vote());
-        SL_HIP(hipEventRecord(c.ev_stop, s));
-        SL_TRY(c.stage_end("consensus", s));
-        c.timed = true;
+        case CONS_CODE: return launch(k_consensus_code, plan.vote, a, s);   // rows written as vote codes by the MSA stage: nothing to decode
     }
-
-    // ---- results and error resolution ----
-    std::vector<int32_t> len(static_cast<size_t>(ngroups), 0);
-    std::vector<int8_t> status(static_cast<size_t>(std::max<int64_t>(rows_eval, 1)), 0);
-    unsigned long long badchar = ~0ull;
-    int fixn = 0;
-    if (ng_eval > 0) {
-        SL_HIP(hipMemcpy(len.data(), d_len, sizeof(int32_t) * static_cast<size_t>(ng_eval), hipMemcpyDeviceToHost));
-        SL_HIP(hipMemcpy(status.data(), d_status, static_cast<size_t>(std::max<int64_t>(rows_eval, 1)), hipMemcpyDeviceToHost));
-        SL_HIP(hipMemcpy(&badchar, d_badchar, sizeof badchar, hipMemcpyDeviceToHost));
-        SL_HIP(hipMemcpy(&fixn, d_fixn, sizeof fixn, hipMemcpyDeviceToHost));
-    }
-    // earliest error in the reference's processing order
-    if (!quality && badchar != ~0ull) {
-        char bc = '?';
-        if (aln_host) bc = aln_host[static_cast<int64_t>(badchar)];
-        else SL_HIP(hipMemcpy(&bc, a.aln + badchar, 1, hipMemcpyDeviceToHost));
-        char msg[96];
-        snprintf(msg, sizeof msg, "unknown character '%c' in alignment string", bc);
-        return fail("%s", msg);
-    }
-    if (a.codes && a.code_bad) {
-        int bad_row = 0x7fffffff;
-        SL_HIP(hipMemcpy(&bad_row, a.code_bad, sizeof bad_row, hipMemcpyDeviceToHost));
-        if (bad_row != 0x7fffffff) return fail("quality cannot be lower than smallest encoded value");
-    }
-    if (quality)
-        for (int64_t r = 0; r < rows_eval; ++r) {
-            if (status[r] == 1) return fail("quality cannot be lower than smallest encoded value");
-            if (status[r] == 2) return fail("quality vector is shorter than the alignment sequence");
-            if (status[r] == 3) return fail("quality vector is longer than the alignment sequence");
-        }
-    if (struct_err_kind == 1) return fail("alignment strings should have the same length");
-    if (struct_err_kind == 2) return fail("alignments and qualities have different numbers of entries");
-    // More boundary columns than the list holds (every column of an alignment of equal rows can sit on one): the count
-    // is exact and the kernels are deterministic, so the vote runs once more with a list of that size.
-    while (fixn > fix_cap) {
-        fix_cap = fixn;
-        SL_TRY(fix_list());
-        SL_TRY(vote());
-        SL_HIP(hipMemcpy(&fixn, d_fixn, sizeof fixn, hipMemcpyDeviceToHost));
-    }
-
-    // compact the kept columns on the device, then copy only those back
-    std::vector<long long> dst(static_cast<size_t>(ngroups) + 1, 0);
-    for (int64_t g = 0; g < ngroups; ++g) dst[g + 1] = dst[g] + len[g];
-    const long long kept = dst[ngroups];
-    // (the caller's buffers hold the KEPT columns: their number is known only now -- the alignments of clusters of several
-    // molecules are several reads wide and keep one read's worth of columns, so a bound from the widths would refuse, and make a
-    // caller repeat, calls whose results fit easily)
-    if (cons_cap >= 0 && kept > cons_cap) return fail("sarlacc_amd: consensus output buffer too small (%lld needed)", kept);
-    // results land directly in the caller's buffers (no intermediate host copies)
-    uint8_t* const hc = reinterpret_cast<uint8_t*>(cons);
-    uint8_t* const hp = reinterpret_cast<uint8_t*>(phred);
-    double* const hl = lerr;
-    if (kept) {
-        long long* d_dst; uint8_t* d_cc; uint8_t* d_cp; double* d_cl = nullptr;
-        SL_TRY(upload("cons.dst", dst.data(), dst.size(), &d_dst, s));
-        SL_TRY(scratch("cons.cc", static_cast<size_t>(kept), &d_cc));
-        SL_TRY(scratch("cons.cp", static_cast<size_t>(kept), &d_cp));
-        if (lerr) SL_TRY(scratch("cons.cl", static_cast<size_t>(kept), &d_cl));
-        hipLaunchKernelGGL(k_consensus_compact, dim3(static_cast<unsigned>(ng_eval)), dim3(256), 0, s, d_cons, d_phred, d_lerr,
-                           d_ooff, d_len, d_dst, static_cast<long long>(ng_eval), d_cc, d_cp, d_cl);
-        SL_HIP(hipGetLastError());
-        SL_HIP(hipMemcpy(hc, d_cc, static_cast<size_t>(kept), hipMemcpyDeviceToHost));
-        SL_HIP(hipMemcpy(hp, d_cp, static_cast<size_t>(kept), hipMemcpyDeviceToHost));
-        if (lerr) SL_HIP(hipMemcpy(hl, d_cl, sizeof(double) * static_cast<size_t>(kept), hipMemcpyDeviceToHost));
-    }
-    if (fixn > 0) {  // exact host-libm re-evaluation of boundary columns
-        std::vector<long long> fp(static_cast<size_t>(fixn));
-        std::vector<double> fv(static_cast<size_t>(fixn) * 4);
-        SL_HIP(hipMemcpy(fp.data(), d_fixpos, sizeof(long long) * fp.size(), hipMemcpyDeviceToHost));
-        SL_HIP(hipMemcpy(fv.data(), d_fixval, sizeof(double) * fv.size(), hipMemcpyDeviceToHost));
-        // entries the fast kernel made for a group it later handed over are void (the generic kernel made its own)
-        std::vector<int> fg(static_cast<size_t>(fixn)), gflag;
-        SL_HIP(hipMemcpy(fg.data(), d_fixgrp, sizeof(int) * fg.size(), hipMemcpyDeviceToHost));
-        if (a.only_flagged) {
-            gflag.resize(static_cast<size_t>(ng_eval));
-            SL_HIP(hipMemcpy(gflag.data(), d_gflag, sizeof(int) * gflag.size(), hipMemcpyDeviceToHost));
-        }
-        for (int k = 0; k < fixn; ++k) {
-            if (fg[k] >= 0 && !gflag.empty() && gflag[static_cast<size_t>(fg[k])]) continue;
-            double le;
-            if (quality) le = log_error(fv[4 * k], fv[4 * k + 1], fv[4 * k + 2], fv[4 * k + 3]);
-            else le = std::log1p(-((fv[4 * k] + pseudo / 4) / (fv[4 * k + 1] + pseudo)));
-            // fix_pos is an index into the uncompacted layout: find its alignment, then its slot
-            const long long pos = fp[k];
-            const int64_t g = static_cast<int64_t>(std::upper_bound(out_off.begin(), out_off.begin() + ng_eval, pos) - out_off.begin()) - 1;
-            const size_t at = static_cast<size_t>(dst[g] + (pos - out_off[g]));
-            hp[at] = static_cast<uint8_t>(phred_char(le));
-            if (lerr) hl[at] = le;
-        }
-    }
-    for (int64_t g = 0; g < ngroups; ++g) cons_off[g + 1] = dst[g + 1];
-    return 0;
+    return fail("sarlacc_amd: unknown consensus route %d", static_cast<int>(plan.route));
 }
 
-static int run_consensus(bool quality, const char* aln, const int64_t* aln_off, const int64_t* grp_rows,
-                         int64_t ngroups, const char* qual, const int64_t* qual_off, const int64_t* qgrp_rows,
-                         double min_cov, double pseudo, const double* enc_errors, const char* enc_names, int enc_n,
-                         char* cons, char* phred, int64_t* cons_off, double* lerr) {
-    if (ngroups < 0) return fail("sarlacc_amd: negative number of alignments");
-    if (quality) SL_TRY(check_encoding(enc_errors, enc_names, enc_n));
-    cons_off[0] = 0;
-    if (ngroups == 0) return 0;
-    const int64_t nrows_total = grp_rows[ngroups];
-
-    // host-side structural checks, in the reference's order (group by group):
-    // equal row widths (src/DNA_input.cpp:90-104), then matching entry counts (:186-190)
-    int64_t struct_err_group = -1;
-    int struct_err_kind = 0;
-    int max_rows = 1;
-    for (int64_t g = 0; g < ngroups && struct_err_group < 0; ++g) {
-        const int64_t r0 = grp_rows[g], r1 = grp_rows[g + 1];
-        max_rows = static_cast<int>(std::max<int64_t>(max_rows, r1 - r0));
-        for (int64_t r = r0 + 1; r < r1; ++r)
-            if (aln_off[r + 1] - aln_off[r] != aln_off[r0 + 1] - aln_off[r0]) { struct_err_group = g; struct_err_kind = 1; break; }
-        if (struct_err_group < 0 && quality && (qgrp_rows[g + 1] - qgrp_rows[g]) != (r1 - r0)) {
-            struct_err_group = g;
-            struct_err_kind = 2;
-        }
-    }
-    // Only groups before the first structural error are evaluated on the device.
-    const int64_t ng_eval = struct_err_group >= 0 ? struct_err_group : ngroups;
-    const int64_t rows_eval = grp_rows[ng_eval];
-    if (quality)
-        for (int64_t g = 0; g < ng_eval; ++g)
-            if (qgrp_rows[g] != grp_rows[g]) return fail("sarlacc_amd: alignment and quality row numbering differ");
-
-    SL_TRY(ensure_device());
-    hipStream_t s = nullptr;
-    const int64_t total = aln_off[nrows_total] - aln_off[0];
-    const int64_t base = aln_off[0];
-
-    std::vector<int64_t> rel(static_cast<size_t>(nrows_total) + 1), out_off(static_cast<size_t>(std::max<int64_t>(ngroups, 1)));
-    for (int64_t r = 0; r <= nrows_total; ++r) rel[r] = aln_off[r] - base;
-    for (int64_t g = 0; g < ngroups; ++g) out_off[g] = rel[grp_rows[g]];
-
-    ConsArgs a{};
-    uint8_t* d_aln;
-    SL_TRY(upload("cons.aln", reinterpret_cast<const uint8_t*>(aln) + base, static_cast<size_t>(total), &d_aln, s));
-    a.aln = d_aln;
-    SL_TRY(upload_rows(a, rel, grp_rows, ngroups, out_off, max_rows, s));
-    if (quality) {
-        const int64_t qrows = qgrp_rows[ng_eval];
-        const int64_t qbase = qual_off[0];
-        const int64_t qtotal = qual_off[qrows] - qbase;
-        std::vector<int64_t> qrel(static_cast<size_t>(qrows) + 1);
-        for (int64_t r = 0; r <= qrows; ++r) qrel[r] = qual_off[r] - qbase;
-        uint8_t* d_q; int64_t* d_qoff;
-        SL_TRY(upload("cons.qual", reinterpret_cast<const uint8_t*>(qual) + qbase, static_cast<size_t>(qtotal), &d_q, s));
-        SL_TRY(upload("cons.qoff", qrel.data(), qrel.size(), &d_qoff, s));
-        a.qual = d_q; a.qual_off = d_qoff; a.qual_bytes = qtotal;
-    }
-    return consensus_core(quality, a, ngroups, ng_eval, rows_eval, total, out_off, aln + base, struct_err_kind, min_cov, pseudo,
-                          enc_errors, enc_names, enc_n, cons, phred, cons_off, lerr, s);
+int launch_compact(const ConsArgs& a, const long long* d_dst, uint8_t* d_cons, uint8_t* d_phred, double* d_lerr, hipStream_t s) {
+    hipLaunchKernelGGL(k_consensus_compact, dim3(static_cast<unsigned>(a.ngroups)), dim3(256), 0, s, a.cons, a.phred, a.lerr, a.out_off,
+                       a.cons_len, d_dst, a.ngroups, d_cons, d_phred, d_lerr);
+    SL_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace sarlacc
-
-using namespace sarlacc;
-
-extern "C" {
-
-int sarlacc_create_consensus_basic_loop(const char* aln, const int64_t* aln_off, const int64_t* grp_rows,
-                                        int64_t ngroups, double min_cov, double pseudo_count, char* cons,
-                                        char* phred, int64_t* cons_off, double* lerr) {
-    return run_consensus(false, aln, aln_off, grp_rows, ngroups, nullptr, nullptr, nullptr, min_cov, pseudo_count,
-                         nullptr, nullptr, 0, cons, phred, cons_off, lerr);
-}
-
-// Shared body of sarlacc_msa_consensus (host pointers) and sarlacc_dev_msa_consensus (reads and
-// qualities already in HBM: d_seq / d_qual non-null, seq / qual unused).
-static int msa_consensus_impl(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const char* seq,
-                              const int64_t* seq_off, const char* qual, const int64_t* qual_off, int64_t nseq, double match,
-                              double mismatch, double gap_extension, double gap_opening, int bandwidth, double min_cov,
-                              double pseudo_count, const double* enc_errors, const char* enc_names, int enc_n, char* cons,
-                              char* phred, int64_t* cons_off, int64_t cons_cap, const uint8_t* d_seq_res, const uint8_t* d_qual_res,
-                              bool quality) {
-    if (ngroups < 0 || nseq < 0) return fail("sarlacc_amd: negative sizes");
-    if (quality) SL_TRY(check_encoding(enc_errors, enc_names, enc_n));
-    cons_off[0] = 0;
-    if (ngroups == 0) return 0;
-    MsaResult res;
-    res.width.assign(static_cast<size_t>(ngroups), 0);
-    res.out_off.assign(static_cast<size_t>(ngroups) + 1, 0);
-    // the quality strings travel to the device on a stream of their own while the pairwise
-    // alignments run (qualities stay in read order; every row finds its string through the member list)
-    uint8_t* d_q = nullptr; int64_t* d_qoff = nullptr;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t q_ready = nullptr;
-    std::vector<int64_t> qrel;
-    // Rows as vote codes (k_consensus_code) when the quality strings are laid out like the reads -- every read as long as
-    // its quality string, which is also what the reference demands -- and the table fits LDS; otherwise characters.
-    bool codes = quality && static_cast<size_t>(enc_n + 1) * QC_ROWB <= 150 * 1024 && static_cast<int>(enc_names[0]) + enc_n <= 255 &&
-                 !option(OPT_CONSENSUS_CHARS);
-    for (int64_t r = 0; codes && r < nseq; ++r)
-        if (qual_off[r + 1] - qual_off[r] != seq_off[r + 1] - seq_off[r]) codes = false;
-    const uint8_t* d_q_const = nullptr;
-    if (codes) {
-        SL_TRY(ensure_device());
-        int* d_bad;
-        SL_TRY(scratch("cons.codebad", 1, &d_bad));
-        const int none = 0x7fffffff;
-        SL_HIP(hipMemcpy(d_bad, &none, sizeof none, hipMemcpyHostToDevice));
-        SL_HIP(hipEventCreateWithFlags(&q_ready, hipEventDisableTiming));
-        res.code.want = true; res.code.qual = &d_q_const; res.code.ready = q_ready;
-        res.code.qoffset = static_cast<int>(enc_names[0]); res.code.navail = enc_n; res.code.d_bad = d_bad;
-    }
-    const std::function<int()> upload_quals = [&]() -> int {
-        if (!quality) return 0;
-        const int64_t qbase = qual_off[0];
-        qrel.resize(static_cast<size_t>(nseq) + 1);
-        for (int64_t r = 0; r <= nseq; ++r) qrel[r] = qual_off[r] - qbase;
-        SL_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-        if (d_qual_res) d_q = const_cast<uint8_t*>(d_qual_res);
-        else SL_TRY(upload("cons.qual", reinterpret_cast<const uint8_t*>(qual) + qbase, static_cast<size_t>(qrel[nseq]), &d_q, copy_stream));
-        SL_TRY(upload("cons.qoff", qrel.data(), qrel.size(), &d_qoff, copy_stream));
-        d_q_const = d_q;
-        if (q_ready) SL_HIP(hipEventRecord(q_ready, copy_stream));
-        return 0;
-    };
-    struct EventGuard { hipEvent_t* e; ~EventGuard() { if (*e) (void)hipEventDestroy(*e); } } q_ready_guard{&q_ready};
-    const int msa_rc = msa_run(grp_off, grp, ngroups, seq, seq_off, nseq, match, mismatch, gap_extension, gap_opening, bandwidth, true,
-                               -1, &res, &upload_quals, d_seq_res);
-    if (copy_stream) {
-        const hipError_t e1 = hipStreamSynchronize(copy_stream), e2 = hipStreamDestroy(copy_stream);
-        if (!msa_rc && (e1 != hipSuccess || e2 != hipSuccess)) return fail("HIP error while uploading the quality strings");
-    }
-    if (msa_rc) return msa_rc;
-    if (quality && !d_q) return fail("sarlacc_amd: quality upload did not run");
-    const int64_t total = res.out_off[ngroups];
-    if (total == 0) {
-        for (int64_t g = 0; g < ngroups; ++g) cons_off[g + 1] = 0;
-        return 0;
-    }
-    hipStream_t s = nullptr;
-    // row table of the alignments the MSA stage left in HBM
-    const int64_t nrows = grp_off[ngroups] - grp_off[0];
-    std::vector<int64_t> rel(static_cast<size_t>(nrows) + 1), grows(static_cast<size_t>(ngroups) + 1);
-    std::vector<int64_t> out_off(static_cast<size_t>(ngroups));
-    int max_rows = 1;
-    int64_t row = 0;
-    for (int64_t g = 0; g < ngroups; ++g) {
-        const int64_t m = grp_off[g + 1] - grp_off[g];
-        grows[g] = row;
-        out_off[g] = res.out_off[g];
-        max_rows = static_cast<int>(std::max<int64_t>(max_rows, m));
-        for (int64_t r = 0; r < m; ++r) rel[row++] = res.out_off[g] + r * res.width[g];
-    }
-    grows[ngroups] = row;
-    rel[nrows] = total;
-    ConsArgs a{};
-    a.aln = res.d_out;
-    SL_TRY(upload_rows(a, rel, grows.data(), ngroups, out_off, max_rows, s));
-    if (codes) { a.codes = res.d_codes; a.code_bad = res.code.d_bad; }
-    if (quality) { a.qual = d_q; a.qual_off = d_qoff; a.row_read = res.d_members; a.qual_bytes = qrel[static_cast<size_t>(nseq)]; }
-    return consensus_core(quality, a, ngroups, ngroups, nrows, total, out_off, nullptr, 0, min_cov, pseudo_count, enc_errors,
-                          enc_names, enc_n, cons, phred, cons_off, nullptr, s, cons_cap);
-}
-
-int sarlacc_msa_consensus(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const char* seq,
-                          const int64_t* seq_off, const char* qual, const int64_t* qual_off, int64_t nseq, double match,
-                          double mismatch, double gap_extension, double gap_opening, int bandwidth, double min_cov,
-                          double pseudo_count, const double* enc_errors, const char* enc_names, int enc_n, char* cons,
-                          char* phred, int64_t* cons_off, int64_t cons_cap) {
-    return msa_consensus_impl(grp_off, grp, ngroups, seq, seq_off, qual, qual_off, nseq, match, mismatch, gap_extension,
-                              gap_opening, bandwidth, min_cov, pseudo_count, enc_errors, enc_names, enc_n, cons, phred,
-                              cons_off, cons_cap, nullptr, nullptr, qual != nullptr);
-}
-
-int sarlacc_dev_msa_consensus(const int64_t* grp_off, const int32_t* grp, int64_t ngroups, const uint8_t* d_seq,
-                              const uint8_t* d_qual, const int64_t* off, int64_t nseq, double match, double mismatch,
-                              double gap_extension, double gap_opening, int bandwidth, double min_cov, double pseudo_count,
-                              const double* enc_errors, const char* enc_names, int enc_n, char* cons, char* phred,
-                              int64_t* cons_off, int64_t cons_cap) {
-    if (!d_seq) return fail("sarlacc_amd: sarlacc_dev_msa_consensus needs the reads in device memory");
-    return msa_consensus_impl(grp_off, grp, ngroups, nullptr, off, nullptr, off, nseq, match, mismatch, gap_extension,
-                              gap_opening, bandwidth, min_cov, pseudo_count, enc_errors, enc_names, enc_n, cons, phred,
-                              cons_off, cons_cap, d_seq, d_qual, d_qual != nullptr);
-}
-
-int sarlacc_create_consensus_quality_loop(const char* aln, const int64_t* aln_off, const int64_t* grp_rows,
-                                          int64_t ngroups, const char* qual, const int64_t* qual_off,
-                                          const int64_t* qgrp_rows, double min_cov, const double* enc_errors,
-                                          const char* enc_names, int enc_n, char* cons, char* phred,
-                                          int64_t* cons_off, double* lerr) {
-    return run_consensus(true, aln, aln_off, grp_rows, ngroups, qual, qual_off, qgrp_rows, min_cov, 0.0, enc_errors,
-                         enc_names, enc_n, cons, phred, cons_off, lerr);
-}
-}

@@ -29,10 +29,17 @@ def _same(got, want, what):
     assert got[1] == want[1], "%s: Phred strings differ: %s" % (what, _first_difference(got[1], want[1]))
 
 
-def quality_routes(oracle, alns, quals, table, mincov=0.6, single=True, handover=True, fused=None, what=""):
+def _vote_passes(passes, what):
+    """passes (None: not checked): how often the vote of the last call ran -- 1 + the runs repeated for a longer boundary list"""
+    from sarlacc_amd import _lib
+    if passes is not None:
+        assert _lib.stage_count("consensus_vote_passes") == passes, what
+
+
+def quality_routes(oracle, alns, quals, table, mincov=0.6, single=True, handover=True, fused=None, what="", passes=None):
     """Routes 1 to 5 on the alignments `alns` under the encoding table (errors, names).  handover: two more groups in
     the loop calls that k_consensus_qf hands to k_consensus_q4.  fused: (alignments, qualities) of gap-free rows for
-    routes 4 and 5."""
+    routes 4 and 5.  passes: the vote passes every one of the calls must have taken."""
     from sarlacc_amd import calls
     from sarlacc_amd.encoding import Encoding
     enc = Encoding(*table)
@@ -40,6 +47,7 @@ def quality_routes(oracle, alns, quals, table, mincov=0.6, single=True, handover
         for g, (a, q) in enumerate(zip(alns, quals)):
             want = oracle.create_consensus_quality(a, mincov, q, table)
             got = calls.create_consensus_quality(a, mincov, q, enc)
+            _vote_passes(passes, "%s route 1, group %d" % (what, g))
             assert got[0] == want[0], "%s route 1, group %d: %s" % (what, g, _first_difference([got[0]], [want[0]]))
             assert np.allclose(got[1], want[1], rtol=1e-11, atol=1e-300), (what, g)
     alns, quals = list(alns), list(quals)
@@ -51,6 +59,7 @@ def quality_routes(oracle, alns, quals, table, mincov=0.6, single=True, handover
         for generic in (0, 1):
             calls.set_option("consensus_generic", generic)
             _same(calls.create_consensus_quality_loop(alns, mincov, quals, enc), want, "%s route %d" % (what, 2 + generic))
+            _vote_passes(passes, "%s route %d" % (what, 2 + generic))
         calls.set_option("consensus_generic", 0)
         if fused is not None:
             want = oracle.create_consensus_quality_loop(fused[0], mincov, fused[1], table)
@@ -59,6 +68,7 @@ def quality_routes(oracle, alns, quals, table, mincov=0.6, single=True, handover
             for chars in (0, 1):
                 calls.set_option("consensus_chars", chars)
                 got = calls.msa_consensus_flat(goff, gvals, reads, *K.DEFAULT_SCORES, mincov, quals=rquals, encoding=enc)
+                _vote_passes(passes, "%s route %d" % (what, 4 + chars))
                 _same([got[0].to_strings(), got[1].to_strings()], want, "%s route %d" % (what, 4 + chars))
     finally:
         calls.set_option("consensus_generic", 0)
@@ -115,7 +125,7 @@ def test_near_ties(oracle, n):
 
 def test_near_ties_fused(oracle):
     alns, quals = K.tie_fused()
-    quality_routes(oracle, alns, quals, K.phred_table(), single=False, fused=(alns, quals), what="ties, fused")
+    quality_routes(oracle, alns, quals, K.phred_table(), single=False, fused=(alns, quals), what="ties, fused", passes=1)
 
 
 # ---------------------------------------------------------------------------
@@ -217,11 +227,13 @@ def test_boundary_flood_basic(oracle):
     rows, pc = K.flood_basic()
     want = oracle.create_consensus_basic(rows, 0.6, pc)
     got = calls.create_consensus_basic(rows, 0.6, pc)
+    _vote_passes(2, "flood, basic, single")
     assert got[0] == want[0]
     assert np.allclose(got[1], want[1], rtol=1e-11, atol=0)
     alns, _ = K.split_groups(rows, rows)
     for batch in ([rows], alns):
         _same(calls.create_consensus_basic_loop(batch, 0.6, pc), oracle.create_consensus_basic_loop(batch, 0.6, pc), "flood, basic")
+        _vote_passes(2, "flood, basic, %d groups" % len(batch))
 
 
 def test_boundary_flood_quality(oracle):
@@ -229,9 +241,9 @@ def test_boundary_flood_quality(oracle):
     third has an N in its last column -- k_consensus_qf has listed such a group's columns by the time it meets the N and
     hands the group to k_consensus_q4, which lists them again: the first entries are void, under a grown list too."""
     rows, quals, table = K.flood_quality()
-    quality_routes(oracle, [rows], [quals], table, fused=([rows], [quals]), what="flood, whole")
+    quality_routes(oracle, [rows], [quals], table, fused=([rows], [quals]), what="flood, whole", passes=2)
     alns, qs = K.split_groups(rows, quals)
-    quality_routes(oracle, alns, qs, table, single=False, handover=False, fused=(alns, qs), what="flood, 40 groups")
+    quality_routes(oracle, alns, qs, table, single=False, handover=False, fused=(alns, qs), what="flood, 40 groups", passes=2)
     mixed = [K.with_n(a) if g % 3 == 0 else a for g, a in enumerate(alns)]
     assert sum(len(a[0]) for a in mixed) - len(mixed[::3]) > 4096
-    quality_routes(oracle, mixed, qs, table, single=False, handover=False, what="flood, hand-over")
+    quality_routes(oracle, mixed, qs, table, single=False, handover=False, what="flood, hand-over", passes=2)
