@@ -355,14 +355,73 @@ int sarlacc_dev_fastq_format(const uint8_t* d_seq, const uint8_t* d_qual, const 
  * every record: the piece boundaries for sarlacc_dev_bgzf_deflate_cuts.  Step 2 writes the bytes d_rec_off[first] ..
  * d_rec_off[first + count] of the stream to d_out[0 ..], at any alignment of d_out.  n == 0 and count == 0 succeed
  * without a launch.  Both calls return when the device has finished.
- * Out of scope: tags (read groups, MM / ML), aligned records, paired flags, qualities written as the 0xff "missing"
- * marker; the header and the BGZF container are the caller's (DeviceReads.to_bam). */
+ * sarlacc_dev_bam_format_size_aux / _format_aux are the same pair with the reads' tags (below: "tags of a resident
+ * batch"), d_aux / d_aux_off, behind QUAL: record i ends with its d_aux_off[i + 1] - d_aux_off[i] aux bytes as they lie
+ * and block_size counts them.  d_cuts then gets 3 n sorted offsets, SEQ start, QUAL start and tag start of every record
+ * (tag bytes are text-like and get a Huffman table of their own under the deflate's 64-byte piece rule); a read without
+ * tags has its tag start at its record's end, and equal neighbouring cuts are harmless to sarlacc_dev_bgzf_deflate_cuts
+ * (a piece ends at the FIRST cut at least 64 bytes into it).  Step 1 walks every read's aux area and refuses, within a
+ * record after the quality refusal and in front of the size refusal, "malformed tags" (see sarlacc_dev_bam_tags_find)
+ * and, in an area that is well-formed, "tag XX appears twice" (the first entry whose tag an earlier one carries).
+ * With d_aux == NULL (and d_aux_off == NULL) both calls are the pair above: the same bytes, the same 2 n cuts.
+ * Out of scope: aligned records, paired flags, qualities written as the 0xff "missing" marker, @RG header lines for
+ * the RG tags written; the header and the BGZF container are the caller's (DeviceReads.to_bam). */
 int sarlacc_dev_bam_format_size(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
                                 const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
                                 int64_t* d_rec_off, int64_t* d_cuts, int64_t* total_bytes, void* stream);
 int sarlacc_dev_bam_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
                            const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
                            int64_t count, uint8_t* d_out, void* stream);
+int sarlacc_dev_bam_format_size_aux(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
+                                    const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
+                                    const uint8_t* d_aux, const int64_t* d_aux_off, int64_t* d_rec_off, int64_t* d_cuts,
+                                    int64_t* total_bytes, void* stream);
+int sarlacc_dev_bam_format_aux(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
+                               const int64_t* d_name_off, int64_t first_index, const uint8_t* d_aux, const int64_t* d_aux_off,
+                               const int64_t* d_rec_off, int64_t first, int64_t count, uint8_t* d_out, void* stream);
+
+/* Tags of a resident batch.  A read's tags are the raw aux bytes of its BAM record (SAM specification section 4.2.4):
+ * everything behind QUAL up to the record's end, in file order, unparsed.  A batch holds them flat, as names are held:
+ * d_aux bytes and n + 1 int64 offsets d_aux_off.  An aux area is a run of entries, tag (two bytes) | type letter | value;
+ * it is malformed when fewer than 3 bytes are left in front of its end, a type letter is not one of AcCsSiIfZHB, a
+ * fixed value or a B header or payload runs past the end, a B subtype is not one of cCsSiIf, or a Z or H has no NUL in
+ * front of the end.  No call reads at or behind a read's aux end, whatever the bytes say.
+ * sarlacc_dev_bam_tags_find walks the whole aux area of every read, one wavefront per read, so it is also the
+ * validator: "read K: malformed tags" for the lowest such read, K 1-based in the batch.  `tag` is two bytes.  Per read
+ * it reports the first entry with that tag (a repeated tag counts once, as htslib's bam_aux_get): d_type its type letter
+ * (0: absent), d_val_off / d_val_len where its value starts, counted from the read's aux start, and its bytes (Z / H
+ * without the NUL, B with its 5-byte header), d_tag_off / d_tag_len the same for the whole entry; all zero where the tag
+ * is absent.  The five arrays (n entries each) may all be NULL: validation only.  *n_present is the number of reads that
+ * hold the tag, *string_bytes the bytes of their A / Z / H values (either may be NULL).
+ * sarlacc_dev_bam_tags_strings turns the result of a find into a flat string set on the device: d_str_off gets n + 1
+ * offsets, d_chars (string_bytes bytes) the A / Z / H values, an empty string where the tag is absent.
+ * sarlacc_dev_bam_tags_ints turns it into int64 d_values (types cCsSiI, 0 where absent) and a d_present byte mask.
+ * Where a read holds the tag with another type either call fails with "read K: tag XX has type T" (lowest read) --
+ * f and B values are not decoded, they are kept and written as they lie.
+ * sarlacc_dev_bam_tags_splice is the one edit: output read r (n_out of them, their n_out + 1 offsets d_out_off computed
+ * by the caller, who holds every length) is the aux area of read d_src[r] (NULL: r, and n_out == n_src) without its byte
+ * span [d_cut_off[r], d_cut_off[r] + d_cut_len[r]) (both NULL: nothing cut), followed, where d_mask[r] (NULL: everywhere),
+ * by a new entry `tag` of type `kind`: 'Z' with the string r of the flat set d_col_chars / d_col_off (n_out + 1 offsets)
+ * and a NUL, 'i' with the int32 d_col_ints[r], 0 for no entry.  So one kernel takes or permutes reads, drops a tag,
+ * appends one, or replaces one (cut + append).  The span is clamped to the read's aux area and a d_src outside
+ * [0, n_src) reads as an empty area; bytes of d_out_off's ranges that the three sources do not fill are written as 0.
+ * d_out may have any alignment.  The kernel does not look into the values: the caller keeps a Z free of bytes outside
+ * ' '..'~'.
+ * n == 0 (n_out == 0) succeeds without a launch.  All calls return when the device has finished.
+ * Out of scope: decoding f and B, rewriting MM / ML / mv after a trim or a reversal. */
+int sarlacc_dev_bam_tags_find(const uint8_t* d_aux, const int64_t* d_aux_off, int64_t n, const uint8_t* tag, uint8_t* d_type,
+                              int64_t* d_val_off, int64_t* d_val_len, int64_t* d_tag_off, int64_t* d_tag_len,
+                              int64_t* n_present, int64_t* string_bytes, void* stream);
+int sarlacc_dev_bam_tags_strings(const uint8_t* d_aux, const int64_t* d_aux_off, int64_t n, const uint8_t* tag,
+                                 const uint8_t* d_type, const int64_t* d_val_off, const int64_t* d_val_len, uint8_t* d_chars,
+                                 int64_t* d_str_off, void* stream);
+int sarlacc_dev_bam_tags_ints(const uint8_t* d_aux, const int64_t* d_aux_off, int64_t n, const uint8_t* tag,
+                              const uint8_t* d_type, const int64_t* d_val_off, int64_t* d_values, uint8_t* d_present,
+                              void* stream);
+int sarlacc_dev_bam_tags_splice(const uint8_t* d_aux, const int64_t* d_aux_off, int64_t n_src, const int64_t* d_src, int64_t n_out,
+                                const int64_t* d_cut_off, const int64_t* d_cut_len, const uint8_t* tag, int kind,
+                                const uint8_t* d_col_chars, const int64_t* d_col_off, const int32_t* d_col_ints,
+                                const uint8_t* d_mask, const int64_t* d_out_off, uint8_t* d_out, void* stream);
 
 /* SAM alignment records already in device memory -> ranges (sam2ranges, R/sam2ranges.R:8-95).  d_text holds
  * body lines of a SAM file (no header), LF or CRLF, blank lines skipped; first_line is the 1-based file line
@@ -463,11 +522,11 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
  * each code complemented (its four bits in reverse order: A 1 <-> T 8, C 2 <-> G 4, M 3 <-> K 12, ..., N 15 <-> N), QUAL
  * reversed.  A first QUAL byte of 0xff says the record holds no qualities (section 4.2.3): every quality of the read is
  * then missing_qual + 33, missing_qual in 0..93.  The name is the read name without its NUL (no /1 or /2 is added),
- * l_seq 0 is a read of length 0, tags are ignored.  Errors are "BAM record K: <reason>" for the lowest failing record,
- * within a record in this order: the locator's two messages and, on every record, "record fields do not fit its block
- * size" as above; on records that become reads "SEQ holds '='" (a code 0) and "quality value above 93" (0xff anywhere
- * but first included).  All of them are reported by sarlacc_dev_bam_reads_index, which keeps its state thread-local
- * like the pairs above (a later locator run on the thread, sarlacc_dev_bam_index included, ends it).
+ * l_seq 0 is a read of length 0, tags are left to the _aux_ pair below.  Errors are "BAM record K: <reason>" for the
+ * lowest failing record, within a record in this order: the locator's two messages and, on every record, "record fields
+ * do not fit its block size" as above; on records that become reads "SEQ holds '='" (a code 0) and "quality value above
+ * 93" (0xff anywhere but first included).  All of them are reported by sarlacc_dev_bam_reads_index, which keeps its
+ * state thread-local like the pairs above (a later locator run on the thread, sarlacc_dev_bam_index included, ends it).
  * sarlacc_dev_bam_reads_range reports what the reads first .. first + count of the buffer indexed last need: their
  * bases, their name bytes, and in *next_byte the offset of the record behind the last of them (used_bytes for
  * first + count == n_reads, which takes the dropped records at the end along; 0 for first + count == 0): where the carry of
@@ -477,7 +536,14 @@ int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_st
  * in d_off that start at 0, the names and count + 1 offsets in d_names / d_name_off (both NULL: no names).  Every
  * output may have any alignment; nothing outside those ranges is written.  count == 0 and nbytes == 0 succeed without a
  * launch.  The three calls return when the device has finished.
- * Out of scope: tags, .bai / .csi random access, CRAM. */
+ * sarlacc_dev_bam_reads_aux_range / _aux_extract are the same two steps for the reads' tags ("tags of a resident batch"
+ * above), over the buffer indexed last: the same thread-local state, ended by the same events.  _aux_range reports the
+ * aux bytes of the reads first .. first + count; _aux_extract copies each read's aux area as it lies into d_aux and fills
+ * count + 1 offsets in d_aux_off that start at 0.  A record with flag 0x10 has its SEQ and QUAL restored by
+ * sarlacc_dev_bam_reads_extract, but its tags are copied unchanged: MM / ML / mv of such a record describe the STORED
+ * strand.  The tags are sized on the first of these calls after an index, so a buffer read without them pays nothing;
+ * they are not validated here (sarlacc_dev_bam_tags_find is the validator).
+ * Out of scope: .bai / .csi random access, CRAM. */
 int sarlacc_bgzf_scan(const uint8_t* buf, int64_t nbytes, int64_t max_blocks, int64_t first_block, int64_t* comp_off,
                       int64_t* text_off, int64_t* n_blocks, int64_t* used_bytes, int* last_is_eof);
 int sarlacc_dev_bgzf_inflate(const uint8_t* d_comp, const int64_t* d_comp_off, const int64_t* d_text_off, int64_t n_blocks,
@@ -504,6 +570,9 @@ int sarlacc_dev_bam_reads_range(int64_t first, int64_t count, int64_t* total_bas
 int sarlacc_dev_bam_reads_records(int64_t reads_taken, int64_t* n_records);
 int sarlacc_dev_bam_reads_extract(const uint8_t* d_bam, int64_t first, int64_t count, int missing_qual, uint8_t* d_seq,
                                   uint8_t* d_qual, int64_t* d_off, uint8_t* d_names, int64_t* d_name_off, void* stream);
+int sarlacc_dev_bam_reads_aux_range(int64_t first, int64_t count, int64_t* aux_bytes);
+int sarlacc_dev_bam_reads_aux_extract(const uint8_t* d_bam, int64_t first, int64_t count, uint8_t* d_aux, int64_t* d_aux_off,
+                                      void* stream);
 
 /* ------------------------------------------------------------------ */
 /* masked Levenshtein, neighbour search, clustering                      */

@@ -150,6 +150,12 @@ def _prototypes():
         "sarlacc_dev_fastq_format": (i, [p, p, p, p, p, i64, p, i64, i64, p, p]),
         "sarlacc_dev_bam_format_size": (i, [p, p, p, i64, p, p, i64, p, p, p, p]),
         "sarlacc_dev_bam_format": (i, [p, p, p, p, p, i64, p, i64, i64, p, p]),
+        "sarlacc_dev_bam_format_size_aux": (i, [p, p, p, i64, p, p, i64, p, p, p, p, p, p]),
+        "sarlacc_dev_bam_format_aux": (i, [p, p, p, p, p, i64, p, p, p, i64, i64, p, p]),
+        "sarlacc_dev_bam_tags_find": (i, [p, p, i64, p, p, p, p, p, p, p, p, p]),
+        "sarlacc_dev_bam_tags_strings": (i, [p, p, i64, p, p, p, p, p, p, p]),
+        "sarlacc_dev_bam_tags_ints": (i, [p, p, i64, p, p, p, p, p, p]),
+        "sarlacc_dev_bam_tags_splice": (i, [p, p, i64, p, i64, p, p, p, i, p, p, p, p, p, p, p]),
         "sarlacc_dev_sam_index": (i, [p, i64, i64, p, p, i64, p, p, p, i64, i, i64, p, p, p, p]),
         "sarlacc_dev_sam_extract": (i, [p, p, p, p, p, p, p, p, p, p]),
         "sarlacc_dev_bam_index": (i, [p, i64, i64, i, i64, p, i, i64, p, p, p, p, p]),
@@ -159,6 +165,8 @@ def _prototypes():
         "sarlacc_dev_bam_reads_range": (i, [i64, i64, p, p, p]),
         "sarlacc_dev_bam_reads_records": (i, [i64, p]),
         "sarlacc_dev_bam_reads_extract": (i, [p, i64, i64, i, p, p, p, p, p, p]),
+        "sarlacc_dev_bam_reads_aux_range": (i, [i64, i64, p]),
+        "sarlacc_dev_bam_reads_aux_extract": (i, [p, i64, i64, p, p, p]),
         "sarlacc_bgzf_scan": (i, [p, i64, i64, i64, p, p, p, p, p]),
         "sarlacc_dev_bgzf_inflate": (i, [p, p, p, i64, i64, p, i, p]),
         "sarlacc_bgzf_deflate_bound": (i, [i64, p, p]),

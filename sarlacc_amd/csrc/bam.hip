@@ -162,14 +162,6 @@ __global__ void __launch_bounds__(64) k_bam_starts(const uint8_t* bam, long long
 
 __device__ __forceinline__ bool bam_consumes_ref(unsigned op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }   // M D N = X
 
-// bytes of a tag value of a fixed-size type, 0 for any other letter
-__device__ __forceinline__ int bam_type_size(int t) {
-    if (t == 'A' || t == 'c' || t == 'C') return 1;
-    if (t == 's' || t == 'S') return 2;
-    if (t == 'i' || t == 'I' || t == 'f') return 4;
-    return 0;
-}
-
 constexpr int BAM_THREADS = 256;   // four wavefronts, one record each at a time
 
 __global__ void __launch_bounds__(BAM_THREADS) k_bam_fields(const uint8_t* bam, const long long* rec_off, long long nrec,

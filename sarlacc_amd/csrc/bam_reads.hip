@@ -24,6 +24,10 @@
 //                   read or of the range is put together base by base.  Nothing outside the record's SEQ and QUAL is
 //                   read, nothing outside the range's bases is written.
 //   k_bamr_names    sixteen lanes per record copy its name
+//   k_bamr_aux_len / k_bamr_aux_offsets / k_bamr_aux   the tags of the reads (sarlacc_dev_bam_reads_aux_range / _extract):
+//                   the bytes behind QUAL of every kept record, sized on the first request for them (a batch read
+//                   without tags never pays for it), scanned, and copied as they lie by a walk over OUTPUT bytes
+//                   (gather_out_tiles): a move table is kilobytes, a mapper's NM:i:3 four bytes.
 //
 // No kernel waits on another workgroup, every loop is bounded by a record's own length or the range, and a bad file is an
 // error return (first_bad: atomicMin on record << 4 | code), never a fault.
@@ -207,6 +211,37 @@ __global__ void __launch_bounds__(256) k_bamr_names(const uint8_t* bam, const lo
     }
 }
 
+// aux_len[k] = bytes behind QUAL of a kept record, 0 of a dropped one and for k == nrec
+__global__ void __launch_bounds__(256) k_bamr_aux_len(const uint8_t* bam, const long long* rec_off, const int* keep, long long nrec,
+                                                      long long* aux_len) {
+    const long long k = blockIdx.x * 256LL + threadIdx.x;
+    if (k > nrec) return;
+    long long n = 0;
+    if (k < nrec && keep[k]) {
+        BamFixed F;
+        bam_layout_ok(bam + rec_off[k], &F);      // (it passed in k_bamr_size)
+        n = F.bs - (32 + F.l_name + 4 * F.n_cig + (F.l_seq + 1) / 2 + F.l_seq);
+    }
+    aux_len[k] = n;
+}
+
+// aux offsets of the reads first .. first + count relative to record a, the record of the first of them
+__global__ void __launch_bounds__(256) k_bamr_aux_offsets(const long long* read_rec, const int64_t* aux_off, long long first,
+                                                          long long count, long long a, int64_t* d_aux_off) {
+    const long long i = blockIdx.x * 256LL + threadIdx.x;
+    if (i > count) return;
+    d_aux_off[i] = aux_off[read_rec[first + i]] - aux_off[a];
+}
+
+// aux[0 .. ) = the aux areas of the records a .. e
+__global__ void __launch_bounds__(OT_THREADS) k_bamr_aux(const uint8_t* bam, const long long* rec_off, const int64_t* aux_off,
+                                                         long long a, long long e, uint8_t* aux) {
+    gather_out_tiles(aux_off, a, e, aux, [&](long long k) {
+        const uint8_t* rec = bam + rec_off[k];
+        return rec + 4 + static_cast<long long>(static_cast<int>(rd_u32(rec))) - (aux_off[k + 1] - aux_off[k]);
+    });
+}
+
 // state of the last sarlacc_dev_bam_reads_index call on this thread
 struct BamReadsIndex {
     bool valid = false;
@@ -217,6 +252,8 @@ struct BamReadsIndex {
     int64_t* base_off = nullptr;           // nrec + 1 each: exclusive scans over the records
     int64_t* name_off = nullptr;
     long long* read_rec = nullptr;         // nreads + 1: record of a read, nrec behind the last
+    const int* keep = nullptr;             // nrec + 1
+    int64_t* aux_off = nullptr;            // nrec + 1, an exclusive scan as base_off is; null until tags are asked for
 };
 thread_local BamReadsIndex g_bamr;
 
@@ -225,6 +262,22 @@ struct BamReadsSpan {
     long long a = 0, e = 0;
     int64_t bases = 0, name_bytes = 0, next_byte = 0;
 };
+
+int bamr_span(long long first, long long count, BamReadsSpan* sp);
+
+// the aux offsets of the indexed buffer's records, made on the first request
+int bamr_aux_index(hipStream_t s) {
+    BamReadsIndex& X = g_bamr;
+    if (X.aux_off || X.nrec == 0) return 0;
+    long long* d_alen; int64_t* d_aoff;
+    SL_TRY(scratch("bamr.alen", static_cast<size_t>(X.nrec) + 1, &d_alen));
+    SL_TRY(scratch("bamr.aoff", static_cast<size_t>(X.nrec) + 1, &d_aoff));
+    hipLaunchKernelGGL(k_bamr_aux_len, dim3(nblk(X.nrec + 1, 256)), dim3(256), 0, s, X.bam, X.rec_off, X.keep, X.nrec, d_alen);
+    SL_HIP(hipGetLastError());
+    SL_TRY(exclusive_scan("bamr.scan", d_alen, d_aoff, static_cast<size_t>(X.nrec) + 1, s));
+    X.aux_off = d_aoff;
+    return 0;
+}
 
 int bamr_span(long long first, long long count, BamReadsSpan* sp) {
     const BamReadsIndex& X = g_bamr;
@@ -328,7 +381,7 @@ int sarlacc_dev_bam_reads_index(const uint8_t* d_bam, int64_t nbytes, int64_t fi
     BamReadsIndex& X = g_bamr;
     X.valid = true; X.bam = d_bam; X.generation = L.generation;
     X.nrec = nrec; X.nreads = nreads; X.used = L.end;
-    X.rec_off = L.d_off; X.base_off = d_boff; X.name_off = d_noff; X.read_rec = d_rrec;
+    X.rec_off = L.d_off; X.base_off = d_boff; X.name_off = d_noff; X.read_rec = d_rrec; X.keep = d_keep;
     *n_records = nrec; *used_bytes = L.end; *n_reads = nreads;
     return 0;
 }
@@ -382,6 +435,46 @@ int sarlacc_dev_bam_reads_extract(const uint8_t* d_bam, int64_t first, int64_t c
         SL_HIP(hipGetLastError());
     }
     SL_TRY(c.stage_end("bam_reads_unpack", s));
+    SL_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int sarlacc_dev_bam_reads_aux_range(int64_t first, int64_t count, int64_t* aux_bytes) {
+    BamReadsSpan sp;
+    SL_TRY(bamr_span(first, count, &sp));
+    *aux_bytes = 0;
+    if (count == 0 || g_bamr.nrec == 0) return 0;
+    SL_TRY(bamr_aux_index(nullptr));
+    int64_t b[2];
+    SL_HIP(hipMemcpy(&b[0], g_bamr.aux_off + sp.a, sizeof(int64_t), hipMemcpyDeviceToHost));
+    SL_HIP(hipMemcpy(&b[1], g_bamr.aux_off + sp.e, sizeof(int64_t), hipMemcpyDeviceToHost));
+    *aux_bytes = b[1] - b[0];
+    return 0;
+}
+
+int sarlacc_dev_bam_reads_aux_extract(const uint8_t* d_bam, int64_t first, int64_t count, uint8_t* d_aux, int64_t* d_aux_off,
+                                      void* stream) {
+    BamReadsSpan sp;
+    SL_TRY(bamr_span(first, count, &sp));
+    BamReadsIndex& X = g_bamr;
+    if (d_bam != X.bam) return fail("sarlacc_amd: not the BAM buffer indexed last on this thread");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (count == 0 || X.nrec == 0) {
+        SL_HIP(hipMemsetAsync(d_aux_off, 0, sizeof(int64_t), s));
+        SL_HIP(hipStreamSynchronize(s));
+        return 0;
+    }
+    SL_TRY(bamr_aux_index(s));
+    Context& c = ctx();
+    c.stage_reset("bam_reads_aux");
+    SL_TRY(c.stage_begin("bam_reads_aux", s));
+    hipLaunchKernelGGL(k_bamr_aux_offsets, dim3(nblk(count + 1, 256)), dim3(256), 0, s, X.read_rec, X.aux_off,
+                       static_cast<long long>(first), static_cast<long long>(count), sp.a, d_aux_off);
+    SL_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_bamr_aux, dim3(static_cast<unsigned>(c.num_cu) * 8), dim3(OT_THREADS), 0, s, d_bam, X.rec_off, X.aux_off,
+                       sp.a, sp.e, d_aux);
+    SL_HIP(hipGetLastError());
+    SL_TRY(c.stage_end("bam_reads_aux", s));
     SL_HIP(hipStreamSynchronize(s));
     return 0;
 }

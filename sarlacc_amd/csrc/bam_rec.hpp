@@ -1,6 +1,6 @@
 // bam_rec.hpp -- what the BAM paths share (bam.hip: records -> ranges, bam_reads.hip: records -> reads, bam_write.hip:
-// reads -> records): SEQ's alphabet in both directions, the unaligned field readers, the layout predicate every record
-// has to pass, and the locator (implemented in bam.hip).
+// reads -> records, bam_tags.hip: the tags of resident reads): SEQ's alphabet in both directions, the unaligned field
+// readers, the layout predicate every record has to pass, the tag walker, and the locator (implemented in bam.hip).
 #pragma once
 
 #include "common.hpp"
@@ -57,6 +57,89 @@ __device__ __forceinline__ bool bam_layout_ok(const uint8_t* rec, BamFixed* F) {
     F->l_seq = static_cast<int>(rd_u32(f + 16));
     const long long fixed = 32 + F->l_name + 4 * F->n_cig;
     return !(F->l_name == 0 || F->l_seq < 0 || fixed + (F->l_seq + 1) / 2 + F->l_seq > F->bs || f[32 + F->l_name - 1] != 0);
+}
+
+// bytes of a tag value of a fixed-size type, 0 for any other letter
+__device__ __forceinline__ int bam_type_size(int t) {
+    if (t == 'A' || t == 'c' || t == 'C') return 1;
+    if (t == 's' || t == 'S') return 2;
+    if (t == 'i' || t == 'I' || t == 'f') return 4;
+    return 0;
+}
+
+// ---- the tag walker ------------------------------------------------------------------------------------------------------
+// An aux area is the bytes behind QUAL up to the record's end (SAM specification section 4.2.4): entries of tag (two
+// bytes), type letter, value.  bam_tag_next steps over one entry, the whole wavefront together and every value the
+// same in all its lanes.  It never reads at or behind `end`, whatever the bytes say.  Malformed: fewer than 3 bytes in
+// front of the end, a type letter outside AcCsSiIfZHB, a fixed value or a B header or payload past the end, a B subtype
+// outside cCsSiIf, a Z or H without a NUL in front of the end.
+typedef uint32_t __attribute__((ext_vector_type(4))) bam_u32x4;
+typedef bam_u32x4 __attribute__((aligned(1))) bam_u32x4_unaligned;
+
+struct BamTag {
+    unsigned name = 0;               // the two tag bytes, the first one low
+    int type = 0;
+    long long at = 0, val = 0, val_len = 0, next = 0;    // entry start, value start, value bytes (Z / H: without the NUL;
+                                                         // B: with its 5-byte header), start of the next entry
+};
+
+enum { BAM_TAG_OK = 0, BAM_TAG_END = 1, BAM_TAG_BAD = 2 };
+
+// first NUL among aux[p .. end), `end` when there is none: 16 bytes per lane and step, the tail byte by byte
+__device__ __forceinline__ long long bam_wave_find_nul(const uint8_t* aux, long long p, long long end, int lane) {
+    for (long long q0 = p; q0 < end; q0 += 16 * 64) {
+        const long long q = q0 + 16LL * lane;
+        int hit = -1;
+        if (q + 16 <= end) {
+            const bam_u32x4 v = *reinterpret_cast<const bam_u32x4_unaligned*>(aux + q);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 3; i >= 0; --i) {
+                const uint32_t z = (w[i] - 0x01010101u) & ~w[i] & 0x80808080u;     // its lowest set bit: the first NUL of the word
+                if (z) hit = 4 * i + ((__ffs(static_cast<int>(z)) - 1) >> 3);
+            }
+        } else {
+            for (long long j = end - 1; j >= q; --j)
+                if (aux[j] == 0) hit = static_cast<int>(j - q);
+        }
+        const unsigned long long any = __ballot(hit >= 0);
+        if (any) {
+            const int first = __ffsll(static_cast<long long>(any)) - 1;
+            return q0 + 16LL * first + __shfl(hit, first);
+        }
+    }
+    return end;
+}
+
+// the entry at aux[p], p <= end
+__device__ __forceinline__ int bam_tag_next(const uint8_t* aux, long long p, long long end, int lane, BamTag* T) {
+    if (p >= end) return BAM_TAG_END;
+    if (end - p < 3) return BAM_TAG_BAD;
+    T->at = p;
+    T->name = aux[p] | (static_cast<unsigned>(aux[p + 1]) << 8);
+    const int ty = aux[p + 2];
+    T->type = ty;
+    T->val = p + 3;
+    long long sz = bam_type_size(ty);
+    if (sz) {
+        T->val_len = sz;
+    } else if (ty == 'Z' || ty == 'H') {
+        const long long nul = bam_wave_find_nul(aux, p + 3, end, lane);
+        if (nul >= end) return BAM_TAG_BAD;
+        T->val_len = nul - (p + 3);
+        sz = T->val_len + 1;
+    } else if (ty == 'B') {
+        if (end - (p + 3) < 5) return BAM_TAG_BAD;
+        const int es = aux[p + 3] == 'A' ? 0 : bam_type_size(aux[p + 3]);
+        if (!es) return BAM_TAG_BAD;
+        sz = 5 + static_cast<long long>(rd_u32(aux + p + 4)) * es;
+        T->val_len = sz;
+    } else {
+        return BAM_TAG_BAD;
+    }
+    if (sz > end - (p + 3)) return BAM_TAG_BAD;
+    T->next = p + 3 + sz;
+    return BAM_TAG_OK;
 }
 
 // how the chain of records ends in a buffer

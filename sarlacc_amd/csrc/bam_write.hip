@@ -7,15 +7,16 @@
 //     flag 4 | l_seq | next_refID -1 | next_pos -1 | tlen 0 | name NUL | SEQ | QUAL          (36 + l_read_name + (L + 1) / 2 + L bytes)
 //
 // SEQ holds two 4-bit codes per byte through "=ACMGRSVTWYHKDBN", high nibble first, the low nibble of an odd last byte 0;
-// QUAL holds byte - 33; there are no tags.  The name is the read's name up to its first space or tab ('*' where nothing
-// is left), READ_<first_index + i> when the batch has no names.  The stream holds records only: the caller puts the
+// QUAL holds byte - 33; a batch with tags (the raw aux bytes of every read, bam_tags.hip) has each read's aux bytes behind
+// QUAL, counted in block_size, and there are no tags otherwise.  The name is the read's name up to its first space or
+// tab ('*' where nothing is left), READ_<first_index + i> when the batch has no names.  The stream holds records only: the caller puts the
 // header in front and compresses (bgzf_deflate.hip, which takes the SEQ and QUAL starts this file reports as the ends
 // of its pieces).
 //
 //   k_bamw_size    one wavefront per record: the kept part of the name, then name, bases and qualities scanned 16
 //                  bytes per lane and step; the byte length of the record
 //   (rocPRIM exclusive scan: n + 1 record offsets, the last one is the size of the stream)
-//   k_bamw_cuts    SEQ start and QUAL start of every record in the stream
+//   k_bamw_cuts    SEQ start and QUAL start of every record in the stream, with tags the tag start as well
 //   k_bamw_format  the bytes of a contiguous record range, divided by OUTPUT bytes as k_fqw_format is: the walk
 //                  out_tiles.hpp describes (this kernel's own copy of it), 16-byte pieces aligned in memory.  A piece
 //                  inside SEQ packs 32 bases read with two unaligned 16-byte loads: the letter's low five bits index a
@@ -26,27 +27,33 @@
 //                  ends of the range are stored byte by byte.
 //
 // No kernel waits on another workgroup and every loop is bounded by a record's own length or the range.  A batch BAM
-// cannot hold is an error return of the size pass (first_bad: atomicMin on record << 4 | code, on the failure path only,
-// as k_bamr_size reports), before a byte is written.
+// cannot hold is an error return of the size pass (first_bad: atomicMin on record << 20 | tag << 4 | code, on the
+// failure path only, as k_bamr_size reports), before a byte is written.
 //
-// Messages, "record K: <reason>", K 1-based; the lowest record wins, within a record name, SEQ, QUAL:
+// The three kernels are templates on "with tags" (sarlacc_dev_bam_format_size_aux / _format_aux); the instantiations
+// without are the kernels as they were.
+//
+// Messages, "record K: <reason>", K 1-based; the lowest record wins, within a record name, SEQ, QUAL, tags:
 //   read name longer than 254 bytes              (after the cut)
 //   read name holds a byte outside '!'..'~'      (in the kept part)
 //   base cannot be stored in BAM                 (anything but the 15 upper-case letters: '=', lower case, '-')
 //   quality byte outside Phred+33                (outside 33..126)
+//   malformed tags                               (bam_rec.hpp's walker; in front of a repeat in the same record)
+//   tag XX appears twice
 //   record larger than 2^31 - 1 bytes
-// Out of scope: tags, aligned records, paired flags, qualities written as the 0xff "missing" marker.
+// Out of scope: aligned records, paired flags, qualities written as the 0xff "missing" marker.
 #include "bam_rec.hpp"
 #include "out_tiles.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace sarlacc {
 namespace {
 
-enum { BAMW_NAME_LONG = 1, BAMW_NAME_BYTE = 2, BAMW_BASE = 3, BAMW_QUAL = 4, BAMW_SIZE = 5 };
+enum { BAMW_NAME_LONG = 1, BAMW_NAME_BYTE = 2, BAMW_BASE = 3, BAMW_QUAL = 4, BAMW_SIZE = 5, BAMW_TAGS = 6, BAMW_TAG_TWICE = 7 };
 
 constexpr int BW_FIXED = 36;                      // block_size and the fixed fields
 constexpr int BW_NAME_MAX = 254;                  // l_read_name is a byte and counts the NUL
@@ -105,10 +112,45 @@ __device__ __forceinline__ void wave_name_scan(const uint8_t* p, long long n, in
     *other = wave_min(fo);
 }
 
-// len[r] = bytes of record r, 0 for a refused one (len[n] = 0 for the scan); first_bad: lowest refused record << 4 | why
+// The tags of a batch (AUX instantiations): the raw aux bytes of every read, flat, with n + 1 offsets.
+struct BwAux {
+    const uint8_t* aux; const int64_t* aux_off;
+};
+
+// Whether the aux area A[0 .. end) can go behind QUAL: 0, BAMW_TAGS for a malformed one, BAMW_TAG_TWICE (*twice: the
+// tag of the first such entry) where two entries of a well-formed one carry one tag.  The whole wavefront walks the
+// entries (bam_tag_next); the tags of the first 64 entries sit one per lane and a new one is compared with all of them
+// in one ballot.  Entries from the 65th on are also compared with the entries 64 .. by a walk of their own each -- no
+// basecaller or mapper writes that many.
+__device__ __forceinline__ int bamw_aux_check(const uint8_t* A, long long end, int lane, unsigned* twice) {
+    BamTag T;
+    unsigned mine = 0xffffffffu;      // no tag: a tag is 16 bits
+    long long p = 0;
+    int st;
+    bool found = false;               // a repeat is reported only once the whole area has proved well-formed
+    for (long long i = 0; (st = bam_tag_next(A, p, end, lane, &T)) == BAM_TAG_OK; ++i, p = T.next) {
+        if (found) continue;
+        bool dup = __ballot(mine == T.name) != 0;
+        if (!dup && i > 64) {
+            BamTag U;
+            long long q = 0;
+            for (long long j = 0; j < i && !dup; ++j, q = U.next) {      // (entries in front of a well-formed one are well-formed)
+                bam_tag_next(A, q, end, lane, &U);
+                dup = j >= 64 && U.name == T.name;
+            }
+        }
+        if (dup) { *twice = T.name; found = true; }
+        if (lane == i) mine = T.name;
+    }
+    return st == BAM_TAG_BAD ? BAMW_TAGS : found ? BAMW_TAG_TWICE : 0;
+}
+
+// len[r] = bytes of record r, 0 for a refused one (len[n] = 0 for the scan); first_bad: lowest refused record << 20 |
+// the tag of BAMW_TAG_TWICE << 4 | why
+template <bool AUX>
 __global__ void __launch_bounds__(OT_THREADS) k_bamw_size(const uint8_t* seq, const uint8_t* qual, const int64_t* off,
                                                           const uint8_t* names, const int64_t* name_off, long long first_index,
-                                                          long long n, long long* len, unsigned long long* first_bad) {
+                                                          long long n, BwAux X, long long* len, unsigned long long* first_bad) {
     const int lane = threadIdx.x & 63;
     const long long nwaves = static_cast<long long>(gridDim.x) * (OT_THREADS / 64);
     if (blockIdx.x == 0 && threadIdx.x == 0) len[n] = 0;
@@ -130,22 +172,33 @@ __global__ void __launch_bounds__(OT_THREADS) k_bamw_size(const uint8_t* seq, co
                                  [](uint8_t c) { return not_base4(c | 0x41414100u) != 0; })) bad = BAMW_BASE;
         if (!bad && wave_any_bad(qual + so, L, lane, [](uint32_t w) { return not_phred4(w); },
                                  [](uint8_t c) { return c < 33 || c > 126; })) bad = BAMW_QUAL;
-        const long long total = BW_FIXED + l_name + (L + 1) / 2 + L;
+        long long total = BW_FIXED + l_name + (L + 1) / 2 + L;
+        unsigned twice = 0;
+        if constexpr (AUX) {
+            const long long ao = X.aux_off[r], al = X.aux_off[r + 1] - ao;
+            if (!bad) bad = bamw_aux_check(X.aux + ao, al, lane, &twice);
+            total += al;
+        }
         if (!bad && total > 0x7fffffffLL) bad = BAMW_SIZE;
         if (lane == 0) {
             len[r] = bad ? 0 : total;
-            if (bad) atomicMin(first_bad, (static_cast<unsigned long long>(r) << 4) | static_cast<unsigned>(bad));
+            if (bad) atomicMin(first_bad, (static_cast<unsigned long long>(r) << 20) | (twice << 4) | static_cast<unsigned>(bad));
         }
     }
 }
 
-// cuts[2 r], cuts[2 r + 1] = where SEQ and QUAL of record r start in the stream
-__global__ void __launch_bounds__(256) k_bamw_cuts(const int64_t* off, const int64_t* rec_off, long long n, int64_t* cuts) {
+// cuts[2 r], cuts[2 r + 1] = where SEQ and QUAL of record r start in the stream; with tags cuts[3 r], cuts[3 r + 1] and
+// in cuts[3 r + 2] where the tags start (the record's end where it has none)
+template <bool AUX>
+__global__ void __launch_bounds__(256) k_bamw_cuts(const int64_t* off, const int64_t* rec_off, BwAux X, long long n, int64_t* cuts) {
     const long long r = blockIdx.x * 256LL + threadIdx.x;
     if (r >= n) return;
-    const long long L = off[r + 1] - off[r], ql = rec_off[r + 1] - L;
-    cuts[2 * r] = ql - (L + 1) / 2;
-    cuts[2 * r + 1] = ql;
+    const long long al = AUX ? X.aux_off[r + 1] - X.aux_off[r] : 0;
+    const long long L = off[r + 1] - off[r], ql = rec_off[r + 1] - al - L;
+    constexpr int PER = AUX ? 3 : 2;
+    cuts[PER * r] = ql - (L + 1) / 2;
+    cuts[PER * r + 1] = ql;
+    if (AUX) cuts[PER * r + 2] = ql + L;
 }
 
 // what a lane knows about the record it is writing
@@ -155,19 +208,28 @@ struct BwRec {
     int l_name = 0;                          // bytes of the name with its NUL
     bool star = false;                       // nothing of the name is kept: '*'
 };
+struct BwRecAux : BwRec {
+    long long ao = 0, al = 0;                // tag offset and length
+};
 
 struct BwSource {
     const uint8_t* seq; const uint8_t* qual; const int64_t* off;
     const uint8_t* names; const int64_t* name_off; long long first_index;
     const int64_t* rec_off;
 
-    __device__ __forceinline__ void load(BwRec& R, long long r) const {
+    __device__ __forceinline__ void load(BwRecAux& R, long long r, const BwAux& X) const {
+        R.ao = X.aux_off[r];
+        R.al = X.aux_off[r + 1] - R.ao;
+        load(R, r, R.al);
+    }
+
+    __device__ __forceinline__ void load(BwRec& R, long long r, long long al = 0) const {
         R.r = r;
         R.start = rec_off[r];
         R.len = rec_off[r + 1] - R.start;
         R.so = off[r];
         R.sl = off[r + 1] - R.so;
-        R.l_name = static_cast<int>(R.len - BW_FIXED - (R.sl + 1) / 2 - R.sl);
+        R.l_name = static_cast<int>(R.len - al - BW_FIXED - (R.sl + 1) / 2 - R.sl);
         R.star = false;
         if (names) {
             R.no = name_off[r];
@@ -176,7 +238,13 @@ struct BwSource {
         }
     }
 
-    // byte q of record R
+    // byte q of record R with tags
+    __device__ __forceinline__ uint8_t byte_at(const BwRecAux& R, long long q, const BwAux& X) const {
+        const long long body = R.len - R.al;
+        return q < body ? byte_at(static_cast<const BwRec&>(R), q) : X.aux[R.ao + (q - body)];
+    }
+
+    // byte q of record R (in front of its tags)
     __device__ __forceinline__ uint8_t byte_at(const BwRec& R, long long q) const {
         if (q < BW_FIXED) {
             const int f = static_cast<int>(q >> 2);
@@ -207,7 +275,10 @@ struct BwSource {
 // out[0 .. ) = bytes rec_off[first] .. rec_off[first + count] of the whole stream.  This kernel keeps its own copy of
 // walk_out_tiles and of OutPiece (out_tiles.hpp; change them together): as a body of the shared walk it left its
 // occupancy step or ran 2 - 5 % longer on 200-base reads (profiles/io_tile_walk_device_code.txt, io_tile_walk_speed.txt).
-__global__ void __launch_bounds__(OT_THREADS) k_bamw_format(BwSource S, long long first, long long count, uint8_t* out) {
+// AUX: the tags are one more kind of piece behind QUAL, a whole piece inside them one unaligned 16-byte load, and a
+// lane carries their offset and length as well (BwRecAux); the instantiation without them is the kernel as it was.
+template <bool AUX>
+__global__ void __launch_bounds__(OT_THREADS) k_bamw_format(BwSource S, BwAux X, long long first, long long count, uint8_t* out) {
     constexpr int BW_TILE = 64 * 16 * OT_PIECES;      // bytes of the stream per wavefront and step
     const long long base = S.rec_off[first], nbytes = S.rec_off[first + count] - base;
     const int mis = static_cast<int>(reinterpret_cast<uintptr_t>(out) & 15);   // pieces are aligned in memory, not in the stream
@@ -215,7 +286,8 @@ __global__ void __launch_bounds__(OT_THREADS) k_bamw_format(BwSource S, long lon
     const int lane = threadIdx.x & 63;
     const long long wave = blockIdx.x * static_cast<long long>(OT_THREADS / 64) + (threadIdx.x >> 6);
     const long long nwaves = static_cast<long long>(gridDim.x) * (OT_THREADS / 64);
-    BwRec R;
+    typename std::conditional<AUX, BwRecAux, BwRec>::type R;
+    const auto load = [&](long long r) { if constexpr (AUX) S.load(R, r, X); else S.load(R, r); };
     for (long long tile = wave; tile < ntiles; tile += nwaves) {
         const long long t0 = tile * BW_TILE - mis;
         const long long tile_lo = t0 > 0 ? t0 : 0, tile_hi = (t0 + BW_TILE < nbytes ? t0 + BW_TILE : nbytes) - 1;
@@ -229,11 +301,19 @@ __global__ void __launch_bounds__(OT_THREADS) k_bamw_format(BwSource S, long lon
             const long long v0 = p0 > 0 ? p0 : 0, v1 = p0 + 16 < nbytes ? p0 + 16 : nbytes;   // head and tail of the range
             if (v0 >= v1) continue;
             const long long r = last_not_above(S.rec_off, r_lo, r_hi + 1, base + v0);
-            if (r != R.r) S.load(R, r);
+            if (r != R.r) load(r);
             long long q = base + v0 - R.start;
             const bool whole = v1 - v0 == 16;
             const long long sq = BW_FIXED + R.l_name, ql = sq + (R.sl + 1) / 2;
-            if (whole && q >= ql && q + 16 <= R.len) {          // sixteen qualities
+            long long qend = R.len;                             // where QUAL ends
+            if constexpr (AUX) {
+                qend -= R.al;
+                if (whole && q >= qend && q + 16 <= R.len) {    // sixteen bytes of tags
+                    *reinterpret_cast<u32x4*>(out + p0) = *reinterpret_cast<const u32x4_unaligned*>(X.aux + R.ao + (q - qend));
+                    continue;
+                }
+            }
+            if (whole && q >= ql && q + 16 <= qend) {           // sixteen qualities
                 u32x4 v = *reinterpret_cast<const u32x4_unaligned*>(S.qual + R.so + (q - ql));
                 v -= 0x21212121u;                               // no borrow between the bytes: the size pass refused values below 33
                 *reinterpret_cast<u32x4*>(out + p0) = v;
@@ -256,8 +336,9 @@ __global__ void __launch_bounds__(OT_THREADS) k_bamw_format(BwSource S, long lon
             uint64_t lo = 0, hi = 0;
 #pragma unroll 1
             for (int d = d0; d < d1; ++d, ++q) {
-                if (q >= R.len) { q = 0; S.load(R, R.r + 1); }     // (inside the range: d < d1)
-                const uint64_t c = S.byte_at(R, q);
+                if (q >= R.len) { q = 0; load(R.r + 1); }          // (inside the range: d < d1)
+                uint64_t c;
+                if constexpr (AUX) c = S.byte_at(R, q, X); else c = S.byte_at(R, q);
                 if (d < 8) lo |= c << (8 * d); else hi |= c << (8 * (d - 8));
             }
             if (whole) {
@@ -278,42 +359,80 @@ __global__ void __launch_bounds__(OT_THREADS) k_bamw_format(BwSource S, long lon
 
 using namespace sarlacc;
 
-extern "C" {
+namespace {
 
-int sarlacc_dev_bam_format_size(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
-                                const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
-                                int64_t* d_rec_off, int64_t* d_cuts, int64_t* total_bytes, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+template <bool AUX>
+int bamw_size(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n, const uint8_t* d_names,
+              const int64_t* d_name_off, int64_t first_index, BwAux X, int64_t* d_rec_off, int64_t* d_cuts, int64_t* total_bytes,
+              hipStream_t s) {
     return format_size_pass("BAM", "bamw", "bam_format_size", n, d_names, d_name_off, first_index, d_rec_off, total_bytes, s,
         [&](Context& c, long long* d_len, unsigned long long* d_bad) {
             const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(n, OT_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
-            hipLaunchKernelGGL(k_bamw_size, dim3(grid), dim3(OT_THREADS), 0, s, d_seq, d_qual, d_off, d_names, d_name_off,
-                               static_cast<long long>(first_index), static_cast<long long>(n), d_len, d_bad);
+            hipLaunchKernelGGL(k_bamw_size<AUX>, dim3(grid), dim3(OT_THREADS), 0, s, d_seq, d_qual, d_off, d_names, d_name_off,
+                               static_cast<long long>(first_index), static_cast<long long>(n), X, d_len, d_bad);
         },
         [&] {
-            if (d_cuts) hipLaunchKernelGGL(k_bamw_cuts, dim3(nblk(n, 256)), dim3(256), 0, s, d_off, d_rec_off, static_cast<long long>(n), d_cuts);
+            if (d_cuts) hipLaunchKernelGGL(k_bamw_cuts<AUX>, dim3(nblk(n, 256)), dim3(256), 0, s, d_off, d_rec_off, X, static_cast<long long>(n), d_cuts);
         },
         [](unsigned long long bad) {
-            const long long k = static_cast<long long>(bad >> 4) + 1;
+            const long long k = static_cast<long long>(bad >> 20) + 1;
+            const unsigned tag = static_cast<unsigned>(bad >> 4) & 0xffffu;
             switch (bad & 15u) {
                 case BAMW_NAME_LONG: return fail("record %lld: read name longer than 254 bytes", k);
                 case BAMW_NAME_BYTE: return fail("record %lld: read name holds a byte outside '!'..'~'", k);
                 case BAMW_BASE: return fail("record %lld: base cannot be stored in BAM", k);
                 case BAMW_QUAL: return fail("record %lld: quality byte outside Phred+33", k);
+                case BAMW_TAGS: return fail("record %lld: malformed tags", k);
+                case BAMW_TAG_TWICE: return fail("record %lld: tag %c%c appears twice", k, static_cast<int>(tag & 255u), static_cast<int>(tag >> 8));
                 default: return fail("record %lld: record larger than 2^31 - 1 bytes", k);
             }
         });
 }
 
-int sarlacc_dev_bam_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
-                           const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
-                           int64_t count, uint8_t* d_out, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+template <bool AUX>
+int bamw_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names, const int64_t* d_name_off,
+                int64_t first_index, BwAux X, const int64_t* d_rec_off, int64_t first, int64_t count, uint8_t* d_out, hipStream_t s) {
     return format_range("BAM", "bam_format", d_names, d_name_off, first_index, first, count, s, [&](dim3 grid) {
         const BwSource src{d_seq, d_qual, d_off, d_names, d_name_off, static_cast<long long>(first_index), d_rec_off};
-        hipLaunchKernelGGL(k_bamw_format, grid, dim3(OT_THREADS), 0, s, src, static_cast<long long>(first),
+        hipLaunchKernelGGL(k_bamw_format<AUX>, grid, dim3(OT_THREADS), 0, s, src, X, static_cast<long long>(first),
                            static_cast<long long>(count), d_out);
     });
 }
+
+}  // namespace
+
+extern "C" {
+
+int sarlacc_dev_bam_format_size(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
+                                const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
+                                int64_t* d_rec_off, int64_t* d_cuts, int64_t* total_bytes, void* stream) {
+    return bamw_size<false>(d_seq, d_qual, d_off, n, d_names, d_name_off, first_index, BwAux{nullptr, nullptr}, d_rec_off, d_cuts,
+                            total_bytes, static_cast<hipStream_t>(stream));
 }
 
+int sarlacc_dev_bam_format(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
+                           const int64_t* d_name_off, int64_t first_index, const int64_t* d_rec_off, int64_t first,
+                           int64_t count, uint8_t* d_out, void* stream) {
+    return bamw_format<false>(d_seq, d_qual, d_off, d_names, d_name_off, first_index, BwAux{nullptr, nullptr}, d_rec_off, first, count,
+                              d_out, static_cast<hipStream_t>(stream));
+}
+
+int sarlacc_dev_bam_format_size_aux(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, int64_t n,
+                                    const uint8_t* d_names, const int64_t* d_name_off, int64_t first_index,
+                                    const uint8_t* d_aux, const int64_t* d_aux_off, int64_t* d_rec_off, int64_t* d_cuts,
+                                    int64_t* total_bytes, void* stream) {
+    if ((d_aux == nullptr) != (d_aux_off == nullptr)) return fail("sarlacc_amd: tags and their offsets go together");
+    if (!d_aux) return sarlacc_dev_bam_format_size(d_seq, d_qual, d_off, n, d_names, d_name_off, first_index, d_rec_off, d_cuts, total_bytes, stream);
+    return bamw_size<true>(d_seq, d_qual, d_off, n, d_names, d_name_off, first_index, BwAux{d_aux, d_aux_off}, d_rec_off, d_cuts,
+                           total_bytes, static_cast<hipStream_t>(stream));
+}
+
+int sarlacc_dev_bam_format_aux(const uint8_t* d_seq, const uint8_t* d_qual, const int64_t* d_off, const uint8_t* d_names,
+                               const int64_t* d_name_off, int64_t first_index, const uint8_t* d_aux, const int64_t* d_aux_off,
+                               const int64_t* d_rec_off, int64_t first, int64_t count, uint8_t* d_out, void* stream) {
+    if ((d_aux == nullptr) != (d_aux_off == nullptr)) return fail("sarlacc_amd: tags and their offsets go together");
+    if (!d_aux) return sarlacc_dev_bam_format(d_seq, d_qual, d_off, d_names, d_name_off, first_index, d_rec_off, first, count, d_out, stream);
+    return bamw_format<true>(d_seq, d_qual, d_off, d_names, d_name_off, first_index, BwAux{d_aux, d_aux_off}, d_rec_off, first, count,
+                             d_out, static_cast<hipStream_t>(stream));
+}
+}

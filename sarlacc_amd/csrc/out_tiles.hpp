@@ -78,6 +78,33 @@ struct OutPiece {
     }
 };
 
+// out[0 .. ) = the bytes off[first] .. off[last] of a flat layout whose record r lies at src(r)[0 .. off[r + 1] - off[r]):
+// a whole piece inside one record is one unaligned 16-byte load, anything else is put together byte by byte.  src is
+// asked for empty records too and must not read through the pointer it returns.
+template <typename Src>
+__device__ __forceinline__ void gather_out_tiles(const int64_t* off, long long first, long long last, uint8_t* out, Src&& src) {
+    long long cur = -1, start = 0, len = 0;
+    const uint8_t* sp = nullptr;
+    walk_out_tiles<OT_THREADS / 64, OT_PIECES>(off, first, last, out,
+                                               [&](long long base, long long p0, long long v0, long long v1, long long r, long long) {
+        if (r != cur) { cur = r; start = off[r]; len = off[r + 1] - start; sp = src(r); }
+        long long q = base + v0 - start;
+        if (v1 - v0 == 16 && q + 16 <= len) {
+            *reinterpret_cast<u32x4*>(out + p0) = *reinterpret_cast<const u32x4_unaligned*>(sp + q);
+            return;
+        }
+        OutPiece P;
+#pragma unroll 1
+        for (long long p = v0; p < v1; ++p, ++q) {
+            while (q >= len) {         // (inside the range: a record with a byte follows)
+                ++cur; start = off[cur]; len = off[cur + 1] - start; sp = src(cur); q = 0;
+            }
+            P.put(static_cast<int>(p - p0), sp[q]);
+        }
+        P.store(out + p0, static_cast<int>(v0 - p0), static_cast<int>(v1 - p0), v1 - v0 == 16);
+    });
+}
+
 __device__ __forceinline__ int decimal_width(unsigned long long v) {
     int w = 1;
     while (v >= 10) { v /= 10; ++w; }

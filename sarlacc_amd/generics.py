@@ -67,13 +67,15 @@ def read_fastq(path):
     return Reads(seqs, quals, names)
 
 
-def read_bam(path, exclude_flags=0x900, missing_qual=1):
+def read_bam(path, exclude_flags=0x900, missing_qual=1, tags=None):
     """The reads of a BAM file -> Reads: resident.DeviceReads.from_bam (unpacked on the device), downloaded, with their
-    names.  The qualities are Phred+33."""
+    names.  The qualities are Phred+33.  With `tags`, a tuple of tag names, the result is (Reads, {name: (values,
+    present)}): what DeviceReads.tag finds of each name on the device."""
     from .resident import DeviceReads
-    dev = DeviceReads.from_bam(path, exclude_flags=exclude_flags, missing_qual=missing_qual)
+    dev = DeviceReads.from_bam(path, exclude_flags=exclude_flags, missing_qual=missing_qual, keep_tags=tags is not None)
     seq, qual = dev.download()
-    return Reads(seq, qual, dev.names, dev.encoding)
+    reads = Reads(seq, qual, dev.names, dev.encoding)
+    return reads if tags is None else (reads, {name: dev.tag(name) for name in tags})
 
 
 def _check_bam_qual_type(path, qual_type):
@@ -101,15 +103,22 @@ def write_fastq(path, reads, append=False, compress=False):
             fh.write(b"@" + name.encode() + b"\n" + s.encode() + b"\n+\n" + q.encode() + b"\n")
 
 
-def write_bam(path, reads, header=None):
+def write_bam(path, reads, header=None, tags=None):
     """Reads -> unaligned BAM (DeviceReads.to_bam, whose byte count is returned): records packed and deflated on the
     device; host Reads are uploaded for it, as write_fastq(compress=True) does.  Names are cut at their first space or
-    tab (READ_<i> where there are none); a batch whose encoding is not Phred+33 is refused."""
+    tab (READ_<i> where there are none); a batch whose encoding is not Phred+33 is refused.  A resident batch is written
+    with its `.tags`; for host Reads `tags` is a dict name -> values or name -> (values, present), set with
+    DeviceReads.set_tag in the dict's order (strings as type Z, integers as type i)."""
     from .resident import DeviceReads
     if isinstance(reads, DeviceReads):
+        if tags is not None:
+            raise ValueError("'tags' goes with host Reads: a resident batch is written with its own (set_tag)")
         return reads.to_bam(path, header=header)
     dev = DeviceReads.upload(reads)
     dev.names = list(reads.names) if reads.names else None
+    for name, values in (tags or {}).items():
+        values, present = values if isinstance(values, tuple) else (values, None)
+        dev.set_tag(name, values, present)
     return dev.to_bam(path, header=header)
 
 
@@ -345,13 +354,15 @@ def filterReads(aligned, score1, score2, essential1=True, essential2=True):
     return out
 
 
-def realizeReads(aligned, number=1e5, trim=True, resident=False):
+def realizeReads(aligned, number=1e5, trim=True, resident=False, keep_tags=False):
     """realizeReads (R/realizeReads.R:5-46): the reads named in `aligned`, re-read from its FASTQ (or BAM) file
     (streamed in chunks of `number` records with the quality class recorded by adaptorAlign, :11-25),
     reverse-complemented where `reversed` and trimmed to [trim.start, trim.end].  Every chunk is parsed
     on the device and the orientation / trimming happen there (DeviceReads.realize); the result comes
-    back as Reads, or stays in HBM with resident=True."""
+    back as Reads, or stays in HBM with resident=True -- then, with `keep_tags` and a BAM file, with every read's tags
+    as the file holds them (DeviceReads.realize carries them)."""
     import warnings
+    from . import sam
     from .resident import DeviceReads
     qual_type, enc = encoding_for_qual_type(aligned["metadata"].get("qual.type", "phred"))
     want = list(aligned["names"])
@@ -367,7 +378,7 @@ def realizeReads(aligned, number=1e5, trim=True, resident=False):
             warnings.warn("no 'trim.start' detected, run 'filterReads' first")
     parts, part_rows, seen = [], [], set()
     _check_bam_qual_type(aligned["metadata"]["filepath"], qual_type)
-    for dev in DeviceReads.stream_reads(aligned["metadata"]["filepath"], number, encoding=enc):
+    for dev in DeviceReads.stream_reads(aligned["metadata"]["filepath"], number, encoding=enc, keep_tags=bool(keep_tags and resident)):
         idx, rows = [], []
         for i, nm in enumerate(dev.names):
             if nm in rows_of and nm not in seen:   # match(): first occurrence in the file
@@ -401,6 +412,10 @@ def realizeReads(aligned, number=1e5, trim=True, resident=False):
     if resident:
         out = DeviceReads.upload(reads)
         out.names = want
+        if keep_tags and sam.is_bam(aligned["metadata"]["filepath"]):   # as the rows: the parts' tags come back and are put in order
+            from .tags import DeviceTags
+            areas = [a for p in parts for a in p.tags.download()]
+            out.tags = DeviceTags.upload([areas[k] for k in back])
         return out
     return reads
 

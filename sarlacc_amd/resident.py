@@ -66,16 +66,19 @@ def _record_ranges(ro, block_bytes):
 
 # What a writer needs to format any record range of a batch (DeviceReads._write_plan): the library's range formatter,
 # the device buffers of names, name offsets, n + 1 record offsets and (BAM) cuts, the host copy `ro` of the record
-# offsets and the record ranges [(first, last)] of the blocks.
-WritePlan = collections.namedtuple("WritePlan", "format names noff rec_off cuts ro ranges")
+# offsets and the record ranges [(first, last)] of the blocks; `per` cuts per record, and the batch's tags where the
+# records carry them (then `format` is the library's formatter with tags).
+WritePlan = collections.namedtuple("WritePlan", "format names noff rec_off cuts ro ranges per tags", defaults=(2, None))
 
 
 class DeviceReads:
-    """seq / qual / offsets in HBM + the host copy of the offsets."""
+    """seq / qual / offsets in HBM + the host copy of the offsets.  `.tags` (a tags.DeviceTags, None by default) holds
+    the reads' BAM tags where from_bam / stream_bam kept them or set_tag made them."""
 
     def __init__(self, seq, qual, off_dev, off_host, encoding):
         self.seq, self.qual, self.off, self.off_host, self.encoding = seq, qual, off_dev, off_host, encoding
         self.names = None
+        self.tags = None
 
     @classmethod
     def upload(cls, reads):
@@ -198,31 +201,37 @@ class DeviceReads:
             carry = (d_text, pos, nbytes - pos) if pos < nbytes else None
 
     @classmethod
-    def stream_reads(cls, path, number, encoding=None, block_bytes=256 << 20):
+    def stream_reads(cls, path, number, encoding=None, block_bytes=256 << 20, keep_tags=False):
         """stream_bam for a BAM file (sam.is_bam), stream_fastq for anything else: the read source of adaptorAlign and
-        realizeReads.  A BAM file stores Phred values, so `encoding` plays no part there."""
+        realizeReads.  A BAM file stores Phred values, so `encoding` plays no part there; `keep_tags` plays no part in
+        a FASTQ file."""
         from . import sam
         if sam.is_bam(path):
-            return cls.stream_bam(path, number, block_bytes=block_bytes)
+            return cls.stream_bam(path, number, block_bytes=block_bytes, keep_tags=keep_tags)
         return cls.stream_fastq(path, number, encoding=encoding, block_bytes=block_bytes)
 
     @classmethod
-    def from_bam(cls, path, exclude_flags=0x900, missing_qual=1):
+    def from_bam(cls, path, exclude_flags=0x900, missing_qual=1, keep_tags=False):
         """The reads of a BAM file (aligned or not: a basecaller's unaligned BAM holds unmapped records only) as one
         resident batch, unpacked on the device (sarlacc_dev_bam_reads_index / _range / _extract, bam_reads.hip).  A record
         becomes a read unless `flag & exclude_flags` (the default drops secondary and supplementary records); a record
         stored reverse-complemented (flag 0x10) is turned back to the read as sequenced; a record without qualities gets
-        `missing_qual` (0..93) at every base.  The encoding is Phred+33; `.names` is a StrList, as from_fastq leaves it."""
-        chunks = list(cls.stream_bam(path, None, exclude_flags, missing_qual, block_bytes=None))
-        return chunks[0] if chunks else cls._bam_range(DevBuffer(1), 0, 0, missing_qual)
+        `missing_qual` (0..93) at every base.  The encoding is Phred+33; `.names` is a StrList, as from_fastq leaves it.
+        With `keep_tags` the batch gets `.tags`: every read's aux bytes as they lie in its record (tags.DeviceTags;
+        sarlacc_dev_bam_reads_aux_range / _aux_extract), walked once on the device, so that a file with malformed tags
+        fails here ("read K: malformed tags", K counted in the batch).  The tags of a record stored reverse-complemented
+        are kept unchanged: its MM / ML / mv describe the stored strand.  Without `keep_tags` tags are skipped."""
+        chunks = list(cls.stream_bam(path, None, exclude_flags, missing_qual, block_bytes=None, keep_tags=keep_tags))
+        return chunks[0] if chunks else cls._bam_range(DevBuffer(1), 0, 0, missing_qual, keep_tags=keep_tags)
 
     @classmethod
-    def stream_bam(cls, path, number, exclude_flags=0x900, missing_qual=1, block_bytes=256 << 20):
+    def stream_bam(cls, path, number, exclude_flags=0x900, missing_qual=1, block_bytes=256 << 20, keep_tags=False):
         """Generator over the reads of a BAM file (see from_bam) in chunks of `number` reads, each a resident batch: every
         chunk but the last holds exactly `number`, wherever the buffers end.  The header is read on the host
         (sam.read_bam_header); the records are inflated on the device, whole BGZF blocks worth `block_bytes` at a time
         (bgzf.DeviceTextStream).  A chunk that continues past the buffer carries the bytes from its first unused record
-        on, on the device, into the next buffer; a buffer in which no record is complete grows."""
+        on, on the device, into the next buffer; a buffer in which no record is complete grows.  With `keep_tags` every
+        chunk carries `.tags`, read for read (see from_bam)."""
         from . import bgzf, sam
         if number is not None:      # (None: the whole file, from_bam)
             number = int(number)
@@ -250,7 +259,7 @@ class DeviceReads:
                 pos, start = 0, 0
                 while pos < nreads.value and (eof or number is None or nreads.value - pos >= number):
                     count = nreads.value - pos if number is None else min(number, nreads.value - pos)
-                    chunk, start = cls._bam_range(d_bam, pos, count, int(missing_qual), with_next=True)
+                    chunk, start = cls._bam_range(d_bam, pos, count, int(missing_qual), with_next=True, keep_tags=keep_tags)
                     pos += count
                     yield chunk
                 if pos == nreads.value:     # the dropped records at the end go too
@@ -263,9 +272,10 @@ class DeviceReads:
                 carry = (d_bam, start, nbytes - start) if start < nbytes else None
 
     @classmethod
-    def _bam_range(cls, d_bam, first, count, missing_qual, with_next=False):
+    def _bam_range(cls, d_bam, first, count, missing_qual, with_next=False, keep_tags=False):
         """The reads first .. first + count of the BAM buffer indexed last (sarlacc_dev_bam_reads_range / _extract) as a
-        resident batch, and with `with_next` the offset of the record behind them."""
+        resident batch, with `keep_tags` with their validated tags, and with `with_next` the offset of the record behind
+        them."""
         lib = _lib.lib()
         tb, tn, nxt = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         if count:
@@ -278,6 +288,16 @@ class DeviceReads:
                 for buf in (off, noff):
                     check(lib.sarlacc_dev_upload(buf, np.zeros(1, np.int64), 8))
         out = cls._extracted(count, tb.value, tn.value, phred_encoding(), extract)
+        if keep_tags:
+            from .tags import DeviceTags
+            if count:
+                ab = C.c_int64(0)
+                check(lib.sarlacc_dev_bam_reads_aux_range(first, count, C.byref(ab)))
+                aux, aoff = DevBuffer(max(ab.value, 1)), DevBuffer(8 * (count + 1))
+                check(lib.sarlacc_dev_bam_reads_aux_extract(d_bam, first, count, aux, aoff, None))
+                out.tags = DeviceTags(aux, aoff, aoff.to_numpy(np.int64, count + 1).copy()).validate()
+            else:
+                out.tags = DeviceTags.empty(0)
         return (out, nxt.value) if with_next else out
 
     def __len__(self):
@@ -321,6 +341,14 @@ class DeviceReads:
         if ss is not None:      # (names that are all empty: the library tells "no names" by a null pointer)
             names, noff = DevBuffer.from_numpy(ss.chars if ss.chars.size else np.zeros(1, np.uint8)), DevBuffer.from_numpy(ss.off)
         rec_off, total = DevBuffer(8 * (n + 1)), C.c_int64(0)
+        if bam and self.tags is not None:
+            tags = self._tags()
+            cuts = DevBuffer(max(24 * n, 8))
+            check(_lib.lib().sarlacc_dev_bam_format_size_aux(self.seq, self.qual, self.off, n, names, noff, 1, tags.aux, tags.off,
+                                                             rec_off, cuts, C.byref(total), None))
+            ro = rec_off.to_numpy(np.int64, n + 1)
+            return WritePlan(_lib.lib().sarlacc_dev_bam_format_aux, names, noff, rec_off, cuts, ro, _record_ranges(ro, block_bytes),
+                             3, tags)
         if bam:
             cuts = DevBuffer(max(16 * n, 8))
             check(_lib.lib().sarlacc_dev_bam_format_size(self.seq, self.qual, self.off, n, names, noff, 1, rec_off, cuts,
@@ -361,11 +389,12 @@ class DeviceReads:
             check(_lib.lib().sarlacc_dev_upload(d_raw, head, head.size))
             yield block(head.size)
         for (a, b), nbytes in zip(plan.ranges, sizes):
-            check(plan.format(self.seq, self.qual, self.off, plan.names, plan.noff, 1, plan.rec_off, a, b - a, d_raw, None))
+            aux = () if plan.tags is None else (plan.tags.aux, plan.tags.off)
+            check(plan.format(self.seq, self.qual, self.off, plan.names, plan.noff, 1, *aux, plan.rec_off, a, b - a, d_raw, None))
             if plan.cuts is None:
                 yield block(nbytes)
             else:
-                yield block(nbytes, cuts=(plan.cuts.ptr.value + 16 * a, 2 * (b - a)), cut_origin=int(plan.ro[a]))
+                yield block(nbytes, cuts=(plan.cuts.ptr.value + 8 * plan.per * a, plan.per * (b - a)), cut_origin=int(plan.ro[a]))
 
     def fastq_text(self, block_bytes=None):
         """The batch as 4-line FASTQ text (bytes), formatted on the device: record i is
@@ -409,7 +438,8 @@ class DeviceReads:
     def to_bam(self, path, header=None, block_bytes=256 << 20):
         """Writes the batch to `path` as unaligned BAM (uBAM: what basecallers write and every long-read mapper and
         samtools take; from_bam reads it back) and returns the bytes written.  Record i is an unmapped, unpaired record
-        (flag 4, no reference, no CIGAR, no tags) of read i: SEQ packed and QUAL turned into Phred values on the device
+        (flag 4, no reference, no CIGAR) of read i, with the read's tags behind QUAL where the batch has `.tags` (kept by
+        from_bam(keep_tags=True), made by set_tag) and without tags otherwise: SEQ packed and QUAL turned into Phred values on the device
         (sarlacc_dev_bam_format).  Its name is the read's name up to the first space or tab, as samtools import keeps it
         ('*' where nothing is left; READ_1, READ_2, ... without `.names`).  The records are formatted in ranges of whole
         records of at most `block_bytes`, as to_fastq plans its blocks; every range is deflated where it lies into BGZF
@@ -421,8 +451,11 @@ class DeviceReads:
         is header + end-of-file block.  There is no append: a BAM file has one header.
         Refused before the file is opened, so that it keeps what it held: an encoding other than Phred+33 (BAM stores
         Phred values), and "record K: <reason>" for the lowest record BAM cannot hold -- a kept name above 254 bytes or
-        with a byte outside '!'..'~', a base that is not one of ACMGRSVTWYHKDBN, a quality byte outside 33..126.
-        Not done here: tags, aligned records, @SQ headers, paired flags, indexes."""
+        with a byte outside '!'..'~', a base that is not one of ACMGRSVTWYHKDBN, a quality byte outside 33..126, malformed
+        tags, a tag that appears twice in one read.  With tags, the tag start of every record is a third piece boundary
+        of the deflate.
+        Not done here: @RG lines for the RG tags written (the header text is the caller's), aligned records, @SQ headers,
+        paired flags, indexes."""
         from . import bgzf, sam
         from .encoding import encoding_name
         if block_bytes is not None and int(block_bytes) < 1:
@@ -434,12 +467,52 @@ class DeviceReads:
         plan = self._write_plan(block_bytes, bam=True)
         return self._write_blocks(path, "wb", self._blocks(plan, compress=True, head=head), bgzf.EOF_BLOCK)
 
+    def _tags(self):
+        """`.tags`, checked against the batch."""
+        if len(self.tags) != len(self):
+            raise _lib.SarlaccError("tags of %d reads for %d reads" % (len(self.tags), len(self)))
+        return self.tags
+
+    def tag(self, name):
+        """The values of the tag `name` ([A-Za-z][A-Za-z0-9]) and a boolean mask of the reads that hold it, found on the
+        device (sarlacc_dev_bam_tags_find; the first entry of a repeated tag, as htslib's bam_aux_get).  Types A, Z and
+        H give a StrList (an empty string where the tag is absent), the integer types c C s S i I -- mixed widths
+        across the reads are fine -- an int64 array (0 where absent).  Strings and integers under one name are an
+        error ("read K: tag XX has type T"), and so are the types f and B, which are not decoded: they are kept and
+        written as they lie.  On a batch without tags, or where no read holds the tag, every read is absent and the
+        values are empty strings."""
+        from .tags import DeviceTags, tag_name
+        name = tag_name(name)
+        return (self._tags() if self.tags is not None else DeviceTags.empty(len(self))).values(name)
+
+    def set_tag(self, name, values, present=None):
+        """Sets the tag `name` on the reads where `present` (a boolean mask; None: on every read): replaced where a read
+        holds it, appended behind the read's other tags where not -- one find and one splice on the device
+        (sarlacc_dev_bam_tags_splice).  `values` (one per read, those outside `present` are ignored) are a StringSet, a
+        StrList or a list of str, written as type Z -- a byte outside ' '..'~' is refused --, or integers within int32,
+        written as type i.  A batch without `.tags` gets them."""
+        from .tags import DeviceTags, present_mask, tag_column, tag_name
+        name, column, mask = tag_name(name), tag_column(values, len(self)), present_mask(present, len(self))
+        tags = self._tags() if self.tags is not None else DeviceTags.empty(len(self))
+        self.tags = tags.set(name, column, mask)
+
+    def drop_tags(self, names):
+        """Removes every entry of the tags `names` (one name or several) from every read: what MM, ML and mv need
+        after a trim or a reversal, which nothing here rewrites."""
+        from .tags import tag_name
+        names = [tag_name(nm) for nm in ([names] if isinstance(names, (str, bytes)) else names)]
+        if self.tags is not None:
+            tags = self._tags()
+            for nm in names:
+                tags = tags.drop(nm)
+            self.tags = tags
+
     def _like(self, off_host):
         total = int(off_host[-1])
         return DeviceReads(DevBuffer(total), DevBuffer(total), DevBuffer.from_numpy(off_host), off_host, self.encoding)
 
     def front_and_back(self, tolerance):
-        """.get_front_and_back (R/adaptorAlign.R:86-95) on the device."""
+        """.get_front_and_back (R/adaptorAlign.R:86-95) on the device.  The two window batches carry no tags."""
         w = np.minimum(int(tolerance), np.diff(self.off_host))
         woff = np.zeros(len(self) + 1, np.int64)
         np.cumsum(w, out=woff[1:])
@@ -452,7 +525,7 @@ class DeviceReads:
 
     def subseq(self, start, width, other=None, from_other=None):
         """XVector::subseq on the resident batch, straight to a host StringSet: element r = `width[r]` bases from the 1-based
-        position `start[r]` of read r -- of `other`'s read r where `from_other[r]` (sarlacc_dev_subseq)."""
+        position `start[r]` of read r -- of `other`'s read r where `from_other[r]` (sarlacc_dev_subseq).  No tags go along."""
         n = len(self)
         st = np.ascontiguousarray(start, dtype=np.int32)
         wd = np.ascontiguousarray(np.maximum(np.asarray(width, dtype=np.int64), 0), dtype=np.int32)
@@ -467,7 +540,8 @@ class DeviceReads:
     def realize(self, idx, reversed_, trim_start=None, trim_end=None):
         """Reads `idx` (0-based) of this batch, reverse-complemented where `reversed_`, cut to the
         1-based inclusive [trim_start, trim_end] of the oriented read (whole read when None):
-        the device half of realizeReads (R/realizeReads.R:28-43)."""
+        the device half of realizeReads (R/realizeReads.R:28-43).  `.tags` go along in `idx` order, each read's bytes
+        unchanged (a splice with src): MM / ML / mv no longer fit a trimmed or reversed read -- drop_tags."""
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         rev = np.ascontiguousarray(reversed_, dtype=np.uint8)
         w = np.diff(self.off_host)[idx]
@@ -482,10 +556,12 @@ class DeviceReads:
         if idx.size:
             d_idx, d_rev, d_ts = DevBuffer.from_numpy(idx), DevBuffer.from_numpy(rev), DevBuffer.from_numpy(ts)   # kept alive over the call
             check(_lib.lib().sarlacc_dev_realize(self.seq, self.qual, self.off, d_idx, d_rev, d_ts, idx.size, d.off, d.seq, d.qual, None))
+        if self.tags is not None:
+            d.tags = self._tags().take(idx)
         return d
 
     def scramble(self, seed):
-        """.scramble_input (R/getAdaptorThresholds.R:68-92) on the device, deterministic in `seed`."""
+        """.scramble_input (R/getAdaptorThresholds.R:68-92) on the device, deterministic in `seed`.  The result carries no tags."""
         d = self._like(self.off_host.copy())
         check(_lib.lib().sarlacc_dev_scramble(self.seq, self.qual, self.off, len(self), int(seed), d.seq, d.qual, None))
         return d
