@@ -60,7 +60,12 @@ double sarlacc_stage_ms(const char* name);
 /* Work counters of the last call that set them (for rooflines): "msa_pairs", "msa_cells" (banded DP
  * cells of the pairwise alignments), "consensus_cells" (rows x width); "consensus_route" (the kernels the vote ran:
  * 0 k_consensus<false>, 1 k_consensus<true>, 2 k_consensus_q4, 3 k_consensus_qf then k_consensus_q4 on the groups it
- * flagged, 4 k_consensus_code) and "consensus_vote_passes" (1 + the runs repeated for a longer boundary list); <0 if unset. */
+ * flagged, 4 k_consensus_code) and "consensus_vote_passes" (1 + the runs repeated for a longer boundary list); of every
+ * UMI neighbour search "umi_pairs_words" (64-bit code words per string: 1 up to 32 bases, 4 up to 128, beyond what the
+ * longest string needs) and "umi_pairs_k" (the template K of the tile-pair kernel it ran: k_umi_pairs<K> at one word,
+ * k_umi_pairs_long<K, XL> beyond; -1 the long kernels' full DP; -2 no tile-pair kernel at all: a split-key search with no
+ * string that holds an N or is shorter than 8 bases, or a negative threshold); <0 if unset (-1).  Read
+ * "umi_pairs_words" first: while it is > 0 a search has run and an "umi_pairs_k" of -1 is the full DP, not "unset". */
 double sarlacc_stage_count(const char* name);
 /* Duration in ms of the DP kernel launches recorded by the last
  * sarlacc_dev_* align call (HIP events on the launch stream; a panel call: the sum over its DP launches); <0 if none. */

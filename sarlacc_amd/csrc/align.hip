@@ -185,8 +185,6 @@ struct TbStore<16> { using type = unsigned long long; };
 
 template <bool B>
 struct Flag { static constexpr bool value = B; };
-template <int V>
-struct Int { static constexpr int value = V; };
 
 // MODE 3 (adaptor_align, local, gapopen >= 0): no traceback stream at all.  The fill keeps only
 // scores, the landing row of column R and, every SNAP_P steps, a snapshot of the complete lane
@@ -2346,18 +2344,6 @@ static int raise_dynamic_lds(const void* kernel, size_t bytes) {
     if (bytes > set) SL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
     set = std::max(set, bytes);
     return 0;
-}
-
-// Runtime values -> template arguments: f(Int<V1>{}, Int<V2>{}, ...) with, from each list, the V that equals the runtime
-// value behind it; NO_KERNEL when a value is in none.
-constexpr int NO_KERNEL = -1;
-template <int... Vs> struct Ints {};
-template <typename F> static int pick(F&& f) { return f(); }
-template <typename F, int... Vs, typename... Rest>
-static int pick(F&& f, Ints<Vs...>, int v, Rest... rest) {
-    int rc = NO_KERNEL;
-    (void)((v == Vs && ((rc = pick([&](auto... tags) { return f(Int<Vs>{}, tags...); }, rest...)), true)) || ...);
-    return rc;
 }
 
 // The instantiations of k_align the library is built with (each costs compile time and code-object size).

@@ -141,6 +141,21 @@ int scratch(const std::string& name, size_t count, T** dev) {
     return 0;
 }
 
+// ---- runtime values -> template arguments -----------------------------------
+// pick(f, Ints<V...>{}, v, ...): f(Int<V1>{}, Int<V2>{}, ...) with, from each list, the V that equals the runtime value
+// behind it; NO_KERNEL when a value is in none.
+constexpr int NO_KERNEL = -1;
+template <int V>
+struct Int { static constexpr int value = V; };
+template <int... Vs> struct Ints {};
+template <typename F> static int pick(F&& f) { return f(); }
+template <typename F, int... Vs, typename... Rest>
+static int pick(F&& f, Ints<Vs...>, int v, Rest... rest) {
+    int rc = NO_KERNEL;
+    (void)((v == Vs && ((rc = pick([&](auto... tags) { return f(Int<Vs>{}, tags...); }, rest...)), true)) || ...);
+    return rc;
+}
+
 // ---- MSA stage with the rows left on the device (msa.hip) ---------------------
 // Rows as vote codes (fused MSA + quality consensus): the row writers know the read position of every cell, so they
 // can emit, instead of the character, the 16-bit code the vote kernel needs -- the index of the (quality, base)

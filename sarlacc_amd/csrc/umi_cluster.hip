@@ -3,7 +3,8 @@
 // sequential by definition; it is evaluated exactly, in parallel rounds: a node whose (remaining, index) key is the
 // maximum within two hops cannot be affected by any earlier pick, so all such nodes are picked in the same round.
 // The pick sequence of the reference is recovered by sorting the picks by their key (descending), solos first
-// (SURVEY section 0, App.B Q12).  Design: DESIGN.md "UMI stage".
+// (SURVEY section 0, App.B Q12).  This file: the kernels and one device step per round kind; the round control is
+// cluster_dev (umi_host.cpp).  Design: DESIGN.md "UMI stage".
 #include "umi_common.hpp"
 
 namespace sarlacc {
@@ -11,22 +12,7 @@ namespace sarlacc {
 // ---------------------------------------------------------------------------
 // greedy clustering in exact parallel rounds
 
-struct ClusterState {
-    const long long* off;
-    const int* nbr;
-    int n;
-    int* remaining;
-    int* state;                 // 0 live, 1 solo, 2 clustered
-    int* mark;                  // round in which the node was clustered
-    unsigned long long* key;
-    unsigned long long* m1;
-    int* seed;                  // 1 if picked as a seed (any round)
-    unsigned long long* pickkey;
-    int* memb;                  // members of the cluster seeded at v, stored at off[v]..
-    int* csize;
-    int* err;                   // [0] min index with empty list, [1] min index bad solo, [2] missing self / asymmetric
-    int* live;                  // count of live pool nodes this round
-};
+// (ClusterState, ClusterTop and the control block's names: umi_common.hpp)
 
 __global__ void k_cl_init(ClusterState S, int check_sym) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -173,22 +159,10 @@ __global__ void __launch_bounds__(256) k_cl_decrement_w(ClusterState S, int roun
 // within two hops -- hop1[w] = max key over candidates adjacent to w (lists are symmetric), and v is picked iff the
 // maximum of hop1 over its live neighbours is its own key.  Picks outside C are left for a later round (every pick is
 // valid on its own), so the clusters are those of the full rounds; the work per round is |C| lists instead of all.
-struct ClusterTop {
-    int* maxrem;                // largest remaining of a live node, this round
-    int* cand;                  // candidate list
-    int* counts;                // [0] candidates, [1] picks, [2] 1 when the list was cut off at `cap`, [3] nodes clustered this round
-    unsigned long long* hop1;
-    int cap;
-    int* marked;                // the nodes clustered this round (two picks of a round share no neighbour: no node twice)
-    int* ctl;                   // the rounds' control block, see k_cl_control
-};
 // Control block of the candidate-set rounds.  The decisions between two rounds -- is anything left, did the last candidate
 // list overflow, how wide is the next one -- need three counters of the round before; taken on the host they cost one
 // read-back per round (190 us per round with its six launches, 330 rounds at threshold 3 on 10^6 12-base UMIs).  k_cl_control
 // takes them on the device, every kernel of a round looks at the mode first, and the host enqueues CL_GROUP rounds at a time.
-enum { CTL_MODE, CTL_DELTA, CTL_WAS_TOP, CTL_ROUNDS, CTL_MAXREM, CTL_N = 8 };
-enum { CL_DONE = 0, CL_TOP = 1, CL_WANTS_FULL = 3 };   // CL_WANTS_FULL: the list was cut off -- the host runs one round over every list
-constexpr int CL_GROUP = 8;
 
 __global__ void __launch_bounds__(1024) k_cl_keys_top(ClusterState S, ClusterTop T) {
     __shared__ int s_live[16], s_max[16];
@@ -383,128 +357,108 @@ __global__ void k_cl_write(ClusterState S, const int* order, long long nclu, con
     }
 }
 
-// Greedy clustering of a device CSR graph.  `require_symmetric` is the documented
-// precondition of this implementation (the reference's results on asymmetric input
-// are an accident of its update order; umi_group always produces symmetric lists).
-int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const int* d_gid, int ngroups, bool check_sym,
-                ClusterResult* res, hipStream_t s) {
+// ---------------------------------------------------------------------------
+// device steps (umi_common.hpp); cluster_dev (umi_host.cpp) runs them
+
+// one wavefront per node in the dense rounds, one thread per node otherwise
+static dim3 per_node(const ClusterState& S) { return dim3(nblk(S.n, 256)); }
+static dim3 per_node_w(const ClusterState& S) { return dim3(nblk(S.n, 4)); }
+static const dim3 CL_B(256);
+
+void gid_keys(const int* gid, const int* val, long long n, unsigned long long* key, hipStream_t s) {
+    hipLaunchKernelGGL(k_cl_gidkey, dim3(nblk(n, 256)), CL_B, 0, s, gid, val, n, key);
+}
+
+// The state of a clustering and k_cl_init; herr: the three error indices it found (INT_MAX: none).
+int cluster_begin(const DevAdj& adj, int n, bool check_sym, ClusterState* S, int herr[3], hipStream_t s) {
     const std::string p = UMI_WS[WS_CL];
-    ClusterState S{};
-    S.off = adj.off; S.nbr = adj.nbr; S.n = n;
+    S->off = adj.off; S->nbr = adj.nbr; S->n = n;
     const size_t nn = static_cast<size_t>(n) + 1;
-    SL_TRY(scratch(p + ".remaining", nn, &S.remaining));
-    SL_TRY(scratch(p + ".state", nn, &S.state));
-    SL_TRY(scratch(p + ".mark", nn, &S.mark));
-    SL_TRY(scratch(p + ".key", nn, &S.key));
-    SL_TRY(scratch(p + ".m1", nn, &S.m1));
-    SL_TRY(scratch(p + ".seed", nn, &S.seed));
-    SL_TRY(scratch(p + ".pickkey", nn, &S.pickkey));
-    SL_TRY(scratch(p + ".memb", static_cast<size_t>(adj.nnz) + 1, &S.memb));
-    SL_TRY(scratch(p + ".csize", nn, &S.csize));
-    SL_TRY(scratch(p + ".err", 3, &S.err));
-    SL_TRY(scratch(p + ".live", 1, &S.live));
+    SL_TRY(scratch(p + ".remaining", nn, &S->remaining));
+    SL_TRY(scratch(p + ".state", nn, &S->state));
+    SL_TRY(scratch(p + ".mark", nn, &S->mark));
+    SL_TRY(scratch(p + ".key", nn, &S->key));
+    SL_TRY(scratch(p + ".m1", nn, &S->m1));
+    SL_TRY(scratch(p + ".seed", nn, &S->seed));
+    SL_TRY(scratch(p + ".pickkey", nn, &S->pickkey));
+    SL_TRY(scratch(p + ".memb", static_cast<size_t>(adj.nnz) + 1, &S->memb));
+    SL_TRY(scratch(p + ".csize", nn, &S->csize));
+    SL_TRY(scratch(p + ".err", 3, &S->err));
+    SL_TRY(scratch(p + ".live", 1, &S->live));
     const int big = std::numeric_limits<int>::max();
     const int init[3] = {big, big, big};
-    SL_HIP(hipMemcpyAsync(S.err, init, sizeof init, hipMemcpyHostToDevice, s));
-    const dim3 g(nblk(n, 256)), b(256), gw(nblk(n, 4));
-    // one wavefront per node from 24 links per node on average (one thread per node below that)
-    const bool dense = adj.nnz >= 24LL * n;
-    ctx().counts["umi_links"] = static_cast<double>(adj.nnz);
-    ctx().counts["umi_cluster_candidate_rounds"] = 0;
-    ctx().counts["umi_cluster_full_rounds"] = 0;
-    hipLaunchKernelGGL(k_cl_init, g, b, 0, s, S, check_sym ? 1 : 0);
-    int herr[3];
-    SL_HIP(hipMemcpyAsync(herr, S.err, sizeof herr, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipMemcpyAsync(S->err, init, sizeof init, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_cl_init, per_node(*S), CL_B, 0, s, *S, check_sym ? 1 : 0);
+    SL_HIP(hipMemcpyAsync(herr, S->err, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));
-    // first error in index order, as the reference's loop would meet it (src/cluster_umis.cpp:21-40)
-    if (herr[0] != big || herr[1] != big) {
-        if (herr[0] < herr[1]) return fail("zero length read group");
-        return fail("single-read groups should contain only the read itself");
-    }
-    if (herr[2] != big)
-        return fail("sarlacc_amd: neighbour lists must be symmetric and contain the read itself (list %d is not)", herr[2] + 1);
+    return 0;
+}
 
-    ClusterTop T{};
-    if (dense) {
-        SL_TRY(scratch(p + ".maxrem", 1, &T.maxrem));
-        SL_TRY(scratch(p + ".counts", 4, &T.counts));
-        SL_TRY(scratch(p + ".hop1", nn, &T.hop1));
-        T.cap = std::max(1024, n / 8);
-        SL_TRY(scratch(p + ".cand", static_cast<size_t>(T.cap), &T.cand));
-        SL_HIP(hipMemsetAsync(T.counts, 0, 4 * sizeof(int), s));
-    }
-    const bool top_rounds = dense && !option(OPT_UMI_FULL_ROUNDS);
-    long long top_rounds_run = 0, full_rounds_run = 0;
-    int rounds_total = 0;
-    if (top_rounds) {
-        // Candidate-set rounds under the device's control (k_cl_control): CL_GROUP rounds per read-back.  A round whose list
-        // was cut off parks the control block (CL_WANTS_FULL; the rounds still queued behind it do nothing) and the host
-        // runs that round over every list, as before.
-        SL_TRY(scratch(p + ".marked", nn, &T.marked));
-        SL_TRY(scratch(p + ".ctl", CTL_N, &T.ctl));
-        int hctl[CTL_N] = {CL_TOP, 0, 0, 0, 0, 0, 0, 0};
-        SL_HIP(hipMemcpyAsync(T.ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s));
-        SL_HIP(hipMemsetAsync(S.live, 0, sizeof(int), s));
-        SL_HIP(hipMemsetAsync(T.maxrem, 0, sizeof(int), s));
-        int round = 0;
-        for (;;) {
-            for (int q = 0; q < CL_GROUP; ++q, ++round) {
-                hipLaunchKernelGGL(k_cl_keys_top, dim3(nblk(n, 1024)), dim3(1024), 0, s, S, T);
-                hipLaunchKernelGGL(k_cl_control, dim3(1), dim3(1), 0, s, S, T);
-                hipLaunchKernelGGL(k_cl_collect, g, b, 0, s, S, T, 0);
-                hipLaunchKernelGGL(k_cl_mark_top, dim3(1024), b, 0, s, S, T);
-                hipLaunchKernelGGL(k_cl_pick_top, dim3(1024), b, 0, s, S, T, round);
-                hipLaunchKernelGGL(k_cl_commit_list, dim3(64), b, 0, s, S, T);
-                hipLaunchKernelGGL(k_cl_decrement_list, dim3(1024), b, 0, s, S, T);
-            }
-            SL_HIP(hipGetLastError());
-            SL_HIP(hipMemcpyAsync(hctl, T.ctl, sizeof hctl, hipMemcpyDeviceToHost, s));
-            SL_HIP(hipStreamSynchronize(s));
-            if (hctl[CTL_MODE] == CL_DONE) break;
-            if (hctl[CTL_MODE] == CL_WANTS_FULL) {   // (the keys are those of the round that asked: nothing changed since)
-                hipLaunchKernelGGL(k_cl_m1_w, gw, b, 0, s, S);
-                hipLaunchKernelGGL(k_cl_pick_w, gw, b, 0, s, S, round);
-                hipLaunchKernelGGL(k_cl_commit, g, b, 0, s, S, round);
-                hipLaunchKernelGGL(k_cl_decrement_w, gw, b, 0, s, S, round);
-                ++round; ++full_rounds_run;
-                const int back[3] = {CL_TOP, hctl[CTL_DELTA], 0};
-                SL_HIP(hipMemcpyAsync(T.ctl, back, sizeof back, hipMemcpyHostToDevice, s));
-                SL_HIP(hipStreamSynchronize(s));   // (`back` is on this frame)
-            }
-            if (hctl[CTL_ROUNDS] + full_rounds_run > 4LL * n + 16) return fail("sarlacc_amd: clustering did not converge");
-        }
-        top_rounds_run = hctl[CTL_ROUNDS];
-        rounds_total = static_cast<int>(top_rounds_run + full_rounds_run);
-    } else {
-        for (int round = 0;; ++round) {
-            SL_HIP(hipMemsetAsync(S.live, 0, sizeof(int), s));
-            hipLaunchKernelGGL(k_cl_keys, g, b, 0, s, S);
-            int live = 0;
-            SL_HIP(hipMemcpyAsync(&live, S.live, sizeof live, hipMemcpyDeviceToHost, s));
-            SL_HIP(hipStreamSynchronize(s));
-            if (live == 0) break;
-            if (dense) {
-                hipLaunchKernelGGL(k_cl_m1_w, gw, b, 0, s, S);
-                hipLaunchKernelGGL(k_cl_pick_w, gw, b, 0, s, S, round);
-                hipLaunchKernelGGL(k_cl_commit, g, b, 0, s, S, round);
-                hipLaunchKernelGGL(k_cl_decrement_w, gw, b, 0, s, S, round);
-            } else {
-                hipLaunchKernelGGL(k_cl_m1, g, b, 0, s, S);
-                hipLaunchKernelGGL(k_cl_pick, g, b, 0, s, S, round);
-                hipLaunchKernelGGL(k_cl_commit, g, b, 0, s, S, round);
-                hipLaunchKernelGGL(k_cl_decrement, g, b, 0, s, S, round);
-            }
-            SL_HIP(hipGetLastError());
-            if (round > 4 * n + 16) return fail("sarlacc_amd: clustering did not converge");
-            ++full_rounds_run;
-            rounds_total = round + 1;
-        }
-    }
-    ctx().counts["umi_cluster_rounds"] = rounds_total;
-    ctx().counts["umi_cluster_candidate_rounds"] = static_cast<double>(top_rounds_run);
-    ctx().counts["umi_cluster_full_rounds"] = static_cast<double>(full_rounds_run);
+// Scratch of the candidate-set rounds (dense graphs); control: with the control block, set to start them.
+int cluster_candidates_begin(const ClusterState& S, bool control, ClusterTop* T, hipStream_t s) {
+    const std::string p = UMI_WS[WS_CL];
+    const size_t nn = static_cast<size_t>(S.n) + 1;
+    SL_TRY(scratch(p + ".maxrem", 1, &T->maxrem));
+    SL_TRY(scratch(p + ".counts", 4, &T->counts));
+    SL_TRY(scratch(p + ".hop1", nn, &T->hop1));
+    T->cap = std::max(1024, S.n / 8);
+    SL_TRY(scratch(p + ".cand", static_cast<size_t>(T->cap), &T->cand));
+    SL_HIP(hipMemsetAsync(T->counts, 0, 4 * sizeof(int), s));
+    if (!control) return 0;
+    SL_TRY(scratch(p + ".marked", nn, &T->marked));
+    SL_TRY(scratch(p + ".ctl", CTL_N, &T->ctl));
+    static const int hctl[CTL_N] = {CL_TOP, 0, 0, 0, 0, 0, 0, 0};
+    SL_HIP(hipMemcpyAsync(T->ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s));
+    SL_HIP(hipMemsetAsync(S.live, 0, sizeof(int), s));
+    SL_HIP(hipMemsetAsync(T->maxrem, 0, sizeof(int), s));
+    return 0;
+}
 
-    // ---- output order: solos by index, then picks by key descending ----
+// this round's keys; *live: how many nodes are left
+int cluster_count_live(const ClusterState& S, int* live, hipStream_t s) {
+    SL_HIP(hipMemsetAsync(S.live, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_cl_keys, per_node(S), CL_B, 0, s, S);
+    *live = 0;
+    SL_HIP(hipMemcpyAsync(live, S.live, sizeof *live, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// CL_GROUP candidate-set rounds under the device's control (k_cl_control)
+void rounds_candidates(const ClusterState& S, const ClusterTop& T, int* round, hipStream_t s) {
+    for (int q = 0; q < CL_GROUP; ++q, ++*round) {
+        hipLaunchKernelGGL(k_cl_keys_top, dim3(nblk(S.n, 1024)), dim3(1024), 0, s, S, T);
+        hipLaunchKernelGGL(k_cl_control, dim3(1), dim3(1), 0, s, S, T);
+        hipLaunchKernelGGL(k_cl_collect, per_node(S), CL_B, 0, s, S, T, 0);
+        hipLaunchKernelGGL(k_cl_mark_top, dim3(1024), CL_B, 0, s, S, T);
+        hipLaunchKernelGGL(k_cl_pick_top, dim3(1024), CL_B, 0, s, S, T, *round);
+        hipLaunchKernelGGL(k_cl_commit_list, dim3(64), CL_B, 0, s, S, T);
+        hipLaunchKernelGGL(k_cl_decrement_list, dim3(1024), CL_B, 0, s, S, T);
+    }
+}
+
+// one round over every list, a wavefront per node (the keys are this round's already)
+void round_dense(const ClusterState& S, int round, hipStream_t s) {
+    hipLaunchKernelGGL(k_cl_m1_w, per_node_w(S), CL_B, 0, s, S);
+    hipLaunchKernelGGL(k_cl_pick_w, per_node_w(S), CL_B, 0, s, S, round);
+    hipLaunchKernelGGL(k_cl_commit, per_node(S), CL_B, 0, s, S, round);
+    hipLaunchKernelGGL(k_cl_decrement_w, per_node_w(S), CL_B, 0, s, S, round);
+}
+
+// the same, a thread per node
+void round_sparse(const ClusterState& S, int round, hipStream_t s) {
+    hipLaunchKernelGGL(k_cl_m1, per_node(S), CL_B, 0, s, S);
+    hipLaunchKernelGGL(k_cl_pick, per_node(S), CL_B, 0, s, S, round);
+    hipLaunchKernelGGL(k_cl_commit, per_node(S), CL_B, 0, s, S, round);
+    hipLaunchKernelGGL(k_cl_decrement, per_node(S), CL_B, 0, s, S, round);
+}
+
+// Output order -- solos by index, then picks by key descending, pre-group by pre-group -- and the clusters written in it.
+int clusters_write(const ClusterState& S, const int32_t* d_members, const int* d_gid, int ngroups, ClusterResult* res, hipStream_t s) {
+    const std::string p = UMI_WS[WS_CL];
+    const int n = S.n;
+    const size_t nn = static_cast<size_t>(n) + 1;
+    const dim3 g = per_node(S), b = CL_B;
     int *d_issolo, *d_isseed, *d_order, *d_val, *d_val2, *d_sizes;
     long long *d_spos, *d_kpos;
     unsigned long long *d_sk, *d_sk2;
@@ -532,7 +486,7 @@ int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const int* d
         hipLaunchKernelGGL(k_cl_list, g, b, 0, s, d_issolo, d_spos, d_isseed, d_kpos, nsolo, S.pickkey, n, d_sk, d_val);
         SL_TRY(radix_sort_pairs(p + ".sorttmp", d_sk, d_sk2, d_val, d_val2, static_cast<size_t>(nclu), 64, s));
         if (d_gid && ngroups > 1) {  // stable: keeps the in-group order, groups in input order
-            hipLaunchKernelGGL(k_cl_gidkey, dim3(nblk(nclu, 256)), b, 0, s, d_gid, d_val2, nclu, d_sk);
+            gid_keys(d_gid, d_val2, nclu, d_sk, s);
             SL_TRY(radix_sort_pairs(p + ".sorttmp", d_sk, d_sk2, d_val2, d_val, static_cast<size_t>(nclu),
                                     ceil_log2(static_cast<unsigned long long>(ngroups) + 1), s));
             SL_HIP(hipMemcpyAsync(d_order, d_val, sizeof(int) * static_cast<size_t>(nclu), hipMemcpyDeviceToDevice, s));
@@ -553,7 +507,7 @@ int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const int* d
         SL_HIP(hipMemcpyAsync(&res->total, d_coff + nclu, sizeof(long long), hipMemcpyDeviceToHost, s));
         SL_HIP(hipStreamSynchronize(s));
     } else {
-        const long long zero = 0;
+        static const long long zero = 0;
         SL_HIP(hipMemcpyAsync(d_coff, &zero, sizeof zero, hipMemcpyHostToDevice, s));
         res->total = 0;
     }

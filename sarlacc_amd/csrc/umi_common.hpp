@@ -1,8 +1,13 @@
 // umi_common.hpp -- what the UMI sources share: string constants and layout, workspace names, the doubled masked
-// Levenshtein distance on one-word and multi-word operands, and the host interfaces between
-//   umi_search.hip   encoding, tile search, split-key search (pair_edges, neighbour_keys)
-//   umi_cluster.hip  greedy clustering (cluster_dev)
-//   umi.hip          adjacency, dense distances, the entry points and the pair exchange
+// Levenshtein distance on one-word and multi-word operands, the plan structs and the device steps.  The stage is split
+// like the align, MSA and consensus stages:
+//   umi_host.cpp     everything that decides: the C entry points, the search plan and the sample / retry loop
+//                    (pair_edges), the words decision of the encode, the clustering's round control (cluster_dev), every
+//                    user-facing error, counter and timer
+//   umi_search.hip   kernels and device steps of the encoding, the tile search and the split-key search
+//   umi_cluster.hip  kernels and device steps of the greedy clustering
+//   umi.hip          kernels and device steps of the adjacency, the dense distances and the pair check
+// A kernel is launched only from the file that defines it; the .hip files hold no policy (see "device steps" below).
 #pragma once
 
 #include "common.hpp"
@@ -31,7 +36,7 @@ constexpr int TILE = 256;
 constexpr int INF_D = 1 << 20;
 
 // Workspace names.  Every device buffer of the UMI code is named "<prefix>.<what>" with a prefix of this table, so that
-// sarlacc_release_umi_workspace (umi.hip) gives back exactly the UMI stage's buffers.
+// sarlacc_release_umi_workspace (umi_host.cpp) gives back exactly the UMI stage's buffers.
 enum UmiWs { WS_U1, WS_U2, WS_G1, WS_G2, WS_G, WS_PS, WS_LV, WS_LEV, WS_ADJ, WS_CL, WS_N };
 inline constexpr const char* UMI_WS[WS_N] = {
     "u1", "u2",           // encode_and_rank and the searches of UMI1 / UMI2
@@ -149,7 +154,7 @@ __device__ __forceinline__ int full_lev2(const Str a, int la, const Str b, int l
 }
 
 // ---------------------------------------------------------------------------
-// host interfaces between the UMI sources
+// what travels between the steps
 
 struct SortedUmis {
     UmiArrays U;   // in (pre-group, trie) order
@@ -180,26 +185,153 @@ struct ClusterResult {
     long long total = 0;
 };
 
+// ---------------------------------------------------------------------------
+// the search plan (made by pair_edges, umi_host.cpp; turned into launches by pair_search and split_scans)
+
+constexpr int SK_MIN_LEN = 8;            // shorter strings are "special" (keys under 4 bases select too much)
+constexpr int SK_MAX_KEY = 8;            // bases per key at most (9 bases of the forward string travel with every element)
+
+struct SkClass { int len_lo, len_hi, h, s; bool two; };   // rows of lengths len_lo..len_hi scan with keys of h and s bases; two: by k_sk_scan_pk
+
+struct SkPlan {
+    std::vector<SkClass> classes;   // row lengths present in the set, with the key lengths they scan with
+    int k1 = 0, k2 = 0;             // edits allowed in the prefix / suffix key
+    long long nspecial = 0;
+};
+
+constexpr int PAIRS_K_FULL = -1;    // SearchPlan::K: the long kernels' full DP
+constexpr int PAIRS_K_NONE = -2;    // SearchPlan::K: no tile-pair kernel in the plan
+
+struct SearchPlan {
+    int limit = 0;
+    int words = 1;                  // SortedUmis::words
+    bool xl = false;                // more than UMI_LONG_WORDS words: k_umi_pairs_long<K, true>
+    int K = PAIRS_K_NONE;           // template K of k_umi_pairs / k_umi_pairs_long
+    bool split = false;             // the split-key scans run, by `sk`
+    SkPlan sk;
+    bool tiles = true;              // the tile-pair kernel is part of the search (split: for the pairs with a special member)
+    bool filter = false;            // k_tile_info and k_tile_pairs<L> list the tile pairs to search
+    int L = 0;
+    int special_lreq = -1;          // PairArgs::special_lreq
+    int nt = 0, tile_lo = 0, tile_hi = 0;   // tiles of the set; the row tiles of this search
+    uint32_t row_lo = 0, row_hi = 0;        // the same as trie ranks
+    bool sample_tiles = false;      // a sampled pass may run first: over every sample_stride-th listed tile pair ...
+    bool sample_items = false;      // ... and work item of the scans; it runs when either has SAMPLE_MIN entries
+};
+
+struct SkElem;
+struct TileInfo;
+
+struct SkOrder {
+    SkElem* el;                  // [n] in scan order
+    unsigned long long* okey;    // [n] 3 bits per base (A..T = 1..4, N = 5, past the end = 0), first 21 bases, in scan order
+    int* gid;                    // [n] pre-group in scan order (nullptr: one group)
+    int n;
+};
+
+struct SkScan {          // one scan order with row groups for one key length, ready to launch
+    SkOrder O{};
+    int key = 0;
+    int* rg_start = nullptr;
+    int nrg = 0;
+    int2* ranges = nullptr;
+    int *nranges = nullptr, *ctotal = nullptr;
+    long long* item_off = nullptr;
+    long long nitems = 0;
+};
+
+struct SplitOrders { std::vector<SkScan> fwd, rev; };
+
+struct TileList {               // what the tile filter kept (list == nullptr: no filter, every tile pair is searched)
+    const uint32_t* list = nullptr;
+    const TileInfo* sub = nullptr;
+    unsigned int n = 0;
+};
+
+struct PairBuffer { unsigned long long *edges, *count, cap; };
+
+// ---------------------------------------------------------------------------
+// clustering state (umi_cluster.hip's kernels take it by value; cluster_dev, umi_host.cpp, runs the rounds)
+
+struct ClusterState {
+    const long long* off;
+    const int* nbr;
+    int n;
+    int* remaining;
+    int* state;                 // 0 live, 1 solo, 2 clustered
+    int* mark;                  // round in which the node was clustered
+    unsigned long long* key;
+    unsigned long long* m1;
+    int* seed;                  // 1 if picked as a seed (any round)
+    unsigned long long* pickkey;
+    int* memb;                  // members of the cluster seeded at v, stored at off[v]..
+    int* csize;
+    int* err;                   // [0] min index with empty list, [1] min index bad solo, [2] missing self / asymmetric
+    int* live;                  // count of live pool nodes this round
+};
+
+struct ClusterTop {             // candidate-set rounds, see umi_cluster.hip
+    int* maxrem;                // largest remaining of a live node, this round
+    int* cand;                  // candidate list
+    int* counts;                // [0] candidates, [1] picks, [2] 1 when the list was cut off at `cap`, [3] nodes clustered this round
+    unsigned long long* hop1;
+    int cap;
+    int* marked;                // the nodes clustered this round (two picks of a round share no neighbour: no node twice)
+    int* ctl;                   // the rounds' control block, see k_cl_control
+};
+enum { CTL_MODE, CTL_DELTA, CTL_WAS_TOP, CTL_ROUNDS, CTL_MAXREM, CTL_N = 8 };
+enum { CL_DONE = 0, CL_TOP = 1, CL_WANTS_FULL = 3 };   // CL_WANTS_FULL: the list was cut off -- the host runs one round over every list
+constexpr int CL_GROUP = 8;     // candidate-set rounds per read-back of the control block
+
+// ---------------------------------------------------------------------------
+// device steps: device arrays and sizes in, kernels / scans / sorts enqueued on the stream, device arrays out.  A step may
+// name scratch and read back the one size its own output needs; it decides nothing, sets no counter and raises only HIP
+// and allocation errors (and, in tile_filter and pair_search, an "internal error" when the plan names a template instance
+// the library is not built with: unreachable while plan_search and their Ints<...> lists agree).
+
+struct EncodeIn {
+    const uint8_t* chars; const int64_t* off;
+    const int32_t* members;     // optional 1-based ids selecting the strings
+    const uint8_t* skip;        // optional: elements encoded as empty strings
+    int n;
+};
+struct Encoded {
+    UmiArrays raw;              // in input order: "<p>.raw" at one word, "<p>.rawL" beyond
+    unsigned long long *khi, *klo, *keys;   // sort keys: two at one word, (maxlen + 20) / 21 planes beyond
+    int* idx;
+    int bad_char, too_long;     // first string with a character outside ACGTN / of more than 32 bases (INT_MAX: none)
+    int maxlen;                 // of the strings of more than 32 bases
+};
+
 // umi_search.hip
-__global__ void k_umi_encode(const uint8_t* chars, const int64_t* off, const int32_t* members, int n, UmiArrays U,
-                             unsigned long long* key_hi, unsigned long long* key_lo, int* idx, const uint8_t* skip, int* bad);
-__global__ void k_umi_encode_long(const uint8_t* chars, const int64_t* off, const int32_t* members, int n, UmiArrays U,
-                                  unsigned long long* keys, int* idx, const uint8_t* skip, int* bad, int words, int nkeys);
-int alloc_umi(const std::string& p, size_t n, UmiArrays* U, int words = 1);
-int encode_and_rank(const std::string& p, const uint8_t* d_chars, const int64_t* d_off, const int32_t* d_members,
-                    const int* d_gid, int ngroups, int n, SortedUmis* out, hipStream_t s, const uint8_t* d_skip = nullptr,
-                    int nskip = 0, int max_group = 0);
-int pair_edges(const std::string& p, const SortedUmis& S, int limit, int tile_lo, int tile_hi,
-               unsigned long long** d_edges_out, unsigned long long* m_out, hipStream_t s);
-int neighbour_keys(const std::string& p, const SortedUmis& S, int limit, const uint8_t* d_single, DirectedKeys* out, hipStream_t s);
+int encode_at(const std::string& p, const EncodeIn& in, int words, int maxlen, Encoded* e, hipStream_t s);
+int rank_umis(const std::string& p, const Encoded& e, int words, const int* d_gid, int ngroups, int n, SortedUmis* out, hipStream_t s);
+int length_hist(const std::string& p, const SortedUmis& S, unsigned int hist[34], hipStream_t s);
+int split_orders(const std::string& p, const SortedUmis& S, const SkPlan& plan, SplitOrders* out, hipStream_t s);
+int tile_filter(const std::string& p, const SortedUmis& S, const SearchPlan& P, TileList* out, hipStream_t s);
+void split_scans(const SplitOrders& O, const SearchPlan& P, unsigned stride, const PairBuffer& b, long long* items, int* two_columns, hipStream_t s);
+int pair_search(const SortedUmis& S, const SearchPlan& P, const TileList& T, unsigned stride, const PairBuffer& b, hipStream_t s);
 
 // umi.hip
-int keys_from_edges(const std::string& p, const SortedUmis& S, int limit, const uint8_t* d_single,
-                    const unsigned long long* d_edges, unsigned long long m, DirectedKeys* out, hipStream_t s);
+struct SelfLinks { int* flag; long long* pos; long long n; };
+int self_links(const std::string& p, const SortedUmis& S, int limit, const uint8_t* d_single, SelfLinks* out, hipStream_t s);
+int directed_keys(const std::string& p, const SortedUmis& S, const unsigned long long* d_edges, unsigned long long m,
+                  const SelfLinks& self, DirectedKeys* out, hipStream_t s);
+int adjacency_from_keys(const unsigned long long* keys, long long nk, const int* perm, int n, DevAdj* adj, hipStream_t s);
+int link_set(const std::string& p, const DirectedKeys& K, const int* perm, unsigned long long** d_set, hipStream_t s);
+int links_in_set(const std::string& p, const DirectedKeys& K, const int* perm, const unsigned long long* d_set, long long nset,
+                 DirectedKeys* kept, hipStream_t s);
+int check_pairs(const unsigned long long* d_edges, long long npairs, long long n, int* bad, hipStream_t s);
+int dense_distances(const std::string& p, const UmiArrays& U, int n, int words, double** d_out, hipStream_t s);
 
 // umi_cluster.hip
-__global__ void k_cl_gidkey(const int* gid, const int* val, long long n, unsigned long long* key);
-int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const int* d_gid, int ngroups, bool check_sym,
-                ClusterResult* res, hipStream_t s);
+void gid_keys(const int* gid, const int* val, long long n, unsigned long long* key, hipStream_t s);
+int cluster_begin(const DevAdj& adj, int n, bool check_sym, ClusterState* S, int herr[3], hipStream_t s);
+int cluster_candidates_begin(const ClusterState& S, bool control, ClusterTop* T, hipStream_t s);
+int cluster_count_live(const ClusterState& S, int* live, hipStream_t s);
+void rounds_candidates(const ClusterState& S, const ClusterTop& T, int* round, hipStream_t s);
+void round_dense(const ClusterState& S, int round, hipStream_t s);
+void round_sparse(const ClusterState& S, int round, hipStream_t s);
+int clusters_write(const ClusterState& S, const int32_t* d_members, const int* d_gid, int ngroups, ClusterResult* res, hipStream_t s);
 
 }  // namespace sarlacc

@@ -4,7 +4,8 @@
 // order: 2-bit packed bases + N bit-mask per UMI, one thread per (row, tile), columns broadcast from LDS, a
 // composition / length lower bound rejecting most pairs, then an exact banded DP in registers (band = limit, costs x2
 // as in src/sorted_trie.cpp:13-21).  Only the upper triangle is evaluated.  Thresholds 1 to 3 on large sets take the
-// split-key search below instead.  Design: DESIGN.md "UMI stage".
+// split-key search below instead.  This file: the kernels and the device steps that enqueue them; which of them a call
+// runs is decided in umi_host.cpp (plan_search, pair_edges).  Design: DESIGN.md "UMI stage".
 #include "umi_common.hpp"
 
 namespace sarlacc {
@@ -492,13 +493,6 @@ struct SkElem {
     uint32_t rank;       // rank in trie order
 };
 
-struct SkOrder {
-    SkElem* el;                  // [n] in scan order
-    unsigned long long* okey;    // [n] 3 bits per base (A..T = 1..4, N = 5, past the end = 0), first 21 bases, in scan order
-    int* gid;                    // [n] pre-group in scan order (nullptr: one group)
-    int n;
-};
-
 __device__ __forceinline__ uint32_t sk_even_bits(unsigned long long x) {   // bits 0, 2, 4, ... of x -> bits 0, 1, 2, ...
     x &= 0x5555555555555555ull;
     x = (x | (x >> 1)) & 0x3333333333333333ull;
@@ -883,9 +877,9 @@ __global__ void __launch_bounds__(SK_COLS / 2) k_sk_scan_pk(const SkScanArgs A) 
 }
 
 // ---------------------------------------------------------------------------
-// host orchestration
+// device steps (umi_common.hpp); encode_and_rank and pair_edges (umi_host.cpp) run them
 
-int alloc_umi(const std::string& p, size_t n, UmiArrays* U, int words) {
+static int alloc_umi(const std::string& p, size_t n, UmiArrays* U, int words = 1) {
     U->stride = static_cast<long long>(n);
     SL_TRY(scratch(p + ".code", n * static_cast<size_t>(words), &U->code));
     SL_TRY(scratch(p + ".nmask", n * static_cast<size_t>(words), &U->nmask));
@@ -894,63 +888,58 @@ int alloc_umi(const std::string& p, size_t n, UmiArrays* U, int words) {
     return 0;
 }
 
-// Encode one set of UMIs (optionally the members of a pre-group) and order it like the trie.
-int encode_and_rank(const std::string& p, const uint8_t* d_chars, const int64_t* d_off, const int32_t* d_members,
-                    const int* d_gid, int ngroups, int n, SortedUmis* out, hipStream_t s, const uint8_t* d_skip,
-                    int nskip, int max_group) {
-    out->nskip = d_skip ? nskip : 0;
-    out->max_group = max_group > 0 ? max_group : n;
-    UmiArrays raw;
-    SL_TRY(alloc_umi(p + ".raw", n, &raw));
-    SL_TRY(alloc_umi(p + ".srt", n, &out->U));
-    unsigned long long *khi, *klo, *k2;
-    int *idx, *idx2, *bad;
-    SL_TRY(scratch(p + ".khi", n, &khi));
-    SL_TRY(scratch(p + ".klo", n, &klo));
-    SL_TRY(scratch(p + ".k2", n, &k2));
-    SL_TRY(scratch(p + ".idx", n, &idx));
-    SL_TRY(scratch(p + ".idx2", n, &idx2));
+// Encode at `words` words, in input order: at one word k_umi_encode into "<p>.raw" (strings of more than 32 bases come
+// back in too_long / maxlen), beyond k_umi_encode_long into "<p>.rawL" with one sort key per 21 bases of `maxlen`.
+int encode_at(const std::string& p, const EncodeIn& in, int words, int maxlen, Encoded* e, hipStream_t s) {
+    const int n = in.n;
+    int* bad;
+    SL_TRY(scratch(p + ".idx", n, &e->idx));
     SL_TRY(scratch(p + ".bad", 3, &bad));
     const int init[3] = {std::numeric_limits<int>::max(), std::numeric_limits<int>::max(), 0};
     SL_HIP(hipMemcpyAsync(bad, init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_umi_encode, dim3(nblk(n, 256)), dim3(256), 0, s, d_chars, d_off, d_members, n, raw, khi, klo, idx, d_skip, bad);
+    if (words == 1) {
+        SL_TRY(alloc_umi(p + ".raw", n, &e->raw));
+        SL_TRY(scratch(p + ".khi", n, &e->khi));
+        SL_TRY(scratch(p + ".klo", n, &e->klo));
+        hipLaunchKernelGGL(k_umi_encode, dim3(nblk(n, 256)), dim3(256), 0, s, in.chars, in.off, in.members, n, e->raw, e->khi, e->klo, e->idx, in.skip, bad);
+    } else {
+        const int nkeys = (maxlen + UMI_KEY_BASES - 1) / UMI_KEY_BASES;
+        SL_TRY(alloc_umi(p + ".rawL", n, &e->raw, words));
+        SL_TRY(scratch(p + ".keysL", static_cast<size_t>(n) * nkeys, &e->keys));
+        hipLaunchKernelGGL(k_umi_encode_long, dim3(nblk(n, 256)), dim3(256), 0, s, in.chars, in.off, in.members, n, e->raw, e->keys, e->idx, in.skip, bad, words, nkeys);
+    }
     SL_HIP(hipGetLastError());
     int hbad[3];
     SL_HIP(hipMemcpyAsync(hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));
-    out->words = 1;
-    if (hbad[1] != init[1]) {
-        // some string has more than 32 bases: the whole call runs on 4-word codes
-        const int maxlen = -hbad[2];
-        if (maxlen > UMI_XL_MAX) return fail("sarlacc_amd: UMI longer than %d bases is not supported", UMI_XL_MAX);
-        // 33..128 bases: 4 words per string, tiles staged in LDS; beyond: as many words as the longest string needs
-        out->words = maxlen <= UMI_LONG_MAX ? UMI_LONG_WORDS : (maxlen + 31) / 32;
-        const int nkeys = (maxlen + UMI_KEY_BASES - 1) / UMI_KEY_BASES;
-        SL_TRY(alloc_umi(p + ".rawL", n, &raw, out->words));
-        SL_TRY(alloc_umi(p + ".srtL", n, &out->U, out->words));
-        unsigned long long* keys;
-        SL_TRY(scratch(p + ".keysL", static_cast<size_t>(n) * nkeys, &keys));
-        SL_HIP(hipMemcpyAsync(bad, init, sizeof init, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_umi_encode_long, dim3(nblk(n, 256)), dim3(256), 0, s, d_chars, d_off, d_members, n, raw, keys, idx, d_skip, bad, out->words, nkeys);
-        SL_HIP(hipGetLastError());
-        SL_HIP(hipMemcpyAsync(hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipStreamSynchronize(s));
-        if (hbad[0] != init[0])
-            return fail("sarlacc_amd: UMI contains a character outside ACGTN (the reference silently drops such strings)");
+    e->bad_char = hbad[0];
+    e->too_long = hbad[1];
+    e->maxlen = -hbad[2];
+    return 0;
+}
+
+// Order the encoded set like the trie (most significant: the pre-group) and gather it in that order.
+int rank_umis(const std::string& p, const Encoded& e, int words, const int* d_gid, int ngroups, int n, SortedUmis* out, hipStream_t s) {
+    unsigned long long *klo = e.klo, *k2;   // one word: the low key of encode_at; beyond: a work buffer for one key plane at a time
+    int *idx = e.idx, *idx2;
+    SL_TRY(alloc_umi(p + (words > 1 ? ".srtL" : ".srt"), n, &out->U, words));
+    if (words > 1) SL_TRY(scratch(p + ".klo", n, &klo));
+    SL_TRY(scratch(p + ".k2", n, &k2));
+    SL_TRY(scratch(p + ".idx2", n, &idx2));
+    if (words > 1) {
         // stable sorts, least-significant key first (only the keys some string reaches)
+        const int nkeys = (e.maxlen + UMI_KEY_BASES - 1) / UMI_KEY_BASES;
         int *from = idx, *to = idx2;
         for (int k = nkeys - 1; k >= 0; --k) {
-            hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n, 256)), dim3(256), 0, s, keys + static_cast<size_t>(k) * n, from, klo, n);
+            hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n, 256)), dim3(256), 0, s, e.keys + static_cast<size_t>(k) * n, from, klo, n);
             SL_TRY(radix_sort_pairs(p + ".sorttmp", klo, k2, from, to, n, 63, s));
             std::swap(from, to);
         }
         if (from != idx) SL_HIP(hipMemcpyAsync(idx, from, sizeof(int) * static_cast<size_t>(n), hipMemcpyDeviceToDevice, s));
     } else {
-        if (hbad[0] != init[0])
-            return fail("sarlacc_amd: UMI contains a character outside ACGTN (the reference silently drops such strings)");
         // least-significant key first; both sorts are stable, ties keep the input order
         SL_TRY(radix_sort_pairs(p + ".sorttmp", klo, k2, idx, idx2, n, 64, s));
-        hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n, 256)), dim3(256), 0, s, khi, idx2, klo, n);
+        hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n, 256)), dim3(256), 0, s, e.khi, idx2, klo, n);
         SL_TRY(radix_sort_pairs(p + ".sorttmp", klo, k2, idx2, idx, n, 64, s));
     }
     out->gid = nullptr;
@@ -965,60 +954,24 @@ int encode_and_rank(const std::string& p, const uint8_t* d_chars, const int64_t*
         hipLaunchKernelGGL(k_gather_gid, dim3(nblk(n, 256)), dim3(256), 0, s, d_gid, idx, static_cast<unsigned long long*>(nullptr), gsorted, n);
         out->gid = gsorted;
     }
-    hipLaunchKernelGGL(k_gather_umi, dim3(nblk(n, 256)), dim3(256), 0, s, raw, idx, out->U, n, out->words);
+    hipLaunchKernelGGL(k_gather_umi, dim3(nblk(n, 256)), dim3(256), 0, s, e.raw, idx, out->U, n, words);
     SL_HIP(hipGetLastError());
     out->perm = idx;
     out->n = n;
+    out->words = words;
     return 0;
 }
 
-// ---- split-key search: host side ----
-constexpr int SK_MIN_N = 32768;          // below this (or with pre-groups averaging under half of it) the all-tile-pairs search is quick enough
+// ---- split-key search ----
 
-constexpr int SK_MIN_LEN = 8;            // shorter strings are "special" (keys under 4 bases select too much)
-constexpr int SK_MAX_KEY = 8;            // bases per key at most (9 bases of the forward string travel with every element)
-
-struct SkClass { int len_lo, len_hi, h, s; };
-
-struct SkPlan {
-    std::vector<SkClass> classes;   // row lengths present in the set, with the key lengths they scan with
-    int k1 = 0, k2 = 0;             // edits allowed in the prefix / suffix key
-    long long nspecial = 0;
-};
-
-struct SkScan {          // one scan order with row groups for one key length, ready to launch
-    SkOrder O{};
-    int key = 0;
-    int* rg_start = nullptr;
-    int nrg = 0;
-    int2* ranges = nullptr;
-    int *nranges = nullptr, *ctotal = nullptr;
-    long long* item_off = nullptr;
-    long long nitems = 0;
-};
-
-// The lengths present decide the scans: one class per length 8..15 and one for 16 and longer.
-static int sk_plan(const std::string& p, const SortedUmis& S, int limit, SkPlan* plan, hipStream_t s) {
+// hist: strings per length 0..32, [33] strings with an N
+int length_hist(const std::string& p, const SortedUmis& S, unsigned int hist[34], hipStream_t s) {
     unsigned int* d_hist;
     SL_TRY(scratch(p + ".sk.hist", 34, &d_hist));
     SL_HIP(hipMemsetAsync(d_hist, 0, 34 * sizeof(unsigned int), s));
     hipLaunchKernelGGL(k_sk_lenhist, dim3(std::min(nblk(S.n, 256), 1024u)), dim3(256), 0, s, S.U, S.n, d_hist);
-    unsigned int hist[34];
-    SL_HIP(hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipMemcpyAsync(hist, d_hist, 34 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));
-    plan->classes.clear();
-    for (int L = SK_MIN_LEN; L <= 2 * SK_MAX_KEY; ++L) {
-        long long rows = hist[L];
-        if (L == 2 * SK_MAX_KEY) for (int M = L + 1; M <= 32; ++M) rows += hist[M];
-        if (!rows) continue;
-        const int h = std::min(L / 2, SK_MAX_KEY);
-        plan->classes.push_back(SkClass{L, L == 2 * SK_MAX_KEY ? 32 : L, h, std::min(L - h, SK_MAX_KEY)});
-    }
-    plan->k1 = limit >= 2 ? 1 : 0;   // limit 1: both keys have to match exactly; 2: the suffix key; 3: one edit in either
-    plan->k2 = limit - 1 - plan->k1;
-    long long shorter = 0;
-    for (int L = 0; L < SK_MIN_LEN; ++L) shorter += hist[L];
-    plan->nspecial = shorter + hist[33];   // an upper bound (short strings with an N count twice)
     return 0;
 }
 
@@ -1053,7 +1006,7 @@ static int sk_prepare(const std::string& p, const SkOrder& O, int h, int k1, boo
 }
 
 // Both scan orders with their row groups and candidate ranges.
-static int sk_build(const std::string& p, const SortedUmis& S, const SkPlan& plan, std::vector<SkScan>* fwd, std::vector<SkScan>* rev, hipStream_t s) {
+int split_orders(const std::string& p, const SortedUmis& S, const SkPlan& plan, SplitOrders* out, hipStream_t s) {
     const int n = S.n;
     SkOrder X{}, Y{};
     X.n = Y.n = n;
@@ -1078,7 +1031,7 @@ static int sk_build(const std::string& p, const SortedUmis& S, const SkPlan& pla
         unsigned long long *d_gk, *d_gk2;
         SL_TRY(scratch(p + ".sk.gk", static_cast<size_t>(n), &d_gk));
         SL_TRY(scratch(p + ".sk.gk2", static_cast<size_t>(n), &d_gk2));
-        hipLaunchKernelGGL(k_cl_gidkey, dim3(nblk(n, 256)), dim3(256), 0, s, S.gid, d_val2, static_cast<long long>(n), d_gk);
+        gid_keys(S.gid, d_val2, n, d_gk, s);
         SL_TRY(radix_sort_pairs(p + ".sorttmp", d_gk, d_gk2, d_val2, d_val, static_cast<size_t>(n), ceil_log2(static_cast<unsigned long long>(S.ngroups) + 1), s));
         order = d_val;
         // keys in the final order
@@ -1091,235 +1044,93 @@ static int sk_build(const std::string& p, const SortedUmis& S, const SkPlan& pla
     // row groups and ranges once per key length in use; the prefix scan starts at the row group itself (columns
     // ranked below the row report the pair themselves)
     const bool clip = true;
-    fwd->clear(); rev->clear();
+    out->fwd.clear(); out->rev.clear();
     for (const SkClass& c : plan.classes) {
         bool have = false;
-        for (const SkScan& q : *fwd) have = have || q.key == c.h;
-        if (!have) { fwd->emplace_back(); SL_TRY(sk_prepare(p + ".skx" + std::to_string(c.h), X, c.h, plan.k1, clip, &fwd->back(), s)); }
+        for (const SkScan& q : out->fwd) have = have || q.key == c.h;
+        if (!have) { out->fwd.emplace_back(); SL_TRY(sk_prepare(p + ".skx" + std::to_string(c.h), X, c.h, plan.k1, clip, &out->fwd.back(), s)); }
         have = false;
-        for (const SkScan& q : *rev) have = have || q.key == c.s;
-        if (!have) { rev->emplace_back(); SL_TRY(sk_prepare(p + ".sky" + std::to_string(c.s), Y, c.s, plan.k2, false, &rev->back(), s)); }
+        for (const SkScan& q : out->rev) have = have || q.key == c.s;
+        if (!have) { out->rev.emplace_back(); SL_TRY(sk_prepare(p + ".sky" + std::to_string(c.s), Y, c.s, plan.k2, false, &out->rev.back(), s)); }
     }
     return 0;
 }
 
-static long long sk_launch(const std::vector<SkScan>& F, const std::vector<SkScan>& R, const SkPlan& plan, int limit, uint32_t row_lo, uint32_t row_hi,
-                           unsigned stride, unsigned long long* edges, unsigned long long* count, unsigned long long cap, hipStream_t s) {
-    long long items = 0;
-    ctx().counts["umi_scan_two_columns"] = 0;   // launches of k_sk_scan_pk
-    for (const SkClass& c : plan.classes)
+// The scans of the plan's classes, prefix then suffix; *items: work items of the launches, *two_columns: launches of k_sk_scan_pk.
+void split_scans(const SplitOrders& O, const SearchPlan& P, unsigned stride, const PairBuffer& b, long long* items, int* two_columns, hipStream_t s) {
+    *items = 0;
+    *two_columns = 0;
+    for (const SkClass& c : P.sk.classes)
         for (int pass = 0; pass < 2; ++pass) {
             const SkScan* Q = nullptr;
-            for (const SkScan& q : pass ? R : F) if (q.key == (pass ? c.s : c.h)) Q = &q;
+            for (const SkScan& q : pass ? O.rev : O.fwd) if (q.key == (pass ? c.s : c.h)) Q = &q;
             if (!Q) continue;
             const long long blocks = (Q->nitems + stride - 1) / stride;
             if (blocks <= 0) continue;
-            items += Q->nitems;
-            SkScanArgs a{Q->O.el, Q->rg_start, Q->nrg, Q->ranges, Q->nranges, Q->ctotal, Q->item_off, stride, limit, c.h, plan.k1,
-                         c.len_lo, c.len_hi, row_lo, row_hi, edges, count, cap};
-            // two candidate columns per lane for the rows no string of 16 and more bases can be a neighbour of (the lengths of
-            // neighbours differ by `limit` at most; such columns are simply not valid there)
-            const bool two = c.len_hi + limit < 16 && !option(OPT_UMI_SCAN_SINGLE);
-            if (two) ctx().counts["umi_scan_two_columns"] += 1;
-            if (two) {
-                if (pass) hipLaunchKernelGGL(k_sk_scan_pk<true>, dim3(static_cast<unsigned>(blocks)), dim3(SK_COLS / 2), 0, s, a);
-                else hipLaunchKernelGGL(k_sk_scan_pk<false>, dim3(static_cast<unsigned>(blocks)), dim3(SK_COLS / 2), 0, s, a);
-            } else if (pass) hipLaunchKernelGGL(k_sk_scan<true>, dim3(static_cast<unsigned>(blocks)), dim3(SK_COLS), 0, s, a);
-            else hipLaunchKernelGGL(k_sk_scan<false>, dim3(static_cast<unsigned>(blocks)), dim3(SK_COLS), 0, s, a);
+            *items += Q->nitems;
+            *two_columns += c.two ? 1 : 0;
+            const SkScanArgs a{Q->O.el, Q->rg_start, Q->nrg, Q->ranges, Q->nranges, Q->ctotal, Q->item_off, stride, P.limit, c.h, P.sk.k1,
+                               c.len_lo, c.len_hi, P.row_lo, P.row_hi, b.edges, b.count, b.cap};
+            pick([&](auto two_, auto suffix_) {
+                constexpr bool SUFFIX = decltype(suffix_)::value != 0;
+                if constexpr (decltype(two_)::value != 0) hipLaunchKernelGGL(k_sk_scan_pk<SUFFIX>, dim3(static_cast<unsigned>(blocks)), dim3(SK_COLS / 2), 0, s, a);
+                else hipLaunchKernelGGL(k_sk_scan<SUFFIX>, dim3(static_cast<unsigned>(blocks)), dim3(SK_COLS), 0, s, a);
+                return 0;
+            }, Ints<0, 1>{}, c.two, Ints<0, 1>{}, pass);
         }
-    return items;
 }
 
-template <int K>
-static void launch_pairs(const PairArgs& a, int tile_hi, unsigned ntiles_listed, hipStream_t s) {
-    const unsigned nt = nblk(a.n, TILE);
-    if (tile_hi <= a.tile_lo) return;
-    if (a.tile_list) {
-        if (ntiles_listed) hipLaunchKernelGGL(k_umi_pairs<K>, dim3(ntiles_listed), dim3(TILE), 0, s, a);
-        return;
-    }
-    hipLaunchKernelGGL(k_umi_pairs<K>, dim3(static_cast<unsigned>(tile_hi - a.tile_lo), nt), dim3(TILE), 0, s, a);
-}
+// ---- tile search ----
 
-template <int L>
-static void launch_tile_pairs(const TileInfo* info, int nt, int tile_lo, int tile_hi, int special_only, uint32_t* list, unsigned int* count, hipStream_t s) {
-    hipLaunchKernelGGL(k_tile_pairs<L>, dim3(nblk(nt, 256), static_cast<unsigned>(tile_hi - tile_lo)), dim3(256), 0, s, info, nt,
-                       tile_lo, tile_hi, special_only, list, count);
-}
-
-int pair_edges(const std::string& p, const SortedUmis& S, int limit, int tile_lo, int tile_hi,
-               unsigned long long** d_edges_out, unsigned long long* m_out, hipStream_t s) {
-    Context& c = ctx();
-    const int n = S.n;
-    const int nt = static_cast<int>(nblk(n, TILE));
-    if (tile_hi < 0) { tile_lo = 0; tile_hi = nt; }
-    tile_lo = std::max(0, std::min(tile_lo, nt));
-    tile_hi = std::max(tile_lo, std::min(tile_hi, nt));
-    const int lim2 = 2 * limit;
-    unsigned long long* d_count;
-    SL_TRY(scratch(p + ".ecount", 1, &d_count));
-    unsigned long long cap = std::max<unsigned long long>(1u << 20, 32ull * n);
-    unsigned long long m = 0;
-    unsigned long long* d_edges = nullptr;
-    if (n > static_cast<long long>(65535) * TILE) return fail("sarlacc_amd: more than %d UMIs in one call", 65535 * TILE);
-    {   // make sure a buffer exists even when nothing is launched
-        void* pe;
-        SL_TRY(c.buffer((p + ".edges").c_str(), cap * sizeof(unsigned long long), &pe));
-        d_edges = static_cast<unsigned long long*>(pe);
-    }
-    // Thresholds 1 to 3 on a large set: candidates from the split keys (see k_sk_scan); the tile kernel then only
-    // looks at the pairs with a "special" member, if there are any.
-    SkPlan plan;
-    std::vector<SkScan> fwd, rev;
-    const int min_n = option(OPT_UMI_SPLIT_MIN) > 0 ? option(OPT_UMI_SPLIT_MIN) : SK_MIN_N;
-    // (the largest pre-group decides, not the average: a set with one large pre-group among thousands of small ones has the
-    // quadratic tile search to lose; the reads that sit alone in their pre-group are encoded as empty strings, take no part
-    // in any comparison and are not "special")
-    bool split = S.words == 1 && limit >= 1 && limit <= 3 && n >= min_n && !option(OPT_UMI_TILE_SEARCH) && S.max_group >= min_n / 2;
-    if (split) {
-        SL_TRY(sk_plan(p, S, limit, &plan, s));
-        plan.nspecial = std::max<long long>(0, plan.nspecial - S.nskip);
-        split = !plan.classes.empty() && 4 * plan.nspecial <= n - S.nskip;
-    }
-    if (split) SL_TRY(sk_build(p, S, plan, &fwd, &rev, s));
-    const int special_lreq = split ? SK_MIN_LEN : -1;
-    long long split_items = 0;
-    const bool tiles = !split || plan.nspecial > 0;
-    c.counts["umi_split_search"] = split ? 1 : 0;
-    c.counts["umi_split_classes"] = split ? static_cast<double>(plan.classes.size()) : 0;
-    c.counts["umi_split_special"] = split ? static_cast<double>(plan.nspecial) : 0;
-    // tile pairs that can hold neighbours (see k_tile_pairs); worth it from a few dozen tiles on
-    const uint32_t* d_list = nullptr;
-    const TileInfo* d_subinfo = nullptr;
-    unsigned int nlisted = 0;
-    const long long ntp = static_cast<long long>(tile_hi - tile_lo) * nt;
-    if (tiles && S.words == 1 && limit >= 0 && limit <= 5 && nt >= 16 && ntp <= (1ll << 31)) {
-        TileInfo* d_info; uint32_t* d_l; unsigned int* d_lc;
-        SL_TRY(scratch(p + ".tinfo", static_cast<size_t>(nt), &d_info));
-        // the list is bounded by the upper triangle of the launch
-        const size_t max_list = static_cast<size_t>(tile_hi - tile_lo) * static_cast<size_t>(nt);
-        SL_TRY(scratch(p + ".tlist", max_list, &d_l));
-        SL_TRY(scratch(p + ".tcount", 1, &d_lc));
-        SL_HIP(hipMemsetAsync(d_lc, 0, sizeof(unsigned int), s));
-        hipLaunchKernelGGL(k_tile_info<TILE>, dim3(static_cast<unsigned>(nt)), dim3(TILE), 0, s, S.U, S.gid, n, std::max(special_lreq, 0), d_info);
-        // prefixes of the 64-element blocks for the sub-tile filter inside the pair kernel
-        TileInfo* d_sub;
-        const unsigned nsub = nblk(n, 64);
-        SL_TRY(scratch(p + ".tsub", static_cast<size_t>(nsub), &d_sub));
-        hipLaunchKernelGGL(k_tile_info<64>, dim3(nsub), dim3(64), 0, s, S.U, S.gid, n, 0, d_sub);
-        d_subinfo = d_sub;
-        const int so = split ? 1 : 0;
-        switch (limit) {
-            case 0: launch_tile_pairs<0>(d_info, nt, tile_lo, tile_hi, so, d_l, d_lc, s); break;
-            case 1: launch_tile_pairs<1>(d_info, nt, tile_lo, tile_hi, so, d_l, d_lc, s); break;
-            case 2: launch_tile_pairs<2>(d_info, nt, tile_lo, tile_hi, so, d_l, d_lc, s); break;
-            case 3: launch_tile_pairs<3>(d_info, nt, tile_lo, tile_hi, so, d_l, d_lc, s); break;
-            case 4: launch_tile_pairs<4>(d_info, nt, tile_lo, tile_hi, so, d_l, d_lc, s); break;
-            default: launch_tile_pairs<5>(d_info, nt, tile_lo, tile_hi, so, d_l, d_lc, s); break;
-        }
-        SL_HIP(hipGetLastError());
-        SL_HIP(hipMemcpyAsync(&nlisted, d_lc, sizeof nlisted, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipStreamSynchronize(s));
-        d_list = d_l;
-    }
-    // what the tile filter kept: upper-triangle tile pairs of this launch, and how many of them are searched (0: no list)
-    const long long below_diagonal = static_cast<long long>(tile_lo + tile_hi - 1) * (tile_hi - tile_lo) / 2;   // sum of the row tiles' indices
-    c.counts["umi_tile_pairs_total"] = static_cast<double>(ntp - below_diagonal);
-    c.counts["umi_tile_pairs_listed"] = d_list ? static_cast<double>(nlisted) : 0;
-    const uint32_t row_lo = static_cast<uint32_t>(std::min<long long>(static_cast<long long>(tile_lo) * TILE, n));
-    const uint32_t row_hi = static_cast<uint32_t>(std::min<long long>(static_cast<long long>(tile_hi) * TILE, n));
-    // every search kernel of one pass over the set; `stride` > 1: a sample (every stride-th tile pair / work item)
-    auto launch_all = [&](unsigned stride, unsigned long long capacity) {
-        if (split && row_hi > row_lo) split_items = sk_launch(fwd, rev, plan, limit, row_lo, row_hi, stride, d_edges, d_count, capacity, s);
-        if (!tiles) return;
-        PairArgs a{S.U, S.gid, n, lim2, d_edges, d_count, capacity, tile_lo, d_list, d_subinfo, stride, special_lreq};
-        const unsigned listed = d_list ? nlisted / stride : 0u;
-        if (stride > 1 && !d_list) return;   // a sample needs the list
-        const int K = std::min(limit, UMI_MAXLEN);
-        if (S.words > 1) {
-            if (tile_hi > tile_lo) {
-                const dim3 grid(static_cast<unsigned>(tile_hi - tile_lo), static_cast<unsigned>(nt));
-#define UMI_LONG_LAUNCH(KK)                                                                                  \
-    {                                                                                                        \
-        if (S.words > UMI_LONG_WORDS) hipLaunchKernelGGL((k_umi_pairs_long<KK, true>), grid, dim3(TILE), 0, s, a);   \
-        else hipLaunchKernelGGL((k_umi_pairs_long<KK, false>), grid, dim3(TILE), 0, s, a);                   \
-    }
-                if (limit <= 0) UMI_LONG_LAUNCH(0)
-                else if (limit == 1) UMI_LONG_LAUNCH(1)
-                else if (limit == 2) UMI_LONG_LAUNCH(2)
-                else if (limit == 3) UMI_LONG_LAUNCH(3)
-                else if (limit <= 5) UMI_LONG_LAUNCH(5)
-                else if (limit <= 8) UMI_LONG_LAUNCH(8)
-                else if (limit <= 16) UMI_LONG_LAUNCH(16)
-                else UMI_LONG_LAUNCH(-1)
-#undef UMI_LONG_LAUNCH
-            }
-        }
-        else if (K <= 0) launch_pairs<0>(a, tile_hi, listed, s);
-        else if (K == 1) launch_pairs<1>(a, tile_hi, listed, s);
-        else if (K == 2) launch_pairs<2>(a, tile_hi, listed, s);
-        else if (K == 3) launch_pairs<3>(a, tile_hi, listed, s);
-        else if (K == 4) launch_pairs<4>(a, tile_hi, listed, s);
-        else if (K == 5) launch_pairs<5>(a, tile_hi, listed, s);
-        else if (K <= 8) launch_pairs<8>(a, tile_hi, listed, s);
-        else if (K <= 16) launch_pairs<16>(a, tile_hi, listed, s);
-        else launch_pairs<UMI_MAXLEN>(a, tile_hi, listed, s);
-    };
-    // Capacity of the pair buffer: 32 per element covers thresholds 1 and 2; dense neighbourhoods (threshold 3 on 12-base
-    // UMIs: hundreds of neighbours each) would overflow it and cost a second full search, so the density is first
-    // estimated from a sample: every 32nd listed tile pair (k_tile_pairs appends them in no particular order) and
-    // every 32nd work item of the split-key scans.
-    const bool sample_tiles = d_list && nlisted >= 2048;
-    long long all_items = 0;
-    for (const SkScan& q : fwd) all_items += q.nitems;
-    for (const SkScan& q : rev) all_items += q.nitems;
-    const bool sample_items = split && all_items >= 2048;
-    if (limit >= 0 && (sample_tiles || sample_items) && (!tiles || d_list)) {
-        const unsigned stride = 32;
-        SL_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
-        launch_all(stride, cap);
-        SL_HIP(hipGetLastError());
-        unsigned long long ms = 0;
-        SL_HIP(hipMemcpyAsync(&ms, d_count, sizeof ms, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipStreamSynchronize(s));
-        const double est = static_cast<double>(ms) * stride;
-        cap = std::max<unsigned long long>(cap, static_cast<unsigned long long>(est * 1.25) + (1u << 20));
-        ctx().counts["umi_pairs_estimated"] = est;
-    }
-    for (int attempt = 0; attempt < 2 && limit >= 0; ++attempt) {
-        void* pe;
-        SL_TRY(c.buffer((p + ".edges").c_str(), cap * sizeof(unsigned long long), &pe));
-        d_edges = static_cast<unsigned long long*>(pe);
-        SL_HIP(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
-        SL_HIP(hipEventRecord(c.ev_start, s));
-        c.stage_reset("umi_pairs");
-        SL_TRY(c.stage_begin("umi_pairs", s));
-        launch_all(1u, cap);
-        SL_HIP(hipGetLastError());
-        SL_HIP(hipEventRecord(c.ev_stop, s));
-        SL_TRY(c.stage_end("umi_pairs", s));
-        c.timed = true;
-        SL_HIP(hipMemcpyAsync(&m, d_count, sizeof m, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipStreamSynchronize(s));
-        ctx().counts["umi_pair_attempts"] = attempt + 1;
-        if (m <= cap) break;
-        cap = m;  // the kernels kept counting: second attempt has the exact size
-    }
-    c.counts["umi_split_items"] = static_cast<double>(split_items);
-    *d_edges_out = d_edges;
-    *m_out = m;
+// Tile pairs that can hold neighbours (see k_tile_pairs), and the prefixes of the 64-element blocks for the sub-tile
+// filter inside the pair kernel.
+int tile_filter(const std::string& p, const SortedUmis& S, const SearchPlan& P, TileList* out, hipStream_t s) {
+    const int n = S.n, nt = P.nt;
+    TileInfo* d_info; uint32_t* d_l; unsigned int* d_lc;
+    SL_TRY(scratch(p + ".tinfo", static_cast<size_t>(nt), &d_info));
+    // the list is bounded by the upper triangle of the launch
+    const size_t max_list = static_cast<size_t>(P.tile_hi - P.tile_lo) * static_cast<size_t>(nt);
+    SL_TRY(scratch(p + ".tlist", max_list, &d_l));
+    SL_TRY(scratch(p + ".tcount", 1, &d_lc));
+    SL_HIP(hipMemsetAsync(d_lc, 0, sizeof(unsigned int), s));
+    hipLaunchKernelGGL(k_tile_info<TILE>, dim3(static_cast<unsigned>(nt)), dim3(TILE), 0, s, S.U, S.gid, n, std::max(P.special_lreq, 0), d_info);
+    TileInfo* d_sub;
+    const unsigned nsub = nblk(n, 64);
+    SL_TRY(scratch(p + ".tsub", static_cast<size_t>(nsub), &d_sub));
+    hipLaunchKernelGGL(k_tile_info<64>, dim3(nsub), dim3(64), 0, s, S.U, S.gid, n, 0, d_sub);
+    const int rc = pick([&](auto l_) {
+        hipLaunchKernelGGL(k_tile_pairs<decltype(l_)::value>, dim3(nblk(nt, 256), static_cast<unsigned>(P.tile_hi - P.tile_lo)), dim3(256), 0, s,
+                           d_info, nt, P.tile_lo, P.tile_hi, P.split ? 1 : 0, d_l, d_lc);
+        return 0;
+    }, Ints<0, 1, 2, 3, 4, 5>{}, P.L);
+    if (rc == NO_KERNEL) return fail("sarlacc_amd: internal error: no tile filter for prefix distance %d", P.L);
+    SL_HIP(hipGetLastError());
+    SL_HIP(hipMemcpyAsync(&out->n, d_lc, sizeof out->n, hipMemcpyDeviceToHost, s));
+    SL_HIP(hipStreamSynchronize(s));
+    out->list = d_l;
+    out->sub = d_sub;
     return 0;
 }
 
-// All neighbour pairs within `limit`, as sorted directed keys (self links included).
-int neighbour_keys(const std::string& p, const SortedUmis& S, int limit, const uint8_t* d_single, DirectedKeys* out, hipStream_t s) {
-    if (limit < 0) limit = -1;  // nothing can match a negative limit
-    unsigned long long* d_edges;
-    unsigned long long m;
-    const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    SL_TRY(pair_edges(p, S, limit, 0, -1, &d_edges, &m, s));
-    ctx().counts["umi_pair_search_s"] = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
-    return keys_from_edges(p, S, limit, d_single, d_edges, m, out, s);
+// The plan's tile-pair kernel: over the listed tile pairs (every stride-th of them: a sample), or over every pair of a
+// row tile of the plan with a tile of the set.
+int pair_search(const SortedUmis& S, const SearchPlan& P, const TileList& T, unsigned stride, const PairBuffer& b, hipStream_t s) {
+    if (P.tile_hi <= P.tile_lo) return 0;
+    const PairArgs a{S.U, S.gid, S.n, 2 * P.limit, b.edges, b.count, b.cap, P.tile_lo, T.list, T.sub, stride, P.special_lreq};
+    const dim3 grid = T.list ? dim3(T.n / stride) : dim3(static_cast<unsigned>(P.tile_hi - P.tile_lo), static_cast<unsigned>(P.nt));
+    if (grid.x == 0) return 0;
+    int rc;
+    if (P.words > 1)
+        rc = pick([&](auto k_, auto xl_) {
+            hipLaunchKernelGGL((k_umi_pairs_long<decltype(k_)::value, decltype(xl_)::value != 0>), grid, dim3(TILE), 0, s, a);
+            return 0;
+        }, Ints<0, 1, 2, 3, 5, 8, 16, PAIRS_K_FULL>{}, P.K, Ints<0, 1>{}, P.xl);
+    else
+        rc = pick([&](auto k_) {
+            hipLaunchKernelGGL(k_umi_pairs<decltype(k_)::value>, grid, dim3(TILE), 0, s, a);
+            return 0;
+        }, Ints<0, 1, 2, 3, 4, 5, 8, 16, UMI_MAXLEN>{}, P.K);
+    return rc != NO_KERNEL ? rc : fail("sarlacc_amd: internal error: no tile-pair kernel for band %d at %d words", P.K, P.words);
 }
 
 }  // namespace sarlacc

@@ -263,7 +263,13 @@ def test_split_key_search_small_sets(oracle, lo, hi, n_rate, short, split):
                     calls.set_option("umi_scan_single", single)
                     got = calls.fast_levdist_test(umis, t)
                     assert _lib.stage_count("umi_split_search") == split
+                    # the plan's tile-pair kernel: k_umi_pairs<t>, and none (-2) where the split-key search leaves it no
+                    # "special" string (one with an N or of under 8 bases)
+                    special = any("N" in u or len(u) < 8 for u in umis)
+                    assert _lib.stage_count("umi_pairs_k") == (-2 if split and not special else t)
+                    assert _lib.stage_count("umi_pairs_words") == 1
                     if split:
+                        assert (_lib.stage_count("umi_split_special") > 0) == special
                         # (the rows of up to 15 - t bases scan two columns per lane)
                         assert (_lib.stage_count("umi_scan_two_columns") > 0) == (any(8 <= len(u) <= 15 - t for u in umis) and not single)
                     same_lists(got, want)
@@ -452,6 +458,15 @@ def test_lev_masked_dense_long(oracle, lo, hi, alphabet):
     from sarlacc_amd import calls
     rng = np.random.default_rng(2000 + lo)
     seqs = seqsim(rng, 20, lo, hi, alphabet) + umisim(rng, 20, hi, 0.1, alphabet)
+    assert calls.compute_lev_masked(seqs).tolist() == oracle.compute_lev_masked(seqs).tolist()
+
+
+@pytest.mark.parametrize("lengths", [(8, 8, 8, 8, 8), (8, 8, 33, 8, 8), (8, 129, 8)])
+def test_lev_masked_dense_word_classes(oracle, lengths):
+    # one string decides the words of the whole call: 1, 4 and 5 through the encode step the neighbour search shares
+    from sarlacc_amd import calls
+    rng = np.random.default_rng(sum(lengths))
+    seqs = ["".join(rng.choice(list("ACGTN"), n)) for n in lengths]
     assert calls.compute_lev_masked(seqs).tolist() == oracle.compute_lev_masked(seqs).tolist()
 
 

@@ -6,7 +6,7 @@ lists and the groups from the oracle's trie walk.  The inputs (tests/umi_cases.p
 hold what they claim) put pairs exactly at and just past each threshold, make the tile filter discard tile pairs that lie
 next to tiles with true neighbours, and push the pair count past the first buffer.
 
-Thresholds and the instantiation each one reaches:
+Thresholds and the instantiation each one reaches (asserted through the counters umi_pairs_k and umi_pairs_words):
   k_umi_pairs<K>, strings of up to 32 bases (8, 12, 31, 32):   0 1 2 3 4 5 -> K = limit;  6 7 8 -> 8;  9 15 16 -> 16;
                                                                 17 31 32 33 40 -> 32 (33 and 40: above every string length)
   k_umi_pairs_long<K, false>, 33 to 128 bases (33, 64, 65, 128): 4 -> 5;  6 7 8 -> 8;  10 15 16 -> 16;  17 19 40 -> full DP
@@ -53,6 +53,11 @@ def at_limit_case(oracle, length, limit):
     print("length %d limit %d: n %d, pairs at the limit %d, just past %d, odd %d" % (length, limit, len(seqs), census["at"], census["past"], census["odd"]))
     got = calls.fast_levdist_test(seqs, limit, True)
     assert _lib.stage_count("umi_split_search") == 0 and _lib.stage_count("umi_tile_pairs_listed") == 0
+    # the instantiation the threshold reached, and the words per string it ran on
+    longest = max(len(s) for s in seqs)
+    assert _lib.stage_count("umi_pairs_k") == (K.one_word_band(limit) if length <= 32 else K.long_band(limit))
+    assert _lib.stage_count("umi_pairs_words") == (1 if length <= 32 else 4 if length <= 128 else
+                                                   min((longest + 31) // 32, (K.path_max_length(length) + 31) // 32))
     same_lists(got, K.neighbours_from_d2(seqs, d2, limit))       # content (and order) from the dense distances
     same_lists(got, oracle.fast_levdist_test(seqs, limit))       # order from the trie walk
     same_groups_or_same_error(oracle, seqs, limit, [list(range(1, len(seqs) + 1))])
