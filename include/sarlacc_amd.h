@@ -428,6 +428,45 @@ int sarlacc_dev_bam_tags_splice(const uint8_t* d_aux, const int64_t* d_aux_off, 
                                 const uint8_t* d_col_chars, const int64_t* d_col_off, const int32_t* d_col_ints,
                                 const uint8_t* d_mask, const int64_t* d_out_off, uint8_t* d_out, void* stream);
 
+/* Pre-groups of a read batch from alignment records (generics.readGroups; csrc/read_groups.hip).  Four calls on data
+ * already in device memory, each usable alone; names are flat string sets, bytes plus n + 1 int64 offsets, as a batch
+ * holds them.  Limits: n_reads, n_records and n are below 2^31.  Every result is exact and the same from run to run:
+ * no value depends on the order in which atomics arrive.  All calls return when the device has finished.
+ * sarlacc_dev_names_match joins records to reads by name.  A read's key is its name up to, and not including, its first
+ * space or tab (the cut sarlacc_dev_bam_format_size makes); a record's name is compared whole.  d_read_of_record[r]
+ * (n_records entries) is the 0-based read whose key equals record r's name byte for byte, -1 where there is none;
+ * *n_unmatched (may be NULL) counts the latter.  A hash only finds candidates: equality is always decided by the
+ * bytes.  Option names_hash_bits (sarlacc_set_option; 0 = all 64 bits, k = 1 .. 64 keeps k bits of the hash for slot
+ * and tag) exists so that tests make every probe walk chains of unequal keys.  No byte outside the two name buffers
+ * (d_read_off[n_reads] and d_rec_off[n_records] bytes) is read.  Errors:
+ *   read names J and K are the same up to their first space or tab      (1-based; K the lowest read that is not the
+ *                                                                        first of its key, J the first read of that key)
+ *   read name K / record name K: its offsets do not ascend inside the name buffer
+ * n_reads == 0 marks every record unmatched.
+ * sarlacc_dev_records_pick chooses one record per read: among the records r with d_read_of_record[r] == i the one of
+ * greatest d_width[r], the lowest r among equal widths (d_record_of_read[i], -1: none), and counts them
+ * (d_records_per_read[i]); n_reads entries each.  "record K: a read index outside the batch or a negative width".
+ * sarlacc_dev_locus_labels labels the reads by overlap of their chosen ranges.  d_ref / d_strand ('-' or anything else)
+ * / d_start / d_width are the n_records rows d_record_of_read points into.  The reads with a record are sorted by
+ * (reference, strand with '+' first unless ignore_strand, start, read index); a group starts where reference or strand
+ * change and where start > (greatest end since the group began) + maxgap, end = start + width - 1 in 64 bits, maxgap in
+ * 0 .. 2^31 - 1.  d_label[i] (n_reads entries) counts the groups in that order from 0, -1 for a read without a record;
+ * *n_groups (may be NULL) is their number.  "read K: its record lies outside the columns, or has a seqname code outside
+ * 0 .. 2^30 - 1 or a negative width".
+ * sarlacc_dev_labels_csr splits 1 .. n by label: the distinct non-negative labels ascending are the groups, negative
+ * labels are dropped.  d_group_off (room for n + 1 entries) gets *n_groups + 1 offsets into d_members (room for n
+ * entries; only the first *n_members are defined), the 1-based indices of every group ascending. */
+int sarlacc_dev_names_match(const uint8_t* d_read_names, const int64_t* d_read_off, int64_t n_reads,
+                            const uint8_t* d_rec_names, const int64_t* d_rec_off, int64_t n_records,
+                            int32_t* d_read_of_record, int64_t* n_unmatched, void* stream);
+int sarlacc_dev_records_pick(const int32_t* d_read_of_record, const int32_t* d_width, int64_t n_records, int64_t n_reads,
+                             int32_t* d_record_of_read, int32_t* d_records_per_read, void* stream);
+int sarlacc_dev_locus_labels(const int32_t* d_ref, const uint8_t* d_strand, const int32_t* d_start, const int32_t* d_width,
+                             int64_t n_records, const int32_t* d_record_of_read, int64_t n_reads, int64_t maxgap,
+                             int ignore_strand, int32_t* d_label, int64_t* n_groups, void* stream);
+int sarlacc_dev_labels_csr(const int32_t* d_label, int64_t n, int64_t* d_group_off, int32_t* d_members, int64_t* n_groups,
+                           int64_t* n_members, void* stream);
+
 /* SAM alignment records already in device memory -> ranges (sam2ranges, R/sam2ranges.R:8-95).  d_text holds
  * body lines of a SAM file (no header), LF or CRLF, blank lines skipped; first_line is the 1-based file line
  * number of its first line, used in error messages.  The caller reads the header: ref_names / ref_off (n_ref + 1
@@ -680,7 +719,9 @@ int sarlacc_set_msa_spec(int spec);
  *   hand-over folded into its max alone, 2 the staging prefetch held as raw load results until the next refill alone, 3 both,
  *   which is the default),
  *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel),
- *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes).
+ *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes),
+ *   "names_hash_bits" (sarlacc_dev_names_match: bits of the name hash kept for slot and tag, 1 .. 64; 0 = all 64.  A test
+ *   keeps 1, 2 or 8 so that every probe walks long chains of colliding, unequal keys; the results do not change).
  * The environment (SARLACC_<NAME>) is read once, when the first option is asked for; afterwards only this call changes a
  * value.  Nothing in the reference corresponds. */
 int sarlacc_set_option(const char* name, int value);

@@ -766,7 +766,8 @@ def profileReads(reads, reference, gapOpening=5, gapExtension=1, expand=False, a
     histograms (lengths, multiplicities) -- alignments without an insertion at a position count as length 0 -- or, with
     expand=True, the sorted lists of the two generics, value for value.  With `assignment` (per read the index of its
     reference in the list `reference`, -1 = skip; the `seqnames` of sam2ranges) the reads of each reference are
-    gathered on the device and one result per reference is returned."""
+    gathered on the device and one result per reference is returned.  readGroups(ranges, reads)["reference"] is that
+    vector, one entry per read in the reads' order."""
     from .resident import DeviceReads
     if assignment is not None:
         dev = reads if isinstance(reads, DeviceReads) else DeviceReads.upload(reads)
@@ -804,3 +805,30 @@ def sam2ranges(sam, minq=10, restricted=None, block_bytes=256 << 20):
     CG tag.  Departures from the reference: DESIGN.md §8, "Known deviations"."""
     from .sam import sam2ranges as _sam2ranges
     return _sam2ranges(sam, minq=minq, restricted=restricted, block_bytes=block_bytes)
+
+
+# ---------------------------------------------------------------------------
+# readGroups: the pre-groups of umiGroup(groups=) from a mapping (vignettes/correction.Rmd)
+
+def readGroups(ranges, reads, by="reference", maxgap=0, ignore_strand=True):
+    """The `pre.groups` of the reference's correction vignette ("each set of reads mapping to the same transcript would
+    then be defined as a single group", the name of the reference sequence taken from sam2ranges()), one value per
+    read: the rows of `ranges` (what sam2ranges returns) are joined to `reads` (a resident.DeviceReads or Reads with
+    names, a StrList or a list of names) on the device.  A read's key is its name up to, and not including, its first
+    space or tab (the cut to_bam and a mapper make); record names are compared whole.  Two reads with the same key are
+    refused ("read names J and K are the same up to their first space or tab", 1-based).  Among the rows that name a
+    read the one of greatest width is chosen, the lowest row among equal widths -- a proxy for the primary alignment,
+    sam2ranges keeps no FLAG.  by="reference": the group label is the seqinfo code of the chosen row.  by="locus": reads
+    whose chosen ranges lie on one reference (and strand, unless ignore_strand) and overlap or lie within `maxgap` bases
+    of each other (start2 <= end1 + maxgap; 0: they share a base, 1: adjacent ranges merge too, as GenomicRanges::reduce)
+    form a group, transitively; labels ascend by (reference, '+' before '-', start, read index).
+    Returns a dict of numpy arrays with one entry per read, in the reads' order: "record" (0-based row of `ranges`, -1
+    none), "n.records" (rows that name the read), "reference" (seqinfo code of the chosen row, -1 none: what
+    profileReads(assignment=) takes), "group" (the label, -1 none), and "groups", the CSR pair (off int64[G + 1], members
+    int32, 1-based, ascending) that calls.umi_group_flat takes -- strset.lists_from_csr(*out["groups"]) is the list
+    umiGroup(groups=) and multiReadAlign take, split(seq_along(reads), group) without empty levels and NA --, and
+    "unmatched.records", the rows whose name is no read's key (counted and ignored).  Every result is exact and the
+    same from run to run.  Bad arguments raise ValueError before a device is touched; no reads or no rows return the
+    all -1 / empty result without one."""
+    from .groups import read_groups
+    return read_groups(ranges, reads, by=by, maxgap=maxgap, ignore_strand=ignore_strand)
