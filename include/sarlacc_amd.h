@@ -65,7 +65,10 @@ double sarlacc_stage_ms(const char* name);
  * longest string needs) and "umi_pairs_k" (the template K of the tile-pair kernel it ran: k_umi_pairs<K> at one word,
  * k_umi_pairs_long<K, XL> beyond; -1 the long kernels' full DP; -2 no tile-pair kernel at all: a split-key search with no
  * string that holds an N or is shorter than 8 bases, or a negative threshold); <0 if unset (-1).  Read
- * "umi_pairs_words" first: while it is > 0 a search has run and an "umi_pairs_k" of -1 is the full DP, not "unset". */
+ * "umi_pairs_words" first: while it is > 0 a search has run and an "umi_pairs_k" of -1 is the full DP, not "unset".
+ * Of every greedy clustering: "umi_links" (entries of the neighbour lists), "umi_cluster_rounds" (parallel rounds in all) =
+ * "umi_cluster_candidate_rounds" (rounds decided on a candidate window) + "umi_cluster_full_rounds" (rounds over every
+ * list), and "umi_cluster_widened" / "umi_cluster_narrowed" (candidate rounds after which the window was doubled / halved). */
 double sarlacc_stage_count(const char* name);
 /* Duration in ms of the DP kernel launches recorded by the last
  * sarlacc_dev_* align call (HIP events on the launch stream; a panel call: the sum over its DP launches); <0 if none. */
@@ -633,7 +636,8 @@ int sarlacc_fast_levdist_test(const char* seq, const int64_t* off, int64_t n, in
 
 /* replaces .Call cluster_umis_test  (src/cluster_umis_test.cpp:8-30).
  * links: CSR of 1-based neighbour lists; clusters returned as CSR of 1-based ids
- * (clu_off needs n+1 entries, clu n entries). */
+ * (clu_off needs n+1 entries, clu n entries).  Beyond the reference's own two errors, lists that are not symmetric, miss
+ * their own read or name a read twice are refused with a message that names the lowest such list. */
 int sarlacc_cluster_umis_test(const int64_t* link_off, const int32_t* links, int64_t n,
                               int64_t* nclusters, int64_t* clu_off, int32_t* clu);
 

@@ -38,6 +38,11 @@ __global__ void k_cl_init(ClusterState S, int check_sym) {
             }
         }
         if (!self) atomicMin(&S.err[2], v);
+        // a node named twice would be stored twice in memb: a cluster list of more than n entries
+        bool twice = false;
+        for (long long p = a + 1; p < b && !twice; ++p)
+            for (long long q = a; q < p && !twice; ++q) twice = S.nbr[q] == S.nbr[p];
+        if (twice) atomicMin(&S.err[3], v);
     }
     S.state[v] = st;
 }
@@ -200,8 +205,8 @@ __global__ void k_cl_control(ClusterState S, ClusterTop T) {
         // a productive list (a quarter or more of it picked) may be hiding picks just below it -> widen
         const long long nc = T.counts[0], np = T.counts[1];
         if (T.counts[2]) { c[CTL_DELTA] = delta / 2; c[CTL_MODE] = CL_WANTS_FULL; c[CTL_WAS_TOP] = 0; return; }
-        if (4 * np >= nc) delta = 2 * delta + 1;
-        else if (64 * np < nc && nc > 256) delta /= 2;
+        if (4 * np >= nc) { delta = 2 * delta + 1; c[CTL_WIDENED] += 1; }
+        else if (64 * np < nc && nc > 256) { delta /= 2; c[CTL_NARROWED] += 1; }
     }
     c[CTL_DELTA] = delta; c[CTL_WAS_TOP] = 1; c[CTL_ROUNDS] += 1;
     T.counts[0] = T.counts[1] = T.counts[2] = T.counts[3] = 0;
@@ -369,8 +374,8 @@ void gid_keys(const int* gid, const int* val, long long n, unsigned long long* k
     hipLaunchKernelGGL(k_cl_gidkey, dim3(nblk(n, 256)), CL_B, 0, s, gid, val, n, key);
 }
 
-// The state of a clustering and k_cl_init; herr: the three error indices it found (INT_MAX: none).
-int cluster_begin(const DevAdj& adj, int n, bool check_sym, ClusterState* S, int herr[3], hipStream_t s) {
+// The state of a clustering and k_cl_init; herr: the four error indices it found (INT_MAX: none).
+int cluster_begin(const DevAdj& adj, int n, bool check_sym, ClusterState* S, int herr[4], hipStream_t s) {
     const std::string p = UMI_WS[WS_CL];
     S->off = adj.off; S->nbr = adj.nbr; S->n = n;
     const size_t nn = static_cast<size_t>(n) + 1;
@@ -383,13 +388,13 @@ int cluster_begin(const DevAdj& adj, int n, bool check_sym, ClusterState* S, int
     SL_TRY(scratch(p + ".pickkey", nn, &S->pickkey));
     SL_TRY(scratch(p + ".memb", static_cast<size_t>(adj.nnz) + 1, &S->memb));
     SL_TRY(scratch(p + ".csize", nn, &S->csize));
-    SL_TRY(scratch(p + ".err", 3, &S->err));
+    SL_TRY(scratch(p + ".err", 4, &S->err));
     SL_TRY(scratch(p + ".live", 1, &S->live));
     const int big = std::numeric_limits<int>::max();
-    const int init[3] = {big, big, big};
+    const int init[4] = {big, big, big, big};
     SL_HIP(hipMemcpyAsync(S->err, init, sizeof init, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_cl_init, per_node(*S), CL_B, 0, s, *S, check_sym ? 1 : 0);
-    SL_HIP(hipMemcpyAsync(herr, S->err, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    SL_HIP(hipMemcpyAsync(herr, S->err, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));
     return 0;
 }

@@ -266,7 +266,7 @@ struct ClusterState {
     unsigned long long* pickkey;
     int* memb;                  // members of the cluster seeded at v, stored at off[v]..
     int* csize;
-    int* err;                   // [0] min index with empty list, [1] min index bad solo, [2] missing self / asymmetric
+    int* err;                   // [0] min index with empty list, [1] min index bad solo, [2] missing self / asymmetric, [3] a node twice
     int* live;                  // count of live pool nodes this round
 };
 
@@ -279,7 +279,8 @@ struct ClusterTop {             // candidate-set rounds, see umi_cluster.hip
     int* marked;                // the nodes clustered this round (two picks of a round share no neighbour: no node twice)
     int* ctl;                   // the rounds' control block, see k_cl_control
 };
-enum { CTL_MODE, CTL_DELTA, CTL_WAS_TOP, CTL_ROUNDS, CTL_MAXREM, CTL_N = 8 };
+// (the host's write-back after a full round covers CTL_MODE..CTL_WAS_TOP only: the counts behind them survive it)
+enum { CTL_MODE, CTL_DELTA, CTL_WAS_TOP, CTL_ROUNDS, CTL_MAXREM, CTL_WIDENED, CTL_NARROWED, CTL_N = 8 };
 enum { CL_DONE = 0, CL_TOP = 1, CL_WANTS_FULL = 3 };   // CL_WANTS_FULL: the list was cut off -- the host runs one round over every list
 constexpr int CL_GROUP = 8;     // candidate-set rounds per read-back of the control block
 
@@ -326,7 +327,7 @@ int dense_distances(const std::string& p, const UmiArrays& U, int n, int words, 
 
 // umi_cluster.hip
 void gid_keys(const int* gid, const int* val, long long n, unsigned long long* key, hipStream_t s);
-int cluster_begin(const DevAdj& adj, int n, bool check_sym, ClusterState* S, int herr[3], hipStream_t s);
+int cluster_begin(const DevAdj& adj, int n, bool check_sym, ClusterState* S, int herr[4], hipStream_t s);
 int cluster_candidates_begin(const ClusterState& S, bool control, ClusterTop* T, hipStream_t s);
 int cluster_count_live(const ClusterState& S, int* live, hipStream_t s);
 void rounds_candidates(const ClusterState& S, const ClusterTop& T, int* round, hipStream_t s);

@@ -294,12 +294,14 @@ static int group_adjacency(const uint8_t* d_c1, const int64_t* d_o1, const uint8
 static int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const int* d_gid, int ngroups, bool check_sym,
                        ClusterResult* res, hipStream_t s) {
     ClusterState S{};
-    int herr[3];
+    int herr[4];
     // one wavefront per node from 24 links per node on average (one thread per node below that)
     const bool dense = adj.nnz >= 24LL * n;
     ctx().counts["umi_links"] = static_cast<double>(adj.nnz);
     ctx().counts["umi_cluster_candidate_rounds"] = 0;
     ctx().counts["umi_cluster_full_rounds"] = 0;
+    ctx().counts["umi_cluster_widened"] = 0;
+    ctx().counts["umi_cluster_narrowed"] = 0;
     SL_TRY(cluster_begin(adj, n, check_sym, &S, herr, s));
     const int big = std::numeric_limits<int>::max();
     // first error in index order, as the reference's loop would meet it (src/cluster_umis.cpp:21-40)
@@ -307,6 +309,8 @@ static int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const
         if (herr[0] < herr[1]) return fail("zero length read group");
         return fail("single-read groups should contain only the read itself");
     }
+    // (a read named twice in a list: the reference skips the second mention, k_cl_pick would store both)
+    if (herr[3] != big && herr[3] <= herr[2]) return fail("sarlacc_amd: list %d names a read twice", herr[3] + 1);
     if (herr[2] != big)
         return fail("sarlacc_amd: neighbour lists must be symmetric and contain the read itself (list %d is not)", herr[2] + 1);
 
@@ -314,7 +318,7 @@ static int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const
     ClusterTop T{};
     if (dense) SL_TRY(cluster_candidates_begin(S, top_rounds, &T, s));
     long long top_rounds_run = 0, full_rounds_run = 0;
-    int rounds_total = 0;
+    int rounds_total = 0, widened = 0, narrowed = 0;
     if (top_rounds) {
         // Candidate-set rounds under the device's control (k_cl_control): CL_GROUP rounds per read-back.  A round whose list
         // was cut off parks the control block (CL_WANTS_FULL; the rounds still queued behind it do nothing) and the host
@@ -337,6 +341,7 @@ static int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const
             if (hctl[CTL_ROUNDS] + full_rounds_run > 4LL * n + 16) return fail("sarlacc_amd: clustering did not converge");
         }
         top_rounds_run = hctl[CTL_ROUNDS];
+        widened = hctl[CTL_WIDENED]; narrowed = hctl[CTL_NARROWED];
         rounds_total = static_cast<int>(top_rounds_run + full_rounds_run);
     } else {
         for (int round = 0;; ++round) {
@@ -354,6 +359,9 @@ static int cluster_dev(const DevAdj& adj, int n, const int32_t* d_members, const
     ctx().counts["umi_cluster_rounds"] = rounds_total;
     ctx().counts["umi_cluster_candidate_rounds"] = static_cast<double>(top_rounds_run);
     ctx().counts["umi_cluster_full_rounds"] = static_cast<double>(full_rounds_run);
+    // rounds after which k_cl_control doubled / halved the candidate window
+    ctx().counts["umi_cluster_widened"] = widened;
+    ctx().counts["umi_cluster_narrowed"] = narrowed;
     return clusters_write(S, d_members, d_gid, ngroups, res, s);
 }
 
