@@ -470,6 +470,34 @@ int sarlacc_dev_locus_labels(const int32_t* d_ref, const uint8_t* d_strand, cons
 int sarlacc_dev_labels_csr(const int32_t* d_label, int64_t n, int64_t* d_group_off, int32_t* d_members, int64_t* n_groups,
                            int64_t* n_members, void* stream);
 
+/* Reference-free pre-groups of a read batch from k-mer sketches (generics.sequenceGroups; csrc/sketch.hip; the rules are
+ * DESIGN.md §4.19).  Three calls on data already in device memory, each usable alone; labels go to CSR groups by
+ * sarlacc_dev_labels_csr.  Every result is exact and the same from run to run: no value depends on the order in which
+ * atomics arrive.  All calls return when the device has finished.
+ * sarlacc_dev_sketch_reads: the one-permutation MinHash sketch of every read.  d_seq / d_off are the bases and the n + 1
+ * offsets of a batch; A, C, G, T in upper case are bases, every other byte breaks a k-mer.  k in 5 .. 31, buckets a power
+ * of two in 16 .. 256.  A k-mer's value is lo | hi << 32 (bit i of lo / hi: the low / high bit of the code of its base i,
+ * A 0 C 1 G 2 T 3), with canonical != 0 the smaller of that and the value of its reverse complement; its hash is fmix64 of
+ * the value, and a k-mer whose hash is 2^64 - 1 counts as absent.  d_sketch[r * buckets + j] is the smallest hash h of
+ * read r with h >> (64 - log2 buckets) == j, 2^64 - 1 where there is none; d_nkmers[r] counts the read's present k-mers.
+ * No byte outside [d_off[0], d_off[n]) is read.  "read K: its offsets do not ascend inside the sequence buffer".
+ * sarlacc_dev_sketch_links: the non-empty entries (h, read) of d_sketch (n * buckets words, below 2^31) are sorted by h,
+ * then by read; every entry is paired with the entries at distance 1 .. window (1 .. 64) behind it that hold the same h;
+ * shared(a, b) counts the pairs of reads a < b, and a -- b is a link when shared(a, b) >= min_shared (1 .. buckets).
+ * *n_pairs is the number of distinct pairs with shared >= 1, *n_links the number of links (either may be NULL); always
+ * the full numbers.  d_links (may be NULL: sizing) gets the first `capacity` links as a << 32 | b in ascending order, so a
+ * caller whose capacity was below *n_links calls again.
+ * sarlacc_dev_components: the connected components of n vertices under n_links links (a << 32 | b, any order, repeats
+ * allowed).  d_nkmers (n entries; may be NULL: every vertex counts) marks with a value <= 0 the vertices that are in no
+ * group: they get label -1 and their links are ignored.  d_label[v] numbers the components from 0 in ascending order of
+ * their lowest vertex; *n_groups (may be NULL) is their number.  "link K: an end outside 0 .. n - 1". */
+int sarlacc_dev_sketch_reads(const uint8_t* d_seq, const int64_t* d_off, int64_t n, int k, int buckets, int canonical,
+                             uint64_t* d_sketch, int32_t* d_nkmers, void* stream);
+int sarlacc_dev_sketch_links(const uint64_t* d_sketch, int64_t n, int buckets, int window, int min_shared, uint64_t* d_links,
+                             int64_t capacity, int64_t* n_pairs, int64_t* n_links, void* stream);
+int sarlacc_dev_components(const uint64_t* d_links, int64_t n_links, int64_t n, const int32_t* d_nkmers, int32_t* d_label,
+                           int64_t* n_groups, void* stream);
+
 /* SAM alignment records already in device memory -> ranges (sam2ranges, R/sam2ranges.R:8-95).  d_text holds
  * body lines of a SAM file (no header), LF or CRLF, blank lines skipped; first_line is the 1-based file line
  * number of its first line, used in error messages.  The caller reads the header: ref_names / ref_off (n_ref + 1

@@ -832,3 +832,38 @@ def readGroups(ranges, reads, by="reference", maxgap=0, ignore_strand=True):
     all -1 / empty result without one."""
     from .groups import read_groups
     return read_groups(ranges, reads, by=by, maxgap=maxgap, ignore_strand=ignore_strand)
+
+
+# ---------------------------------------------------------------------------
+# sequenceGroups: the pre-groups of umiGroup(groups=) without a mapping (vignettes/correction.Rmd)
+
+def sequenceGroups(reads, k=13, buckets=64, window=8, min_shared=3, canonical=True):
+    """The `pre.groups` of the reference's correction vignette by its second route -- "cluster reads together using
+    software like vsearch" -- without a reference and without leaving the device.  vsearch is not restated; the stage
+    follows a specification of its own.  `reads` is a resident.DeviceReads (used where it lies) or a
+    Reads (uploaded).  Every read gets a one-permutation MinHash sketch: its k-mers (k consecutive A, C, G, T in upper
+    case, 5 <= k <= 31; every other byte breaks a k-mer; with `canonical` a k-mer and its reverse complement are one)
+    are hashed by fmix64, the top log2(buckets) bits of a hash choose one of `buckets` (a power of two in 16 .. 256)
+    buckets, and the sketch keeps the smallest hash of each bucket.  All non-empty sketch entries are sorted by (hash,
+    read); an entry is paired with the entries at distance 1 .. `window` (1 .. 64) behind it that hold the same hash,
+    so reads that share a k-mer minimum become candidates at a cost bounded by n * buckets * window.  Two reads are
+    linked when they share at least `min_shared` (1 .. buckets) such entries, and the groups are the connected
+    components of the links, numbered from 0 in ascending order of their lowest read.  A read with a k-mer and no link
+    is a group of one; a read without any k-mer has label -1 and is in no group.
+    On reads of the mock error process (5 % substitutions, 1 % indels; 12 transcripts x 10 reads of 600 bases and 6 x
+    40 reads of 1 kb, a CPU prototype) every transcript is exactly one group for min_shared 2 to 4; at about twice
+    that rate min_shared = 2 is still clean, 3 starts to split transcripts and 4 splits most of them: lower
+    `min_shared` for noisier reads, raise it (or `k`) where transcripts share long stretches.  The defaults suit small
+    sets.  There are 4^13 / 2 = 3.4e7 canonical 13-mers, so once the distinct sequence of a batch comes near that,
+    13-mers recur by chance: on 1e6 reads of 1e5 random 2-kb transcripts at the mock rates (profiles/sequence_groups.txt)
+    the defaults split no transcript but 5.8 % of the groups hold several, and min_shared = 2 chains everything into
+    one group; min_shared = 4 (0.05 % of the groups mixed) or k = 16 (0.4 %, in under half of the time, since far fewer
+    candidate pairs arise) are the better choice there.  At twice the error rate no setting tried was clean at that
+    scale: longer k-mers do not survive the errors, shorter ones collide.
+    Returns a dict in the reads' order, shaped as readGroups returns it: "group" (int32 labels), "groups" (the CSR pair
+    (off int64[G + 1], members int32, 1-based, ascending) that calls.umi_group_flat takes;
+    strset.lists_from_csr(*out["groups"]) is the list umiGroup(groups=) takes), "n.kmers" (int32), "n.pairs" (int64:
+    distinct candidate pairs) and "n.links" (int64).  Every result is exact and the same from run to run.  Bad
+    arguments raise ValueError before a device is touched; no reads return the empty result without one."""
+    from .sketch import sequence_groups
+    return sequence_groups(reads, k=k, buckets=buckets, window=window, min_shared=min_shared, canonical=canonical)

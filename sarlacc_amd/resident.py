@@ -663,3 +663,14 @@ class DeviceReads:
         out = _profile_fetch(len(rf), ni.value, nr.value, no.value)
         out["score"], out["edit"] = d_scores.to_numpy(np.float64, n), d_edits.to_numpy(np.int32, n)
         return out
+
+    def sketch(self, k=13, buckets=64, canonical=True):
+        """The one-permutation MinHash sketch of every read (sarlacc_dev_sketch_reads): (uint64[n, buckets]
+        bucket minima of the k-mer hashes, 2^64 - 1 in an empty bucket; int32[n] numbers of k-mers), on the host."""
+        from . import sketch as sk
+        k, buckets, _, _ = sk.check_args(k, buckets)
+        n = len(self)
+        if n == 0:
+            return np.zeros((0, buckets), np.uint64), np.zeros(0, np.int32)
+        d_sketch, d_nk = sk.sketch_reads(self.seq, self.off, n, k, buckets, canonical)
+        return d_sketch.to_numpy(np.uint64, n * buckets).copy().reshape(n, buckets), d_nk.to_numpy(np.int32, n).copy()
