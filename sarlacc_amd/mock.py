@@ -10,7 +10,7 @@ from .encoding import error_to_phred_char
 from .strset import StringSet
 
 NUC = np.frombuffer(b"ACGT", dtype=np.uint8)
-_COMP = np.zeros(256, np.uint8)
+_COMP = np.arange(256, dtype=np.uint8)   # the device rule (resident.hip:complement_base): a byte that is no swapped letter is kept
 for a, b in zip(b"ACGTNMRWSYKVHDB-", b"TGCANKYWSRMBDHV-"):
     _COMP[a] = b
 

@@ -513,6 +513,8 @@ class DeviceReads:
 
     def front_and_back(self, tolerance):
         """.get_front_and_back (R/adaptorAlign.R:86-95) on the device.  The two window batches carry no tags."""
+        if int(tolerance) < 0:
+            raise _lib.SarlaccError("'tolerance' must not be negative")
         w = np.minimum(int(tolerance), np.diff(self.off_host))
         woff = np.zeros(len(self) + 1, np.int64)
         np.cumsum(w, out=woff[1:])
@@ -529,10 +531,15 @@ class DeviceReads:
         n = len(self)
         st = np.ascontiguousarray(start, dtype=np.int32)
         wd = np.ascontiguousarray(np.maximum(np.asarray(width, dtype=np.int64), 0), dtype=np.int32)
+        sel = None if from_other is None else np.ascontiguousarray(from_other, dtype=np.uint8)
+        for what, a in (("start", st), ("width", wd), ("from_other", sel)):
+            if a is not None and a.shape != (n,):
+                raise _lib.SarlaccError("'%s' holds %d entries for %d reads" % (what, a.size, n))
+        if other is not None and len(other) != n:
+            raise _lib.SarlaccError("'other' holds %d reads, this batch %d" % (len(other), n))
         off = np.zeros(n + 1, np.int64)
         total = int(wd.sum(dtype=np.int64))
         chars = _lib.host_array(max(total, 1), np.uint8)
-        sel = None if from_other is None else np.ascontiguousarray(from_other, dtype=np.uint8)
         o_seq, o_off = (other.seq, other.off) if other is not None else (None, None)
         check(_lib.lib().sarlacc_dev_subseq(self.seq, self.off, o_seq, o_off, sel, st, wd, n, chars, chars.size, off, None))
         return StringSet(chars, off)
@@ -544,9 +551,14 @@ class DeviceReads:
         unchanged (a splice with src): MM / ML / mv no longer fit a trimmed or reversed read -- drop_tags."""
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         rev = np.ascontiguousarray(reversed_, dtype=np.uint8)
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= len(self))):
+            raise _lib.SarlaccError("'idx' must be a vector of read numbers in 0..%d" % (len(self) - 1))
         w = np.diff(self.off_host)[idx]
         ts = np.ones(idx.size, np.int32) if trim_start is None else np.ascontiguousarray(trim_start, dtype=np.int32)
         te = w.astype(np.int32) if trim_end is None else np.ascontiguousarray(trim_end, dtype=np.int32)
+        for what, a in (("reversed_", rev), ("trim_start", ts), ("trim_end", te)):
+            if a.shape != idx.shape:
+                raise _lib.SarlaccError("'%s' holds %d entries for the %d reads of 'idx'" % (what, a.size, idx.size))
         if idx.size and ((ts < 1).any() or (te > w).any()):
             raise _lib.SarlaccError("trim coordinates outside the read")
         ow = np.maximum(te.astype(np.int64) - ts + 1, 0)
