@@ -21,11 +21,12 @@
 //   k_bam_fields   one wavefront per record: the fixed fields, the keep decision, and on kept records the CIGAR array
 //                  (lanes stride over the ops; a 64-bit wave reduction sums the reference-consuming lengths).  A kept record
 //                  whose CIGAR is the stand-in <l_seq>S<n>N of a CIGAR above 65 535 ops has its tags walked by one lane
-//                  for the CG:B,I array.  It fills SamRec / keep / name_len as k_sam_fields does, and the scans, the
-//                  scatter and the extract step of sam.hip are reused unchanged.
+//                  for the CG:B,I array.  It fills SamRec / keep / name_len as k_sam_fields does; the scans and the
+//                  extract step are shared with the SAM reader (ranges_index, k_sam_scatter).
 //
-// The locator's launch sequence is bam_locate, and the layout check bam_layout_ok (bam_rec.hpp): bam_reads.hip, which
-// turns the same records into reads, calls both.
+// The host side is in readers_host.cpp: the locator's launch sequence (bam_locate, which bam_reads.hip's records go
+// through as well), the entry points and the messages below.  The functions at the end of this file only enqueue.  The
+// layout check is bam_layout_ok (bam_rec.hpp).
 //
 // No kernel waits on a value another workgroup writes: the launches are the synchronisation.  Every loop is bounded by
 // BAM_TILE or nbytes, no byte at or beyond nbytes is read, and a bad file is an error return (the first_bad pattern of
@@ -43,29 +44,13 @@
 //   cigar_clips  CIGAR has only H and S operations
 //   end          alignment end outside the 32-bit integer range
 #include "bam_rec.hpp"
-#include "common.hpp"
 #include "devprim.hpp"
-#include "sam_rec.hpp"
-
-#include "../../include/sarlacc_amd.h"
+#include "readers.hpp"
 
 #include <algorithm>
 #include <climits>
 
 namespace sarlacc {
-
-// status codes of a record, in the order the checks run (one code per record; the first bad record wins)
-enum {
-    BAM_LAYOUT = 1,
-    BAM_POS = 2,
-    BAM_RNAME = 3,
-    BAM_CIGAR_STAR = 4,
-    BAM_CIGAR_OP = 5,
-    BAM_TAGS = 6,
-    BAM_CIGAR_RANGE = 7,
-    BAM_CIGAR_CLIPS = 8,
-    BAM_END = 9,
-};
 
 constexpr int BAM_HOP_THREADS = 1024;
 constexpr int BAM_MIN_RECORD = 36;               // block_size + the 32 fixed bytes
@@ -287,143 +272,42 @@ __global__ void __launch_bounds__(BAM_THREADS) k_bam_fields(const uint8_t* bam, 
     }
 }
 
-static thread_local unsigned long long g_bam_generation = 0;
-
-unsigned long long bam_locate_generation() { return g_bam_generation; }
-
-int bam_locate(const uint8_t* d_bam, long long nbytes, hipStream_t s, BamLocated* out) {
-    Context& c = ctx();
-    for (const char* name : {"bam_hops", "bam_chain", "bam_starts"}) c.stage_reset(name);
-    out->generation = ++g_bam_generation;
-    const long long ntiles = (nbytes + BAM_TILE - 1) / BAM_TILE;
-    if (ntiles > INT_MAX) return fail("sarlacc_amd: BAM buffer too large");
-    unsigned* d_table; long long* d_entry; long long* d_count; long long* d_base; long long* d_term;
-    SL_TRY(scratch("bam.hops", static_cast<size_t>(nbytes), &d_table));
-    SL_TRY(scratch("bam.entry", static_cast<size_t>(ntiles), &d_entry));
-    SL_TRY(scratch("bam.count", static_cast<size_t>(ntiles) + 1, &d_count));
-    SL_TRY(scratch("bam.base", static_cast<size_t>(ntiles) + 1, &d_base));
-    SL_TRY(scratch("bam.term", 2, &d_term));
-    SL_HIP(hipMemsetAsync(d_entry, 0xff, static_cast<size_t>(ntiles) * sizeof(long long), s));
-    SL_HIP(hipMemsetAsync(d_term, 0xff, 2 * sizeof(long long), s));
-    SL_HIP(hipMemsetAsync(d_count + ntiles, 0, sizeof(long long), s));
-    SL_TRY(c.stage_begin("bam_hops", s));
-    hipLaunchKernelGGL(k_bam_hops, dim3(static_cast<unsigned>(ntiles)), dim3(BAM_HOP_THREADS), 0, s, d_bam, nbytes, d_table);
+int bam_hops(const uint8_t* bam, long long nbytes, long long ntiles, unsigned* table, hipStream_t s) {
+    hipLaunchKernelGGL(k_bam_hops, dim3(static_cast<unsigned>(ntiles)), dim3(BAM_HOP_THREADS), 0, s, bam, nbytes, table);
     SL_HIP(hipGetLastError());
-    SL_TRY(c.stage_end("bam_hops", s));
-    SL_TRY(c.stage_begin("bam_chain", s));
-    hipLaunchKernelGGL(k_bam_chain, dim3(1), dim3(64), 0, s, d_table, nbytes, ntiles, d_entry);
-    SL_HIP(hipGetLastError());
-    SL_TRY(c.stage_end("bam_chain", s));
-    SL_TRY(c.stage_begin("bam_starts", s));
-    hipLaunchKernelGGL(k_bam_starts<false>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, d_bam, nbytes, ntiles, d_entry, d_count, d_base,
-                       static_cast<long long*>(nullptr), d_term);
-    SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan("bam.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
-    long long nrec = 0, term[2] = {-1, -1};
-    SL_HIP(hipMemcpyAsync(&nrec, d_base + ntiles, sizeof nrec, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipMemcpyAsync(term, d_term, sizeof term, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipStreamSynchronize(s));
-    if (term[0] < 0 || term[0] > nbytes || nrec < 0) return fail("sarlacc_amd: the BAM record chain did not end (internal error)");
-    SL_TRY(scratch("bam.off", static_cast<size_t>(nrec) + 1, &out->d_off));
-    if (nrec > 0) {
-        hipLaunchKernelGGL(k_bam_starts<true>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, d_bam, nbytes, ntiles, d_entry, d_count,
-                           d_base, out->d_off, d_term);
-        SL_HIP(hipGetLastError());
-    }
-    SL_TRY(c.stage_end("bam_starts", s));
-    out->nrec = nrec;
-    out->end = term[0];
-    out->how = static_cast<int>(term[1]);
     return 0;
 }
 
-int bam_chain_end_error(const BamLocated& L, long long first_record, int at_eof) {
-    if (L.how == BAM_CHAIN_SIZE) return fail("BAM record %lld: block size below 32", first_record + L.nrec);
-    if (L.how == BAM_CHAIN_INCOMPLETE && at_eof) return fail("BAM record %lld: file ends inside the record", first_record + L.nrec);
+int bam_chain(const unsigned* table, long long nbytes, long long ntiles, long long* entry, hipStream_t s) {
+    hipLaunchKernelGGL(k_bam_chain, dim3(1), dim3(64), 0, s, table, nbytes, ntiles, entry);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
+int bam_starts_count(const uint8_t* bam, long long nbytes, long long ntiles, const long long* entry, long long* count,
+                     long long* term, hipStream_t s) {
+    hipLaunchKernelGGL(k_bam_starts<false>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, bam, nbytes, ntiles, entry, count,
+                       static_cast<const long long*>(nullptr), static_cast<long long*>(nullptr), term);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
+int bam_starts_write(const uint8_t* bam, long long nbytes, long long ntiles, const long long* entry, const long long* base,
+                     long long* rec_off, hipStream_t s) {
+    hipLaunchKernelGGL(k_bam_starts<true>, dim3(nblk(ntiles, 64)), dim3(64), 0, s, bam, nbytes, ntiles, entry,
+                       static_cast<long long*>(nullptr), base, rec_off, static_cast<long long*>(nullptr));
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
+int bam_fields(const uint8_t* bam, const long long* rec_off, long long nrec, long long n_ref, const uint8_t* mask, int use_minq,
+               long long minq, SamRec* rec, int* keep, long long* name_len, unsigned long long* first_bad, hipStream_t s) {
+    // one wavefront per record, up to 256 workgroups per CU
+    const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nrec, BAM_THREADS / 64), static_cast<long long>(ctx().num_cu) * 256));
+    hipLaunchKernelGGL(k_bam_fields, dim3(grid), dim3(BAM_THREADS), 0, s, bam, rec_off, nrec, n_ref, mask, use_minq, minq, rec,
+                       keep, name_len, first_bad);
+    SL_HIP(hipGetLastError());
     return 0;
 }
 
 }  // namespace sarlacc
-
-using namespace sarlacc;
-
-extern "C" {
-
-int sarlacc_bam_tile_bytes(void) { return BAM_TILE; }
-
-int sarlacc_dev_bam_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_record, int at_eof, int64_t n_ref,
-                          const uint8_t* restricted_mask, int use_minq, int64_t minq, int64_t* n_records, int64_t* used_bytes,
-                          int64_t* n_kept, int64_t* kept_name_bytes, void* stream) {
-    SL_TRY(ensure_device());
-    if (nbytes < 0 || n_ref < 0) return fail("sarlacc_amd: negative BAM size");
-    if (n_ref >= INT_MAX) return fail("sarlacc_amd: too many reference names");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    g_sam = SamIndex{};
-    *n_records = 0; *used_bytes = 0; *n_kept = 0; *kept_name_bytes = 0;
-    if (nbytes == 0) {
-        g_sam.text = d_bam;    // no records: an empty result
-        return 0;
-    }
-    Context& c = ctx();
-    c.stage_reset("bam_fields");
-    BamLocated L;
-    SL_TRY(bam_locate(d_bam, nbytes, s, &L));
-    const long long nrec = L.nrec;
-    long long* d_off = L.d_off;
-
-    // the records: fields, keep flags, scans (the back end of sam.hip)
-    unsigned long long bad = ~0ull;
-    int64_t nk = 0, nb = 0;
-    if (nrec > 0) {
-        uint8_t* d_mask = nullptr;
-        if (restricted_mask) SL_TRY(upload("bam.mask", restricted_mask, static_cast<size_t>(n_ref) + 1, &d_mask, s));
-        SamRec* d_rec; int* d_keep; long long* d_nlen; int64_t* d_koff; int64_t* d_noff; unsigned long long* d_bad;
-        SL_TRY(scratch("sam.rec", static_cast<size_t>(nrec), &d_rec));
-        SL_TRY(scratch("sam.keep", static_cast<size_t>(nrec) + 1, &d_keep));
-        SL_TRY(scratch("sam.nlen", static_cast<size_t>(nrec) + 1, &d_nlen));
-        SL_TRY(scratch("sam.koff", static_cast<size_t>(nrec) + 1, &d_koff));
-        SL_TRY(scratch("sam.noff", static_cast<size_t>(nrec) + 1, &d_noff));
-        SL_TRY(scratch("sam.bad", 1, &d_bad));
-        SL_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), s));
-        SL_HIP(hipMemsetAsync(d_keep + nrec, 0, sizeof(int), s));
-        SL_HIP(hipMemsetAsync(d_nlen + nrec, 0, sizeof(long long), s));
-        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nrec, BAM_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
-        SL_TRY(c.stage_begin("bam_fields", s));
-        hipLaunchKernelGGL(k_bam_fields, dim3(grid), dim3(BAM_THREADS), 0, s, d_bam, d_off, nrec, static_cast<long long>(n_ref),
-                           d_mask, use_minq ? 1 : 0, static_cast<long long>(minq), d_rec, d_keep, d_nlen, d_bad);
-        SL_HIP(hipGetLastError());
-        SL_TRY(c.stage_end("bam_fields", s));
-        SL_TRY(exclusive_scan("sam.scan", d_keep, d_koff, static_cast<size_t>(nrec) + 1, s));
-        SL_TRY(exclusive_scan("sam.scan", d_nlen, d_noff, static_cast<size_t>(nrec) + 1, s));
-        SL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipMemcpyAsync(&nk, d_koff + nrec, sizeof nk, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipMemcpyAsync(&nb, d_noff + nrec, sizeof nb, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipStreamSynchronize(s));
-    }
-    if (bad != ~0ull) {      // a record before the one the chain ends at: the lowest record wins
-        const long long k = first_record + static_cast<long long>(bad >> 4);
-        switch (bad & 15u) {
-            case BAM_LAYOUT: return fail("BAM record %lld: record fields do not fit its block size", k);
-            case BAM_POS: return fail("BAM record %lld: POS is not a 32-bit integer", k);
-            case BAM_RNAME: return fail("BAM record %lld: reference ID outside the header's reference list", k);
-            case BAM_CIGAR_STAR: return fail("BAM record %lld: no CIGAR on a kept record", k);
-            case BAM_CIGAR_OP: return fail("BAM record %lld: CIGAR operation code above 8", k);
-            case BAM_TAGS: return fail("BAM record %lld: malformed tags or CG tag behind a long-CIGAR stand-in", k);
-            case BAM_CIGAR_RANGE: return fail("BAM record %lld: CIGAR length above 2^31 - 1", k);
-            case BAM_CIGAR_CLIPS: return fail("BAM record %lld: CIGAR has only H and S operations", k);
-            default: return fail("BAM record %lld: alignment end outside the 32-bit integer range", k);
-        }
-    }
-    SL_TRY(bam_chain_end_error(L, first_record, at_eof));
-    g_sam.text = d_bam; g_sam.nlines = nrec; g_sam.nkept = nk; g_sam.name_bytes = nb;
-    *n_records = nrec; *used_bytes = L.end;
-    *n_kept = nk; *kept_name_bytes = nb;
-    return 0;
-}
-
-int sarlacc_dev_bam_extract(const uint8_t* d_bam, int32_t* d_ref, int32_t* d_start, int32_t* d_width, uint8_t* d_strand,
-                            int32_t* d_lclip, int32_t* d_rclip, uint8_t* d_names, int64_t* d_name_off, void* stream) {
-    // the state, the scans and the scatter are the SAM pair's
-    return sarlacc_dev_sam_extract(d_bam, d_ref, d_start, d_width, d_strand, d_lclip, d_rclip, d_names, d_name_off, stream);
-}
-}

@@ -1,7 +1,7 @@
 // bam_reads.hip -- BAM alignment records -> resident read batch, on gfx950: SEQ and QUAL of the records (SAM
 // specification section 4.2) unpacked into the flat seq / qual / offsets / names layout every other kernel consumes.
 // The caller inflates the BGZF blocks on the device (bgzf.hip) and reads the header on the host; the records are
-// located by the locator of bam.hip (bam_locate).
+// located by the locator of bam.hip.
 //
 // A record becomes a read unless flag & exclude_flags.  SEQ holds two 4-bit codes per byte, high nibble first, decoded
 // through "=ACMGRSVTWYHKDBN"; QUAL holds Phred values, written as value + 33; with flag & 0x10 the stored read is the
@@ -33,21 +33,20 @@
 // error return (first_bad: atomicMin on record << 4 | code), never a fault.
 //
 // Messages, "BAM record K: <reason>", K 1-based over the alignment records of the file; the lowest record wins, within
-// a record layout, SEQ, QUAL; the locator's two messages are bam.hip's:
+// a record layout, SEQ, QUAL; the locator's two messages are those of the ranges path (bam.hip).  The host side -- the
+// six sarlacc_dev_bam_reads_* entry points, the index state, these texts -- is in readers_host.cpp; the functions at the
+// end of this file only enqueue:
 //   layout   record fields do not fit its block size      (every record)
 //   seq      SEQ holds '='                                (kept records)
 //   qual     quality value above 93                       (kept records)
 #include "bam_rec.hpp"
 #include "out_tiles.hpp"
-
-#include "../../include/sarlacc_amd.h"
+#include "readers.hpp"
 
 #include <algorithm>
 
 namespace sarlacc {
 namespace {
-
-enum { BAMR_LAYOUT = 1, BAMR_SEQ = 2, BAMR_QUAL = 3 };
 
 constexpr int BR_TILE = 64 * 16 * OT_PIECES;      // bases per wavefront and step
 
@@ -242,240 +241,58 @@ __global__ void __launch_bounds__(OT_THREADS) k_bamr_aux(const uint8_t* bam, con
     });
 }
 
-// state of the last sarlacc_dev_bam_reads_index call on this thread
-struct BamReadsIndex {
-    bool valid = false;
-    const uint8_t* bam = nullptr;
-    unsigned long long generation = 0;     // of the locator run whose record offsets this state points to
-    long long nrec = 0, nreads = 0, used = 0;
-    long long* rec_off = nullptr;          // nrec + 1: the last entry is `used`
-    int64_t* base_off = nullptr;           // nrec + 1 each: exclusive scans over the records
-    int64_t* name_off = nullptr;
-    long long* read_rec = nullptr;         // nreads + 1: record of a read, nrec behind the last
-    const int* keep = nullptr;             // nrec + 1
-    int64_t* aux_off = nullptr;            // nrec + 1, an exclusive scan as base_off is; null until tags are asked for
-};
-thread_local BamReadsIndex g_bamr;
-
-// the records a .. e that hold the reads first .. first + count, what they need and where the next record starts
-struct BamReadsSpan {
-    long long a = 0, e = 0;
-    int64_t bases = 0, name_bytes = 0, next_byte = 0;
-};
-
-int bamr_span(long long first, long long count, BamReadsSpan* sp);
-
-// the aux offsets of the indexed buffer's records, made on the first request
-int bamr_aux_index(hipStream_t s) {
-    BamReadsIndex& X = g_bamr;
-    if (X.aux_off || X.nrec == 0) return 0;
-    long long* d_alen; int64_t* d_aoff;
-    SL_TRY(scratch("bamr.alen", static_cast<size_t>(X.nrec) + 1, &d_alen));
-    SL_TRY(scratch("bamr.aoff", static_cast<size_t>(X.nrec) + 1, &d_aoff));
-    hipLaunchKernelGGL(k_bamr_aux_len, dim3(nblk(X.nrec + 1, 256)), dim3(256), 0, s, X.bam, X.rec_off, X.keep, X.nrec, d_alen);
-    SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan("bamr.scan", d_alen, d_aoff, static_cast<size_t>(X.nrec) + 1, s));
-    X.aux_off = d_aoff;
-    return 0;
-}
-
-int bamr_span(long long first, long long count, BamReadsSpan* sp) {
-    const BamReadsIndex& X = g_bamr;
-    *sp = BamReadsSpan{};
-    if (!X.valid || X.generation != bam_locate_generation())
-        return fail("sarlacc_amd: no BAM reads index on this thread (sarlacc_dev_bam_reads_index comes first)");
-    if (first < 0 || count < 0 || first > X.nreads || count > X.nreads - first) return fail("sarlacc_amd: BAM read range outside the indexed buffer");
-    if (X.nrec == 0) {
-        sp->next_byte = X.used;
-        return 0;
-    }
-    // the record after the last read of the range; everything behind the last read of the buffer goes with it
-    long long e = 0;
-    if (first + count == X.nreads) e = X.nrec;
-    else if (first + count > 0) {
-        SL_HIP(hipMemcpy(&e, X.read_rec + first + count - 1, sizeof e, hipMemcpyDeviceToHost));
-        ++e;
-    }
-    long long a = e;
-    if (count > 0) SL_HIP(hipMemcpy(&a, X.read_rec + first, sizeof a, hipMemcpyDeviceToHost));
-    if (a < 0 || a > e || e > X.nrec) return fail("sarlacc_amd: BAM reads index is damaged (internal error)");
-    int64_t b[2], n[2];
-    long long next = 0;
-    SL_HIP(hipMemcpy(&b[0], X.base_off + a, sizeof(int64_t), hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(&b[1], X.base_off + e, sizeof(int64_t), hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(&n[0], X.name_off + a, sizeof(int64_t), hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(&n[1], X.name_off + e, sizeof(int64_t), hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(&next, X.rec_off + e, sizeof next, hipMemcpyDeviceToHost));
-    sp->a = a; sp->e = e;
-    sp->bases = b[1] - b[0]; sp->name_bytes = n[1] - n[0]; sp->next_byte = next;
-    return 0;
-}
-
 }  // namespace
+
+int bamr_size(const uint8_t* bam, const long long* rec_off, long long nrec, unsigned exclude, int* keep, long long* bases,
+              long long* name_len, unsigned long long* first_bad, hipStream_t s) {
+    // one wavefront per record, up to 256 workgroups per CU
+    const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nrec, OT_THREADS / 64), static_cast<long long>(ctx().num_cu) * 256));
+    hipLaunchKernelGGL(k_bamr_size, dim3(grid), dim3(OT_THREADS), 0, s, bam, rec_off, nrec, exclude, keep, bases, name_len, first_bad);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
+int bamr_reads(const int* keep, const int64_t* read_of, long long nrec, long long* read_rec, hipStream_t s) {
+    hipLaunchKernelGGL(k_bamr_reads, dim3(nblk(nrec + 1, 256)), dim3(256), 0, s, keep, read_of, nrec, read_rec);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
+int bamr_unpack(const BamrArrays& X, const BamrRange& R, int missing_qual, uint8_t* seq, uint8_t* qual, int64_t* off,
+                uint8_t* names, int64_t* name_off, hipStream_t s) {
+    const long long num_cu = ctx().num_cu;
+    hipLaunchKernelGGL(k_bamr_offsets, dim3(nblk(R.count + 1, 256)), dim3(256), 0, s, X.read_rec, X.base_off, X.name_off, R.first,
+                       R.count, R.a, off, name_off);
+    SL_HIP(hipGetLastError());
+    if (R.bases > 0) {
+        const BrSource src{X.bam, X.rec_off, X.base_off, static_cast<uint32_t>(missing_qual + 33) * 0x01010101u};
+        const long long ntiles = (R.bases + 15 + BR_TILE - 1) / BR_TILE;
+        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(ntiles, OT_THREADS / 64), num_cu * 8));
+        hipLaunchKernelGGL(k_bamr_unpack, dim3(grid), dim3(OT_THREADS), 0, s, src, R.a, R.e, seq, qual);
+        SL_HIP(hipGetLastError());
+    }
+    if (names && R.name_bytes > 0) {
+        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(R.e - R.a, 16), num_cu * 32));
+        hipLaunchKernelGGL(k_bamr_names, dim3(grid), dim3(256), 0, s, X.bam, X.rec_off, X.name_off, R.a, R.e, names);
+        SL_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int bamr_aux_len(const uint8_t* bam, const long long* rec_off, const int* keep, long long nrec, long long* aux_len, hipStream_t s) {
+    hipLaunchKernelGGL(k_bamr_aux_len, dim3(nblk(nrec + 1, 256)), dim3(256), 0, s, bam, rec_off, keep, nrec, aux_len);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
+int bamr_aux(const BamrArrays& X, const BamrRange& R, uint8_t* aux, int64_t* aux_off, hipStream_t s) {
+    hipLaunchKernelGGL(k_bamr_aux_offsets, dim3(nblk(R.count + 1, 256)), dim3(256), 0, s, X.read_rec, X.aux_off, R.first, R.count,
+                       R.a, aux_off);
+    SL_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_bamr_aux, dim3(static_cast<unsigned>(ctx().num_cu) * 8), dim3(OT_THREADS), 0, s, X.bam, X.rec_off, X.aux_off,
+                       R.a, R.e, aux);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace sarlacc
-
-using namespace sarlacc;
-
-extern "C" {
-
-int sarlacc_dev_bam_reads_index(const uint8_t* d_bam, int64_t nbytes, int64_t first_record, int at_eof, int exclude_flags,
-                                int64_t* n_records, int64_t* used_bytes, int64_t* n_reads, void* stream) {
-    SL_TRY(ensure_device());
-    if (nbytes < 0) return fail("sarlacc_amd: negative BAM size");
-    if (exclude_flags < 0 || exclude_flags > 0xffff) return fail("'exclude_flags' must lie in 0..65535");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    g_bamr = BamReadsIndex{};
-    *n_records = 0; *used_bytes = 0; *n_reads = 0;
-    if (nbytes == 0) {      // no records: an empty batch
-        g_bamr.valid = true; g_bamr.bam = d_bam; g_bamr.generation = bam_locate_generation();
-        return 0;
-    }
-    Context& c = ctx();
-    c.stage_reset("bam_reads_size");
-    BamLocated L;
-    SL_TRY(bam_locate(d_bam, nbytes, s, &L));
-    const long long nrec = L.nrec;
-
-    unsigned long long bad = ~0ull;
-    int64_t nreads = 0;
-    int* d_keep; long long* d_bases; long long* d_nlen; int64_t* d_roff; int64_t* d_boff; int64_t* d_noff; long long* d_rrec;
-    unsigned long long* d_bad;
-    SL_TRY(scratch("bamr.keep", static_cast<size_t>(nrec) + 1, &d_keep));
-    SL_TRY(scratch("bamr.bases", static_cast<size_t>(nrec) + 1, &d_bases));
-    SL_TRY(scratch("bamr.nlen", static_cast<size_t>(nrec) + 1, &d_nlen));
-    SL_TRY(scratch("bamr.roff", static_cast<size_t>(nrec) + 1, &d_roff));
-    SL_TRY(scratch("bamr.boff", static_cast<size_t>(nrec) + 1, &d_boff));
-    SL_TRY(scratch("bamr.noff", static_cast<size_t>(nrec) + 1, &d_noff));
-    SL_TRY(scratch("bamr.rrec", static_cast<size_t>(nrec) + 1, &d_rrec));
-    SL_TRY(scratch("bamr.bad", 1, &d_bad));
-    if (nrec > 0) {
-        SL_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), s));
-        SL_HIP(hipMemsetAsync(d_keep + nrec, 0, sizeof(int), s));
-        SL_HIP(hipMemsetAsync(d_bases + nrec, 0, sizeof(long long), s));
-        SL_HIP(hipMemsetAsync(d_nlen + nrec, 0, sizeof(long long), s));
-        SL_HIP(hipMemcpyAsync(L.d_off + nrec, &L.end, sizeof(long long), hipMemcpyHostToDevice, s));
-        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nrec, OT_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
-        SL_TRY(c.stage_begin("bam_reads_size", s));
-        hipLaunchKernelGGL(k_bamr_size, dim3(grid), dim3(OT_THREADS), 0, s, d_bam, L.d_off, nrec, static_cast<unsigned>(exclude_flags),
-                           d_keep, d_bases, d_nlen, d_bad);
-        SL_HIP(hipGetLastError());
-        SL_TRY(exclusive_scan("bamr.scan", d_keep, d_roff, static_cast<size_t>(nrec) + 1, s));
-        SL_TRY(exclusive_scan("bamr.scan", d_bases, d_boff, static_cast<size_t>(nrec) + 1, s));
-        SL_TRY(exclusive_scan("bamr.scan", d_nlen, d_noff, static_cast<size_t>(nrec) + 1, s));
-        hipLaunchKernelGGL(k_bamr_reads, dim3(nblk(nrec + 1, 256)), dim3(256), 0, s, d_keep, d_roff, nrec, d_rrec);
-        SL_HIP(hipGetLastError());
-        SL_TRY(c.stage_end("bam_reads_size", s));
-        SL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipMemcpyAsync(&nreads, d_roff + nrec, sizeof nreads, hipMemcpyDeviceToHost, s));
-        SL_HIP(hipStreamSynchronize(s));
-    }
-    if (bad != ~0ull) {      // a record before the one the chain ends at: the lowest record wins
-        const long long k = first_record + static_cast<long long>(bad >> 4);
-        switch (bad & 15u) {
-            case BAMR_LAYOUT: return fail("BAM record %lld: record fields do not fit its block size", k);
-            case BAMR_SEQ: return fail("BAM record %lld: SEQ holds '='", k);
-            default: return fail("BAM record %lld: quality value above 93", k);
-        }
-    }
-    SL_TRY(bam_chain_end_error(L, first_record, at_eof));
-    BamReadsIndex& X = g_bamr;
-    X.valid = true; X.bam = d_bam; X.generation = L.generation;
-    X.nrec = nrec; X.nreads = nreads; X.used = L.end;
-    X.rec_off = L.d_off; X.base_off = d_boff; X.name_off = d_noff; X.read_rec = d_rrec; X.keep = d_keep;
-    *n_records = nrec; *used_bytes = L.end; *n_reads = nreads;
-    return 0;
-}
-
-int sarlacc_dev_bam_reads_range(int64_t first, int64_t count, int64_t* total_bases, int64_t* total_name_bytes,
-                                int64_t* next_byte) {
-    BamReadsSpan sp;
-    SL_TRY(bamr_span(first, count, &sp));
-    *total_bases = sp.bases; *total_name_bytes = sp.name_bytes; *next_byte = sp.next_byte;
-    return 0;
-}
-
-int sarlacc_dev_bam_reads_records(int64_t reads_taken, int64_t* n_records) {
-    BamReadsSpan sp;
-    SL_TRY(bamr_span(0, reads_taken, &sp));
-    *n_records = sp.e;
-    return 0;
-}
-
-int sarlacc_dev_bam_reads_extract(const uint8_t* d_bam, int64_t first, int64_t count, int missing_qual, uint8_t* d_seq,
-                                  uint8_t* d_qual, int64_t* d_off, uint8_t* d_names, int64_t* d_name_off, void* stream) {
-    if (missing_qual < 0 || missing_qual > 93) return fail("'missing_qual' must lie in 0..93");
-    if ((d_names == nullptr) != (d_name_off == nullptr)) return fail("sarlacc_amd: read names and their offsets go together");
-    BamReadsSpan sp;
-    SL_TRY(bamr_span(first, count, &sp));
-    const BamReadsIndex& X = g_bamr;
-    if (d_bam != X.bam) return fail("sarlacc_amd: not the BAM buffer indexed last on this thread");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (count == 0 || X.nrec == 0) {      // offsets that start at 0, and nothing else
-        SL_HIP(hipMemsetAsync(d_off, 0, sizeof(int64_t), s));
-        if (d_name_off) SL_HIP(hipMemsetAsync(d_name_off, 0, sizeof(int64_t), s));
-        SL_HIP(hipStreamSynchronize(s));
-        return 0;
-    }
-    Context& c = ctx();
-    c.stage_reset("bam_reads_unpack");
-    SL_TRY(c.stage_begin("bam_reads_unpack", s));
-    hipLaunchKernelGGL(k_bamr_offsets, dim3(nblk(count + 1, 256)), dim3(256), 0, s, X.read_rec, X.base_off, X.name_off,
-                       static_cast<long long>(first), static_cast<long long>(count), sp.a, d_off, d_name_off);
-    SL_HIP(hipGetLastError());
-    if (sp.bases > 0) {
-        const BrSource src{d_bam, X.rec_off, X.base_off, static_cast<uint32_t>(missing_qual + 33) * 0x01010101u};
-        const long long ntiles = (sp.bases + 15 + BR_TILE - 1) / BR_TILE;
-        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(ntiles, OT_THREADS / 64), static_cast<long long>(c.num_cu) * 8));
-        hipLaunchKernelGGL(k_bamr_unpack, dim3(grid), dim3(OT_THREADS), 0, s, src, sp.a, sp.e, d_seq, d_qual);
-        SL_HIP(hipGetLastError());
-    }
-    if (d_names && sp.name_bytes > 0) {
-        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(sp.e - sp.a, 16), static_cast<long long>(c.num_cu) * 32));
-        hipLaunchKernelGGL(k_bamr_names, dim3(grid), dim3(256), 0, s, d_bam, X.rec_off, X.name_off, sp.a, sp.e, d_names);
-        SL_HIP(hipGetLastError());
-    }
-    SL_TRY(c.stage_end("bam_reads_unpack", s));
-    SL_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
-int sarlacc_dev_bam_reads_aux_range(int64_t first, int64_t count, int64_t* aux_bytes) {
-    BamReadsSpan sp;
-    SL_TRY(bamr_span(first, count, &sp));
-    *aux_bytes = 0;
-    if (count == 0 || g_bamr.nrec == 0) return 0;
-    SL_TRY(bamr_aux_index(nullptr));
-    int64_t b[2];
-    SL_HIP(hipMemcpy(&b[0], g_bamr.aux_off + sp.a, sizeof(int64_t), hipMemcpyDeviceToHost));
-    SL_HIP(hipMemcpy(&b[1], g_bamr.aux_off + sp.e, sizeof(int64_t), hipMemcpyDeviceToHost));
-    *aux_bytes = b[1] - b[0];
-    return 0;
-}
-
-int sarlacc_dev_bam_reads_aux_extract(const uint8_t* d_bam, int64_t first, int64_t count, uint8_t* d_aux, int64_t* d_aux_off,
-                                      void* stream) {
-    BamReadsSpan sp;
-    SL_TRY(bamr_span(first, count, &sp));
-    BamReadsIndex& X = g_bamr;
-    if (d_bam != X.bam) return fail("sarlacc_amd: not the BAM buffer indexed last on this thread");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (count == 0 || X.nrec == 0) {
-        SL_HIP(hipMemsetAsync(d_aux_off, 0, sizeof(int64_t), s));
-        SL_HIP(hipStreamSynchronize(s));
-        return 0;
-    }
-    SL_TRY(bamr_aux_index(s));
-    Context& c = ctx();
-    c.stage_reset("bam_reads_aux");
-    SL_TRY(c.stage_begin("bam_reads_aux", s));
-    hipLaunchKernelGGL(k_bamr_aux_offsets, dim3(nblk(count + 1, 256)), dim3(256), 0, s, X.read_rec, X.aux_off,
-                       static_cast<long long>(first), static_cast<long long>(count), sp.a, d_aux_off);
-    SL_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_bamr_aux, dim3(static_cast<unsigned>(c.num_cu) * 8), dim3(OT_THREADS), 0, s, d_bam, X.rec_off, X.aux_off,
-                       sp.a, sp.e, d_aux);
-    SL_HIP(hipGetLastError());
-    SL_TRY(c.stage_end("bam_reads_aux", s));
-    SL_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-}

@@ -1,6 +1,6 @@
 // bam_rec.hpp -- what the BAM paths share (bam.hip: records -> ranges, bam_reads.hip: records -> reads, bam_write.hip:
 // reads -> records, bam_tags.hip: the tags of resident reads): SEQ's alphabet in both directions, the unaligned field
-// readers, the layout predicate every record has to pass, the tag walker, and the locator (implemented in bam.hip).
+// readers, the layout predicate every record has to pass, and the tag walker.  (The locator's interface is in readers.hpp.)
 #pragma once
 
 #include "common.hpp"
@@ -141,26 +141,5 @@ __device__ __forceinline__ int bam_tag_next(const uint8_t* aux, long long p, lon
     T->next = p + 3 + sz;
     return BAM_TAG_OK;
 }
-
-// how the chain of records ends in a buffer
-enum { BAM_CHAIN_CLEAN = 0, BAM_CHAIN_INCOMPLETE = 1, BAM_CHAIN_SIZE = 2 };
-
-// What the locator found in a buffer: the offsets of the nrec records that lie wholly in it (d_off, nrec + 1 entries of
-// the workspace "bam.off", the last one unset), the offset of the first record that does not (nbytes when none is cut)
-// and how the chain ends there.  `generation` counts the locator runs of this thread: d_off belongs to the last one.
-struct BamLocated {
-    long long nrec = 0, end = 0;
-    int how = BAM_CHAIN_CLEAN;
-    long long* d_off = nullptr;
-    unsigned long long generation = 0;
-};
-
-// k_bam_hops / k_bam_chain / k_bam_starts over nbytes > 0 of inflated BAM whose byte 0 starts a record, under the stage
-// timers bam_hops, bam_chain and bam_starts.  The counts are back on the host when it returns; the launch that writes
-// d_off is still on the stream.
-int bam_locate(const uint8_t* d_bam, long long nbytes, hipStream_t s, BamLocated* out);
-unsigned long long bam_locate_generation();
-// The locator's two refusals, for a caller that found no bad record in front of the chain's end (0: none applies).
-int bam_chain_end_error(const BamLocated& L, long long first_record, int at_eof);
 
 }  // namespace sarlacc

@@ -96,6 +96,11 @@ int Context::buffer(const char* name, size_t bytes, void** out) {
     return 0;
 }
 
+bool Context::holds(const char* name, const void* ptr) const {
+    const auto it = ws.find(name);
+    return it != ws.end() && it->second.ptr != nullptr && it->second.ptr == ptr;
+}
+
 int Context::side_stream(hipStream_t* s, hipEvent_t* fork, hipEvent_t* join) {
     if (!side) {
         SL_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));

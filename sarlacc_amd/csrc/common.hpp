@@ -116,6 +116,8 @@ struct Context {
 
     // Returns a cached device buffer of at least `bytes` (grown geometrically).
     int buffer(const char* name, size_t bytes, void** out);
+    // Whether the cached buffer `name` is still the allocation `ptr` was taken from (a release or a regrowth ends that).
+    bool holds(const char* name, const void* ptr) const;
     // Frees the cached buffers whose name `match` accepts; returns the bytes given back.
     int64_t release_matching(const std::function<bool(const std::string&)>& match);
     void release();

@@ -9,7 +9,7 @@
 // (the head and the tail).  A tile finds its first and last record by binary search in the n + 1 record offsets, a lane
 // searches only between those two.  walk_out_tiles is that walk; a kernel says what a piece is.
 //
-// Everything here has internal linkage (anonymous namespace), as in text_lines.hpp.
+// Everything here has internal linkage (anonymous namespace): every file that includes it gets its own copy.
 #pragma once
 
 #include "common.hpp"

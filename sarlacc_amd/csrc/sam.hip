@@ -4,7 +4,7 @@
 // (:49-53, :65-74, .get_clip_length :80-95).  Here the body text (everything after the header, which the caller
 // reads) is copied to HBM once and parsed there:
 //
-//   k_fq_count / k_fq_lines   line index (text_lines.hpp, shared with the FASTQ parser)
+//   (the line index: k_fq_count, scan, k_fq_lines of text_lines.hip, shared with the FASTQ parser)
 //   k_sam_fields   one wavefront per line: the first six tabs by ballots over 64-byte windows, FLAG / MAPQ / POS,
 //                  RNAME looked up in a hash table of the @SQ names + '*' + the `restricted` names, the keep
 //                  decision, and on kept lines the CIGAR: every lane that holds an op letter reads its digits
@@ -16,52 +16,15 @@
 // A malformed line is reported as k_fq_records does it: atomicMin on (line << 4 | code), read by the host after the
 // launch.  No device assert or trap: a bad file is an error return, never a GPU fault.
 // Streaming byte work, HBM-bound: 2 reads of the text by the line passes + the fields up to the end of the CIGAR.
-#include "common.hpp"
+// The host side -- the entry points, the name table, the keep / scan back end that bam.hip's records share, the
+// messages of the codes (readers.hpp) -- is in readers_host.cpp; the two functions at the end only enqueue.
 #include "devprim.hpp"
-#include "sam_rec.hpp"
-#include "text_lines.hpp"
-
-#include "../../include/sarlacc_amd.h"
+#include "readers.hpp"
 
 #include <algorithm>
 #include <climits>
-#include <string>
-#include <vector>
 
 namespace sarlacc {
-
-// status codes of a line, in the order the checks run (one code per line; the first bad line wins)
-enum {
-    SAM_FIELDS = 1,        // non-blank line with fewer than 6 tab-separated fields
-    SAM_FLAG = 2,          // FLAG not an optionally signed decimal int32
-    SAM_MAPQ = 3,          // MAPQ likewise
-    SAM_POS = 4,           // kept line: POS likewise
-    SAM_RNAME = 5,         // kept line: RNAME neither an @SQ name nor '*'
-    SAM_CIGAR_STAR = 6,    // kept line: CIGAR '*'
-    SAM_CIGAR_SYNTAX = 7,  // kept line: CIGAR not ([0-9]+[MIDNSHP=X])+
-    SAM_CIGAR_RANGE = 8,   // kept line: an op length, the width or a clip above 2^31 - 1
-    SAM_CIGAR_CLIPS = 9,   // kept line: only H / S ops (the reference's right clip is NA)
-    SAM_END = 10,          // kept line: start + width - 1 outside the int32 range
-};
-
-// one slot of the open-addressing table of reference names (len < 0: empty)
-struct SamName {
-    unsigned long long hash;
-    long long off;      // into the name bytes
-    int len;
-    int code;           // seqinfo index, -1 for a `restricted` name that is not in the header
-    int restricted;     // listed in `restricted`
-    int pad;
-};
-
-__host__ __device__ __forceinline__ unsigned long long fnv1a64(const uint8_t* s, long long n) {
-    unsigned long long h = 14695981039346656037ull;
-    for (long long i = 0; i < n; ++i) {
-        h ^= s[i];
-        h *= 1099511628211ull;
-    }
-    return h;
-}
 
 // optionally signed decimal integer of at most 2^31 - 1 in magnitude (R's NA_integer_ is -2^31)
 __device__ bool parse_i32(const uint8_t* s, long long n, int* out) {
@@ -289,154 +252,27 @@ __global__ void __launch_bounds__(SAM_THREADS) k_sam_scatter(const uint8_t* text
     }
 }
 
-thread_local SamIndex g_sam;   // (sam_rec.hpp; sarlacc_dev_bam_index of bam.hip fills it too)
+// one wavefront per line, up to 256 workgroups per CU
+static unsigned sam_grid(long long nlines) {
+    return static_cast<unsigned>(std::min<long long>(nblk(nlines, SAM_THREADS / 64), static_cast<long long>(ctx().num_cu) * 256));
+}
+
+int sam_fields(const uint8_t* text, const long long* line_start, long long nlines, const SamName* table, unsigned long long tmask,
+               const uint8_t* names, int use_restricted, int use_minq, long long minq, SamRec* rec, int* keep,
+               long long* name_len, unsigned long long* first_bad, hipStream_t s) {
+    hipLaunchKernelGGL(k_sam_fields, dim3(sam_grid(nlines)), dim3(SAM_THREADS), 0, s, text, line_start, nlines, table, tmask, names,
+                       use_restricted, use_minq, minq, rec, keep, name_len, first_bad);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
+
+int sam_scatter(const uint8_t* text, const SamRec* rec, const int* keep, const int64_t* koff, const int64_t* noff, long long nlines,
+                int32_t* ref, int32_t* start, int32_t* width, uint8_t* strand, int32_t* lclip, int32_t* rclip, uint8_t* names,
+                int64_t* name_off, hipStream_t s) {
+    hipLaunchKernelGGL(k_sam_scatter, dim3(sam_grid(nlines)), dim3(SAM_THREADS), 0, s, text, rec, keep, koff, noff, nlines, ref,
+                       start, width, strand, lclip, rclip, names, name_off);
+    SL_HIP(hipGetLastError());
+    return 0;
+}
 
 }  // namespace sarlacc
-
-using namespace sarlacc;
-
-extern "C" {
-
-int sarlacc_dev_sam_index(const uint8_t* d_text, int64_t nbytes, int64_t first_line, const char* ref_names,
-                          const int64_t* ref_off, int64_t n_ref, const uint8_t* restricted_mask, const char* extra_names,
-                          const int64_t* extra_off, int64_t n_extra, int use_minq, int64_t minq, int64_t* n_lines,
-                          int64_t* n_kept, int64_t* kept_name_bytes, void* stream) {
-    SL_TRY(ensure_device());
-    if (nbytes < 0 || n_ref < 0 || n_extra < 0) return fail("sarlacc_amd: negative SAM size");
-    if (n_ref >= INT_MAX) return fail("sarlacc_amd: too many reference names");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    g_sam = SamIndex{};
-    *n_lines = 0; *n_kept = 0; *kept_name_bytes = 0;
-
-    // the name table: seqinfo names (code = index), then the `restricted` names not among them (code -1)
-    const int64_t nent = n_ref + n_extra;
-    uint64_t tsize = 16;
-    while (tsize < 2 * static_cast<uint64_t>(nent) + 2) tsize <<= 1;
-    std::vector<SamName> table(tsize, SamName{0, 0, -1, 0, 0, 0});
-    std::vector<uint8_t> bytes;
-    const uint64_t tmask = tsize - 1;
-    for (int64_t i = 0; i < nent; ++i) {
-        const bool is_ref = i < n_ref;
-        const int64_t j = is_ref ? i : i - n_ref;
-        const int64_t* off = is_ref ? ref_off : extra_off;
-        const uint8_t* src = reinterpret_cast<const uint8_t*>((is_ref ? ref_names : extra_names) + off[j]);
-        const int64_t len = off[j + 1] - off[j];
-        if (len < 0 || len >= INT_MAX) return fail("sarlacc_amd: bad reference name offsets");
-        const unsigned long long h = fnv1a64(src, len);
-        uint64_t slot = h & tmask;
-        bool dup = false;
-        for (; table[slot].len >= 0; slot = (slot + 1) & tmask) {
-            const SamName& E = table[slot];
-            if (E.hash == h && E.len == len && std::equal(src, src + len, bytes.data() + E.off)) { dup = true; break; }
-        }
-        if (dup) {
-            if (is_ref) return fail("duplicate @SQ name '%.*s'", static_cast<int>(std::min<int64_t>(len, 200)), src);
-            continue;   // a restricted name listed twice, or one that is also a seqinfo name
-        }
-        table[slot] = SamName{h, static_cast<long long>(bytes.size()), static_cast<int>(len), is_ref ? static_cast<int>(i) : -1,
-                              is_ref ? (restricted_mask ? restricted_mask[i] != 0 : 0) : 1, 0};
-        bytes.insert(bytes.end(), src, src + len);
-    }
-    if (nbytes == 0) {
-        g_sam.text = d_text;   // no lines: an empty result
-        return 0;
-    }
-
-    // line index, as the FASTQ parser builds it
-    const long long ntiles = (nbytes + FQ_TILE - 1) / FQ_TILE;
-    long long* d_count; long long* d_base;
-    SL_TRY(scratch("fq.count", static_cast<size_t>(ntiles) + 1, &d_count));
-    SL_TRY(scratch("fq.base", static_cast<size_t>(ntiles) + 1, &d_base));
-    SL_HIP(hipMemsetAsync(d_count + ntiles, 0, sizeof(long long), s));
-    hipLaunchKernelGGL(k_fq_count, dim3(static_cast<unsigned>(ntiles)), dim3(FQ_THREADS), 0, s, d_text, static_cast<long long>(nbytes), d_count);
-    SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan("fq.scan", d_count, reinterpret_cast<int64_t*>(d_base), static_cast<size_t>(ntiles) + 1, s));
-    long long newlines = 0;
-    uint8_t last = 0;
-    SL_HIP(hipMemcpyAsync(&newlines, d_base + ntiles, sizeof newlines, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipMemcpyAsync(&last, d_text + nbytes - 1, 1, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipStreamSynchronize(s));
-    // one more line than newlines; after a final newline that line is empty, i.e. blank
-    const long long nlines = newlines + 1;
-
-    long long* d_lines; SamName* d_table; uint8_t* d_names;
-    SL_TRY(scratch("sam.lines", static_cast<size_t>(nlines) + 1, &d_lines));
-    const long long zero = 0, end = nbytes + 1;
-    SL_HIP(hipMemcpyAsync(d_lines, &zero, sizeof zero, hipMemcpyHostToDevice, s));
-    SL_HIP(hipMemcpyAsync(d_lines + nlines, &end, sizeof end, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fq_lines, dim3(static_cast<unsigned>(ntiles)), dim3(FQ_THREADS), 0, s, d_text, static_cast<long long>(nbytes), d_base, d_lines);
-    SL_HIP(hipGetLastError());
-    SL_TRY(upload("sam.table", table.data(), table.size(), &d_table, s));
-    SL_TRY(upload("sam.names", bytes.data(), bytes.size(), &d_names, s));
-
-    SamRec* d_rec; int* d_keep; long long* d_nlen; int64_t* d_koff; int64_t* d_noff; unsigned long long* d_bad;
-    SL_TRY(scratch("sam.rec", static_cast<size_t>(nlines), &d_rec));
-    SL_TRY(scratch("sam.keep", static_cast<size_t>(nlines) + 1, &d_keep));
-    SL_TRY(scratch("sam.nlen", static_cast<size_t>(nlines) + 1, &d_nlen));
-    SL_TRY(scratch("sam.koff", static_cast<size_t>(nlines) + 1, &d_koff));
-    SL_TRY(scratch("sam.noff", static_cast<size_t>(nlines) + 1, &d_noff));
-    SL_TRY(scratch("sam.bad", 1, &d_bad));
-    SL_HIP(hipMemsetAsync(d_bad, 0xff, sizeof(unsigned long long), s));
-    SL_HIP(hipMemsetAsync(d_keep + nlines, 0, sizeof(int), s));
-    SL_HIP(hipMemsetAsync(d_nlen + nlines, 0, sizeof(long long), s));
-    Context& c = ctx();
-    const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nlines, SAM_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
-    hipLaunchKernelGGL(k_sam_fields, dim3(grid), dim3(SAM_THREADS), 0, s, d_text, d_lines, nlines, d_table,
-                       static_cast<unsigned long long>(tmask), d_names, restricted_mask ? 1 : 0, use_minq ? 1 : 0,
-                       static_cast<long long>(minq), d_rec, d_keep, d_nlen, d_bad);
-    SL_HIP(hipGetLastError());
-    SL_TRY(exclusive_scan("sam.scan", d_keep, d_koff, static_cast<size_t>(nlines) + 1, s));
-    SL_TRY(exclusive_scan("sam.scan", d_nlen, d_noff, static_cast<size_t>(nlines) + 1, s));
-    unsigned long long bad = 0;
-    int64_t nk = 0, nb = 0;
-    SL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipMemcpyAsync(&nk, d_koff + nlines, sizeof nk, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipMemcpyAsync(&nb, d_noff + nlines, sizeof nb, hipMemcpyDeviceToHost, s));
-    SL_HIP(hipStreamSynchronize(s));
-    if (bad != ~0ull) {
-        const long long line = first_line + static_cast<long long>(bad >> 4);
-        switch (bad & 15u) {
-            case SAM_FIELDS: return fail("SAM line %lld: fewer than 6 tab-separated fields", line);
-            case SAM_FLAG: return fail("SAM line %lld: FLAG is not a 32-bit integer", line);
-            case SAM_MAPQ: return fail("SAM line %lld: MAPQ is not a 32-bit integer", line);
-            case SAM_POS: return fail("SAM line %lld: POS is not a 32-bit integer", line);
-            case SAM_RNAME: return fail("SAM line %lld: RNAME is neither an @SQ name nor '*'", line);
-            case SAM_CIGAR_STAR: return fail("SAM line %lld: CIGAR '*' on a kept record", line);
-            case SAM_CIGAR_SYNTAX: return fail("SAM line %lld: CIGAR does not match ([0-9]+[MIDNSHP=X])+", line);
-            case SAM_CIGAR_RANGE: return fail("SAM line %lld: CIGAR length above 2^31 - 1", line);
-            case SAM_CIGAR_CLIPS: return fail("SAM line %lld: CIGAR has only H and S operations", line);
-            default: return fail("SAM line %lld: alignment end outside the 32-bit integer range", line);
-        }
-    }
-    g_sam.text = d_text; g_sam.nlines = nlines; g_sam.nkept = nk; g_sam.name_bytes = nb;
-    *n_lines = newlines + (last != '\n' ? 1 : 0);
-    *n_kept = nk; *kept_name_bytes = nb;
-    return 0;
-}
-
-int sarlacc_dev_sam_extract(const uint8_t* d_text, int32_t* d_ref, int32_t* d_start, int32_t* d_width, uint8_t* d_strand,
-                            int32_t* d_lclip, int32_t* d_rclip, uint8_t* d_names, int64_t* d_name_off, void* stream) {
-    SL_TRY(ensure_device());
-    if (!d_text || d_text != g_sam.text) return fail("sarlacc_amd: sarlacc_dev_sam_extract without a matching sarlacc_dev_sam_index");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t nlines = g_sam.nlines, nk = g_sam.nkept, nb = g_sam.name_bytes;
-    SL_HIP(hipMemcpyAsync(d_name_off + nk, &nb, sizeof nb, hipMemcpyHostToDevice, s));
-    if (nk > 0) {
-        SamRec* d_rec; int* d_keep; int64_t* d_koff; int64_t* d_noff;
-        SL_TRY(scratch("sam.rec", static_cast<size_t>(nlines), &d_rec));
-        SL_TRY(scratch("sam.keep", static_cast<size_t>(nlines) + 1, &d_keep));
-        SL_TRY(scratch("sam.koff", static_cast<size_t>(nlines) + 1, &d_koff));
-        SL_TRY(scratch("sam.noff", static_cast<size_t>(nlines) + 1, &d_noff));
-        Context& c = ctx();
-        const unsigned grid = static_cast<unsigned>(std::min<long long>(nblk(nlines, SAM_THREADS / 64), static_cast<long long>(c.num_cu) * 256));
-        c.stage_reset("sam_scatter");
-        SL_TRY(c.stage_begin("sam_scatter", s));
-        hipLaunchKernelGGL(k_sam_scatter, dim3(grid), dim3(SAM_THREADS), 0, s, d_text, d_rec, d_keep, d_koff, d_noff,
-                           static_cast<long long>(nlines), d_ref, d_start, d_width, d_strand, d_lclip, d_rclip, d_names, d_name_off);
-        SL_HIP(hipGetLastError());
-        SL_TRY(c.stage_end("sam_scatter", s));
-    }
-    SL_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-}
