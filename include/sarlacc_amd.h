@@ -471,7 +471,7 @@ int sarlacc_dev_labels_csr(const int32_t* d_label, int64_t n, int64_t* d_group_o
                            int64_t* n_members, void* stream);
 
 /* Reference-free pre-groups of a read batch from k-mer sketches (generics.sequenceGroups; csrc/sketch.hip; the rules are
- * DESIGN.md §4.19).  Three calls on data already in device memory, each usable alone; labels go to CSR groups by
+ * DESIGN.md §4.19).  Four calls on data already in device memory, each usable alone; labels go to CSR groups by
  * sarlacc_dev_labels_csr.  Every result is exact and the same from run to run: no value depends on the order in which
  * atomics arrive.  All calls return when the device has finished.
  * sarlacc_dev_sketch_reads: the one-permutation MinHash sketch of every read.  d_seq / d_off are the bases and the n + 1
@@ -490,11 +490,26 @@ int sarlacc_dev_labels_csr(const int32_t* d_label, int64_t n, int64_t* d_group_o
  * sarlacc_dev_components: the connected components of n vertices under n_links links (a << 32 | b, any order, repeats
  * allowed).  d_nkmers (n entries; may be NULL: every vertex counts) marks with a value <= 0 the vertices that are in no
  * group: they get label -1 and their links are ignored.  d_label[v] numbers the components from 0 in ascending order of
- * their lowest vertex; *n_groups (may be NULL) is their number.  "link K: an end outside 0 .. n - 1". */
+ * their lowest vertex; *n_groups (may be NULL) is their number.  "link K: an end outside 0 .. n - 1".
+ * sarlacc_dev_links_verify (optional, between the links and the components; DESIGN §4.19 rule 6a): every link a -- b
+ * (a << 32 | b, 0 <= a < b < n, n_links of them) is checked by an alignment of its two reads, of la and lb bytes.  Two bytes
+ * match when they are the same upper-case A, C, G or T; every other byte matches nothing, itself included.  D_w is the
+ * unit-cost edit distance over the cells |j - i| <= w = bandwidth (0 .. 127) of the matrix, infinite for |la - lb| > w; it
+ * is the edit distance whenever that is <= w.  The bound of a pair is t = max_diff_ppm (0 .. 999999) * max(la, lb) div
+ * 10^6 in 64-bit integers.  The link passes with strand 0 and dist D_w(a, b) when that is <= t; otherwise, and only with
+ * both_strands != 0, with strand 1 and dist D_w(a, rc(b)) when that is <= t (rc reverses b and swaps A with T and C with
+ * G); otherwise it fails with dist -1 and strand 0.  d_dist and d_strand (may be NULL) have n_links entries in the order
+ * of the links; d_kept (may be NULL; room for n_links entries) gets the passing links in that same order, *n_kept (host;
+ * may be NULL) their number.  n_links = 0 launches nothing.  No byte outside the two reads of a link is read.  "link K:
+ * its ends are not 0 <= a < b < n", "read K: its offsets do not ascend inside the sequence buffer, or it has 2^31 bases
+ * or more": nothing that rests on such a link is launched, and d_kept is not written. */
 int sarlacc_dev_sketch_reads(const uint8_t* d_seq, const int64_t* d_off, int64_t n, int k, int buckets, int canonical,
                              uint64_t* d_sketch, int32_t* d_nkmers, void* stream);
 int sarlacc_dev_sketch_links(const uint64_t* d_sketch, int64_t n, int buckets, int window, int min_shared, uint64_t* d_links,
                              int64_t capacity, int64_t* n_pairs, int64_t* n_links, void* stream);
+int sarlacc_dev_links_verify(const uint8_t* d_seq, const int64_t* d_off, int64_t n, const uint64_t* d_links, int64_t n_links,
+                             int bandwidth, int64_t max_diff_ppm, int both_strands, int32_t* d_dist, uint8_t* d_strand,
+                             uint64_t* d_kept, int64_t* n_kept, void* stream);
 int sarlacc_dev_components(const uint64_t* d_links, int64_t n_links, int64_t n, const int32_t* d_nkmers, int32_t* d_label,
                            int64_t* n_groups, void* stream);
 

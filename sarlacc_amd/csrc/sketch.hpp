@@ -1,5 +1,5 @@
-// sketch.hpp -- what sketch.hip (the kernels and the functions that launch them) and sketch_host.cpp (argument checks,
-// scratch, the rocPRIM sorts and scans between the launches, results and errors, the C entry points) share.
+// sketch.hpp -- what sketch.hip and links_verify.hip (the kernels and the functions that launch them) and sketch_host.cpp
+// (argument checks, scratch, the rocPRIM sorts and scans between the launches, results and errors, the C entry points) share.
 #pragma once
 
 #include "common.hpp"
@@ -17,6 +17,8 @@ struct SkState {
     unsigned long long n_pairs;       // distinct candidate pairs
     unsigned long long n_links, n_groups;
     unsigned int changed;             // a hook round moved a root
+    unsigned long long n_kept;        // links that passed the alignment check
+    unsigned long long n_second;      // pairs whose reverse orientation was computed
 };
 
 struct SketchArgs {
@@ -24,6 +26,18 @@ struct SketchArgs {
     const int64_t* off;
     long long n;
     int k, log2_buckets, canonical;
+};
+
+// a launch of the alignment check (rule 6a): w the bandwidth, 0 .. 127
+struct VerifyArgs {
+    const uint8_t* seq;
+    const int64_t* off;
+    long long n;
+    const uint64_t* links;
+    long long n_links;
+    int w;
+    long long max_diff_ppm;
+    int both_strands;
 };
 
 // ---- sketch.hip ----
@@ -54,5 +68,14 @@ int launch_cc_jump(long long n, int32_t* parent, hipStream_t s);
 int launch_cc_heads(const int32_t* parent, const int32_t* nkmers, long long n, int32_t* head, hipStream_t s);
 int launch_cc_labels(const int32_t* parent, const int32_t* nkmers, long long n, const int32_t* before, int32_t* label, SkState* st,
                      hipStream_t s);
+
+// ---- links_verify.hip ----
+// Per link (n_links > 0): dist (-1: the link fails), strand (may be null), flag[p] (n_links + 1 entries, flag[n_links] = 0)
+// marks a link that passes; the lowest link with ends outside 0 <= a < b < n goes to st->bad_link, the lowest read with
+// bad offsets to st->bad_off (such links fail), the pairs whose second strand was computed are counted into st->n_second.
+int launch_links_verify(const VerifyArgs& a, int32_t* dist, uint8_t* strand, int32_t* flag, SkState* st, hipStream_t s);
+// kept[before[p]] = links[p] for the flagged p (kept may be null); st->n_kept = before[n_links]
+int launch_links_keep(const uint64_t* links, long long n_links, const int32_t* flag, const int64_t* before, uint64_t* kept, SkState* st,
+                      hipStream_t s);
 
 }  // namespace sarlacc

@@ -1,11 +1,14 @@
-// sketch_host.cpp -- host side of sketch.hip: argument checks, scratch, the rocPRIM sorts and scans between the launches,
-// results, errors and the three C entry points (include/sarlacc_amd.h "reference-free pre-groups of a read batch").
+// sketch_host.cpp -- host side of sketch.hip and links_verify.hip: argument checks, scratch, the rocPRIM sorts and scans
+// between the launches, results, errors and the four C entry points (include/sarlacc_amd.h "reference-free pre-groups of
+// a read batch").
 //
 // Stage timers (sarlacc_stage_ms): sketch_reads, sketch_entries_sort, sketch_pairs, sketch_pairs_sort, sketch_select,
-// components.  Counter (sarlacc_stage_count): components_rounds.
+// sketch_verify, components.  Counters (sarlacc_stage_count): components_rounds, sketch_verify_pairs (links looked at),
+// sketch_verify_second_strand (pairs whose reverse orientation was computed); the two are 0 after sarlacc_dev_sketch_links.
 #include "sketch.hpp"
 
 #include "devprim.hpp"
+#include "links_verify_core.hpp"
 
 #include "../../include/sarlacc_amd.h"
 
@@ -86,6 +89,8 @@ int sarlacc_dev_sketch_links(const uint64_t* d_sketch, int64_t n, int buckets, i
     if (m >= SK_LIMIT) return fail("sarlacc_amd: %lld sketch entries (reads x buckets): at most 2^31 - 1 in a call", m);
     if (n_pairs) *n_pairs = 0;
     if (n_links) *n_links = 0;
+    ctx().counts["sketch_verify_pairs"] = 0;      // new links: none of them verified yet
+    ctx().counts["sketch_verify_second_strand"] = 0;
     if (n < 2) return 0;
     SL_TRY(ensure_device());
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -133,6 +138,49 @@ int sarlacc_dev_sketch_links(const uint64_t* d_sketch, int64_t n, int buckets, i
     SL_TRY(state_fetch(d_state, &st, s));
     if (n_pairs) *n_pairs = static_cast<int64_t>(st.n_pairs);
     if (n_links) *n_links = static_cast<int64_t>(st.n_links);
+    return 0;
+}
+
+int sarlacc_dev_links_verify(const uint8_t* d_seq, const int64_t* d_off, int64_t n, const uint64_t* d_links, int64_t n_links,
+                             int bandwidth, int64_t max_diff_ppm, int both_strands, int32_t* d_dist, uint8_t* d_strand,
+                             uint64_t* d_kept, int64_t* n_kept, void* stream) {
+    SL_TRY(count_ok(n, "reads"));
+    SL_TRY(count_ok(n_links, "links"));
+    if (bandwidth < 0 || bandwidth > LV_MAX_BANDWIDTH) return fail("sarlacc_amd: 'bandwidth' lies in 0 .. %d", LV_MAX_BANDWIDTH);
+    if (max_diff_ppm < 0 || max_diff_ppm >= LV_PPM) return fail("sarlacc_amd: 'max_diff_ppm' lies in 0 .. 999999");
+    if (n_kept) *n_kept = 0;
+    Context& c = ctx();
+    c.counts["sketch_verify_pairs"] = 0;
+    c.counts["sketch_verify_second_strand"] = 0;
+    if (n_links == 0) return 0;
+    SL_TRY(ensure_device());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t count = static_cast<size_t>(n_links);
+    SkState* d_state;
+    int32_t* d_flag;
+    int64_t* d_before;
+    SL_TRY(state_begin(&d_state, s));
+    SL_TRY(scratch("sk.flag", count + 1, &d_flag));
+    SL_TRY(scratch("sk.before", count + 1, &d_before));
+    const VerifyArgs a{d_seq, d_off, n, d_links, n_links, bandwidth, max_diff_ppm, both_strands ? 1 : 0};
+    SkState st;
+    // the stage in two segments: nothing that rests on a refused link or read is launched
+    c.stage_reset("sketch_verify");
+    SL_TRY(c.stage_begin("sketch_verify", s));
+    SL_TRY(launch_links_verify(a, d_dist, d_strand, d_flag, d_state, s));
+    SL_TRY(c.stage_end("sketch_verify", s));
+    SL_TRY(state_fetch(d_state, &st, s));
+    if (st.bad_link != ~0ull) return fail("link %lld: its ends are not 0 <= a < b < n", static_cast<long long>(st.bad_link) + 1);
+    if (st.bad_off != ~0ull)
+        return fail("read %lld: its offsets do not ascend inside the sequence buffer, or it has 2^31 bases or more", static_cast<long long>(st.bad_off) + 1);
+    SL_TRY(c.stage_begin("sketch_verify", s));
+    SL_TRY(exclusive_scan("sk.scan", d_flag, d_before, count + 1, s));
+    SL_TRY(launch_links_keep(d_links, n_links, d_flag, d_before, d_kept, d_state, s));
+    SL_TRY(c.stage_end("sketch_verify", s));
+    SL_TRY(state_fetch(d_state, &st, s));
+    c.counts["sketch_verify_pairs"] = static_cast<double>(n_links);
+    c.counts["sketch_verify_second_strand"] = static_cast<double>(st.n_second);
+    if (n_kept) *n_kept = static_cast<int64_t>(st.n_kept);
     return 0;
 }
 

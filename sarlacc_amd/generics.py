@@ -837,7 +837,7 @@ def readGroups(ranges, reads, by="reference", maxgap=0, ignore_strand=True):
 # ---------------------------------------------------------------------------
 # sequenceGroups: the pre-groups of umiGroup(groups=) without a mapping (vignettes/correction.Rmd)
 
-def sequenceGroups(reads, k=13, buckets=64, window=8, min_shared=3, canonical=True):
+def sequenceGroups(reads, k=13, buckets=64, window=8, min_shared=3, canonical=True, identity=None, bandwidth=100):
     """The `pre.groups` of the reference's correction vignette by its second route -- "cluster reads together using
     software like vsearch" -- without a reference and without leaving the device.  vsearch is not restated; the stage
     follows a specification of its own.  `reads` is a resident.DeviceReads (used where it lies) or a
@@ -860,10 +860,26 @@ def sequenceGroups(reads, k=13, buckets=64, window=8, min_shared=3, canonical=Tr
     one group; min_shared = 4 (0.05 % of the groups mixed) or k = 16 (0.4 %, in under half of the time, since far fewer
     candidate pairs arise) are the better choice there.  At twice the error rate no setting tried was clean at that
     scale: longer k-mers do not survive the errors, shorter ones collide.
+    `identity` (None, or a number in (0, 1]) adds what vsearch's `-id` stands for: every link is checked by an
+    alignment of its two reads before the components are formed (DESIGN.md §4.19 rule 6a), so the sketch only proposes
+    and the reads themselves decide.  Use it where k-mers recur between molecules -- large batches, transcripts that
+    share exons or tails, noisy reads: lower `min_shared` to 1 or 2 for sensitivity and let the alignment decide.  A
+    link a -- b of reads of la and lb bytes stays when the unit-cost edit distance of the two (upper-case A, C, G, T
+    match themselves, every other byte matches nothing) is at most (max_diff_ppm * max(la, lb)) // 10^6 with
+    max_diff_ppm = int(round((1 - identity) * 10^6)), for b as it stands or, with `canonical`, reverse-complemented
+    (forward is tried first).  The distance is computed inside the band |j - i| <= `bandwidth` (0 .. 127; the default
+    100 is multiReadAlign's) and is infinite when the lengths differ by more; whenever the true distance is at most
+    `bandwidth` the banded one equals it, since a path of cost d never leaves the diagonals within d of the main one.
+    A read whose links all fail is a group of one.  This is not vsearch's identity definition and no parity is
+    claimed; two consequences: the distance is global, so a read truncated by more than the bound does not link to
+    its full-length sibling; and two noisy copies differ by about twice the per-read error rate, so 0.8 suits reads at
+    about 5 % error each, while at 10 % + 2 % per read the identity of two copies is about 0.77.
     Returns a dict in the reads' order, shaped as readGroups returns it: "group" (int32 labels), "groups" (the CSR pair
     (off int64[G + 1], members int32, 1-based, ascending) that calls.umi_group_flat takes;
     strset.lists_from_csr(*out["groups"]) is the list umiGroup(groups=) takes), "n.kmers" (int32), "n.pairs" (int64:
-    distinct candidate pairs) and "n.links" (int64).  Every result is exact and the same from run to run.  Bad
-    arguments raise ValueError before a device is touched; no reads return the empty result without one."""
+    distinct candidate pairs) and "n.links" (int64: the sketch's links); with `identity` also "n.verified" (int64: the
+    links that passed).  Every result is exact and the same from run to run.  Bad arguments raise ValueError before a
+    device is touched; no reads return the empty result without one."""
     from .sketch import sequence_groups
-    return sequence_groups(reads, k=k, buckets=buckets, window=window, min_shared=min_shared, canonical=canonical)
+    return sequence_groups(reads, k=k, buckets=buckets, window=window, min_shared=min_shared, canonical=canonical,
+                           identity=identity, bandwidth=bandwidth)

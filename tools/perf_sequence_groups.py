@@ -15,6 +15,21 @@ generated in HBM, in transcript order, all on one strand.
            group, candidate pairs, links, rounds of the component kernels.
 
     python tools/perf_sequence_groups.py [--molecules 100000] [--copies 10] [--length 2000] [--out profiles/sequence_groups.txt]
+
+With --verify the alignment check of the links (identity=, DESIGN §4.19 rule 6a) is measured instead, into
+profiles/sequence_groups_verify.txt, on the same reads at both error rates:
+
+  v lines  for min_shared 3, 2 and 1 with identity 0.8 and 0.7 (k = 13, bandwidth 100): n.links, n.verified, the pairs
+           whose second strand was computed, the stage timer sketch_verify (HIP events, best of --repeats), links per
+           second, band cells per second -- the (2 w + 1) x |b| cells of the links that PASS alone, a lower bound of the
+           work: a failing link stops early and is not counted --, the whole call, and the two quality shares of the q
+           lines.  A setting whose first call takes more than --slow seconds is not repeated.
+  p lines  identity=None, whole call and stage timers, of the package under --root DIR (default: this tree), appended to
+           --out: how a parent commit is held beside this one, like for like:
+
+    python tools/perf_sequence_groups.py --verify
+    python tools/perf_sequence_groups.py --verify --root . --label "this tree"
+    python tools/perf_sequence_groups.py --verify --root ../parent --label "parent commit"
 """
 import argparse
 import os
@@ -24,7 +39,6 @@ import time
 import numpy as np
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, HERE)
 STAGES = ("sketch_reads", "sketch_entries_sort", "sketch_pairs", "sketch_pairs_sort", "sketch_select", "components", "labels_csr")
 
 
@@ -52,14 +66,90 @@ def quality(group, copies):
     return per_group.size, float((per_transcript > 1).mean()), float((per_group > 1).mean()), int((~kept).sum())
 
 
+def verify_lines(args, out):
+    """The v lines."""
+    import torch
+
+    from sarlacc_amd import _lib, devsynth, generics, sketch
+    bandwidth = 100
+    say(out, "tools/perf_sequence_groups.py --verify --molecules %d --copies %d --length %d --repeats %d" % (args.molecules, args.copies, args.length, args.repeats))
+    for scale in (1, 2):
+        sub, indel = 0.05 * scale, 0.01 * scale
+        sim = devsynth.make_molecule_reads(args.molecules, args.copies, args.length, 1000 + scale, torch.device("cuda:0"), sub_rate=sub, indel_rate=indel)
+        dev = resident(sim)
+        lengths = np.diff(dev.off_host)
+        say(out, "%d reads of %d transcripts, %.1f MB of bases, %.0f %% substitutions + %.0f %% indel events" % (len(dev), args.molecules, dev.total / 1e6, 100 * sub, 100 * indel))
+        for min_shared in (3, 2, 1):
+            for identity in (0.8, 0.7):
+                walls, stage = [], []
+                for _ in range(args.repeats):
+                    t0 = time.perf_counter()
+                    res = generics.sequenceGroups(dev, min_shared=min_shared, identity=identity, bandwidth=bandwidth)
+                    walls.append((time.perf_counter() - t0) * 1e3)
+                    stage.append(_lib.stage_ms("sketch_verify"))
+                    if walls[0] > 1e3 * args.slow:
+                        break
+                second = int(_lib.stage_count("sketch_verify_second_strand"))
+                assert int(_lib.stage_count("sketch_verify_pairs")) == int(res["n.links"])
+                # the passing links once more, for the cells they stand for
+                d_sketch, _ = sketch.sketch_reads(dev.seq, dev.off, len(dev), 13, 64, True)
+                d_links, _, nlinks = sketch.sketch_links(d_sketch, len(dev), 64, 8, min_shared)
+                d_kept, nkept, _, _ = sketch.verify_links(dev.seq, dev.off, len(dev), d_links, nlinks, identity, bandwidth)
+                assert nkept == int(res["n.verified"]) and nlinks == int(res["n.links"])
+                second_reads = (d_kept.to_numpy(np.uint64, nkept) & np.uint64(0xffffffff)).astype(np.int64)
+                cells = float(lengths[second_reads].sum()) * (2 * bandwidth + 1)
+                del d_sketch, d_links, d_kept, second_reads
+                groups, split, mixed, none = quality(res["group"], args.copies)
+                ms = min(stage)
+                say(out, "v min_shared %d, identity %.1f: %d links, %d verified, %d second strands, sketch_verify %.3f ms (best of %d; %s), %.1f M links/s, "
+                    "%.2f T band cells/s, whole call %.1f ms (best of %d), %d groups, transcripts in several groups %.4f, groups with several transcripts %.4f"
+                    % (min_shared, identity, nlinks, nkept, second, ms, len(stage), " ".join("%.3f" % v for v in stage), nlinks / ms / 1e3,
+                       cells / ms / 1e9, min(walls), len(walls), groups, split, mixed))
+        del dev, sim
+        torch.cuda.empty_cache()
+
+
+def parent_lines(args, out):
+    """The p lines: identity=None of the package under --root."""
+    import torch
+
+    from sarlacc_amd import _lib, devsynth, generics
+    label = args.label or os.path.basename(os.path.abspath(args.root))
+    sim = devsynth.make_molecule_reads(args.molecules, args.copies, args.length, 1001, torch.device("cuda:0"), sub_rate=0.05, indel_rate=0.01)
+    dev = resident(sim)
+    stage, walls = {s: [] for s in STAGES}, []
+    generics.sequenceGroups(dev)
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        res = generics.sequenceGroups(dev)
+        walls.append((time.perf_counter() - t0) * 1e3)
+        for s in STAGES:
+            stage[s].append(_lib.stage_ms(s))
+    say(out, "p [%s] identity=None on %d reads: whole call %s ms (best %.1f); %s; all stages %.3f ms; %d links, keys %s, sketch_verify_pairs %d"
+        % (label, len(dev), " ".join("%.1f" % v for v in walls), min(walls), ", ".join("%s %.3f" % (s, min(stage[s])) for s in STAGES),
+           sum(min(stage[s]) for s in STAGES), int(res["n.links"]), " ".join(sorted(res)), int(_lib.stage_count("sketch_verify_pairs"))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--molecules", type=int, default=100000)
     ap.add_argument("--copies", type=int, default=10)
     ap.add_argument("--length", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "sequence_groups.txt"))
+    ap.add_argument("--out")
+    ap.add_argument("--verify", action="store_true", help="measure the alignment check of the links (v lines)")
+    ap.add_argument("--slow", type=float, default=20.0, help="--verify: seconds above which a setting is run once only")
+    ap.add_argument("--root", help="--verify: the p lines of the package of this checkout, appended to --out")
+    ap.add_argument("--label", help="what the p lines call that checkout (default: its directory's name)")
     args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root) if args.root else HERE)
+    if args.out is None:
+        args.out = os.path.join(HERE, "profiles", "sequence_groups_verify.txt" if args.verify else "sequence_groups.txt")
+    if args.verify:
+        if args.root:
+            return parent_lines(args, args.out)
+        open(args.out, "w").close()
+        return verify_lines(args, args.out)
     import torch
 
     from sarlacc_amd import _lib, devsynth, generics
