@@ -73,6 +73,10 @@ double sarlacc_stage_count(const char* name);
 /* Duration in ms of the DP kernel launches recorded by the last
  * sarlacc_dev_* align call (HIP events on the launch stream; a panel call: the sum over its DP launches); <0 if none. */
 double sarlacc_last_kernel_ms(void);
+/* Diagnostic, for tests: what the integer locator of this thread's last adaptor-align call reported, {I_max, lo, hi} per
+ * read (lo, hi in units of half a row, see align.hip LOC_NEG), 3 n int32 copied to host memory.  Valid until the next
+ * alignment call; an error where no locator has run for n reads.  Nothing in the reference corresponds. */
+int sarlacc_align_locate_records(int32_t* out, int64_t n);
 
 /* ------------------------------------------------------------------ */
 /* quality-weighted read-vs-reference DP                                 */
@@ -765,6 +769,10 @@ int sarlacc_set_msa_spec(int spec);
  *   "align_locate_trim" (adaptor_align's locator in its frame: -1 the fill loop without its trims; 1 the jump score's lane
  *   hand-over folded into its max alone, 2 the staging prefetch held as raw load results until the next refill alone, 3 both,
  *   which is the default),
+ *   "align_locate_shape" (adaptor_align's locator in its frame: 0 eight columns per lane and sixteen alignments per
+ *   wavefront for adaptors of 25 to 32 columns, with both trims; -1 the window kernel's shape, four columns per lane and
+ *   eight alignments per wavefront, everywhere; sarlacc_stage_count "align_locate_cols" reports the columns per lane of the
+ *   last call's locator, 0 without one),
  *   "align_panel" (sarlacc_*barcode_panel: -1 every barcode on its own with the device fold, none by the fused kernel),
  *   "profile_chunk_reads" (sarlacc_*profile_reads: reads per chunk; 0 = as many as the byte budget takes),
  *   "names_hash_bits" (sarlacc_dev_names_match: bits of the name hash kept for slot and tag, 1 .. 64; 0 = all 64.  A test

@@ -113,6 +113,7 @@ def _prototypes():
         "sarlacc_stage_ms": (f64, [s]),
         "sarlacc_stage_count": (f64, [s]),
         "sarlacc_last_kernel_ms": (f64, []),
+        "sarlacc_align_locate_records": (i, [p, i64]),
         "sarlacc_adaptor_align": (i, scored + [p, p, i, p, p, p, p, p]),
         "sarlacc_adaptor_align_score_only": (i, scored + [p]),
         "sarlacc_barcode_align": (i, scored + [p]),
@@ -276,3 +277,10 @@ def stage_count(name):
 
 def last_kernel_ms():
     return float(lib().sarlacc_last_kernel_ms())
+
+
+def align_locate_records(n):
+    """{I_max, lo, hi} per read as the locator of the last adaptor-align call reported them (n x 3 int32; diagnostic)."""
+    out = np.zeros((int(n), 3), dtype=np.int32)
+    check(lib().sarlacc_align_locate_records(out, int(n)))
+    return out

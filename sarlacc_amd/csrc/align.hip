@@ -42,6 +42,7 @@ namespace sarlacc {
 
 constexpr int NGMAX = 4;   // alignments processed side by side in one wavefront (groups of 16 lanes or more)
 constexpr int NGMAX2 = 8;  // ... with two 8-lane alignments interleaved in every 16-lane DPP row (ROWF 2)
+constexpr int NGMAX4 = 16; // ... with four 4-lane alignments interleaved in every DPP row (ROWF 4: the framed locator at eight columns per lane)
 constexpr int NWAVES = 4;  // wavefronts per workgroup: they share one copy of the cost table in LDS
 constexpr int RING = 128;        // staged read positions per alignment (2 x 64)
 constexpr int RING_MIRROR = 8;   // the first entries again behind the ring: a block of up to 8 steps reads base + 2u without wrapping
@@ -153,12 +154,15 @@ __device__ __forceinline__ double mk64(int hi, int lo) {
 // source lane and keeps `keep` (its DP column 0 value: pass the destination itself and the constant set before the
 // loop stays there for free).  ROWF 2: two 8-lane alignments share a DPP row, one in the even and one in the odd
 // lanes, and the hand-over is row_shr:2 -- lanes 0 and 1 of the row are the two leaders and again have no source.
-// Twice the columns per lane at the same width in columns: half the cross-lane moves per cell.  ROWF 0: across
+// Twice the columns per lane at the same width in columns: half the cross-lane moves per cell.  ROWF 4: four 4-lane
+// alignments share a DPP row, alignment a in the lanes = a mod 4, the hand-over is row_shr:4 and lanes 0 to 3 of the row
+// are the four leaders.  ROWF 0: across
 // the whole wave (wave_shr:1), leaders overwrite what arrives.
 template <int ROWF>
 __device__ __forceinline__ int lane_shr1(int v, int keep) {
     if (ROWF == 1) return __builtin_amdgcn_update_dpp(keep, v, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
     if (ROWF == 2) return __builtin_amdgcn_update_dpp(keep, v, 0x112 /* row_shr:2 */, 0xf, 0xf, false);
+    if (ROWF == 4) return __builtin_amdgcn_update_dpp(keep, v, 0x114 /* row_shr:4 */, 0xf, 0xf, false);
     return __builtin_amdgcn_update_dpp(v, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
 }
 // max(lane_shr1(v, -inf), other): the hand-over of a value whose only consumer is one max.  The fill value is the identity
@@ -166,9 +170,10 @@ __device__ __forceinline__ int lane_shr1(int v, int keep) {
 // a leader, which has no source lane, ends with `other`.
 template <int ROWF>
 __device__ __forceinline__ int lane_shr1_max(int v, int other) {
-    static_assert(ROWF == 1 || ROWF == 2, "row shifts only");
+    static_assert(ROWF == 1 || ROWF == 2 || ROWF == 4, "row shifts only");
     constexpr int NEG = -0x7fffffff - 1;
     if (ROWF == 1) return max(__builtin_amdgcn_update_dpp(NEG, v, 0x111 /* row_shr:1 */, 0xf, 0xf, false), other);
+    if (ROWF == 4) return max(__builtin_amdgcn_update_dpp(NEG, v, 0x114 /* row_shr:4 */, 0xf, 0xf, false), other);
     return max(__builtin_amdgcn_update_dpp(NEG, v, 0x112 /* row_shr:2 */, 0xf, 0xf, false), other);
 }
 template <int ROWF>
@@ -236,6 +241,10 @@ static inline int snap_win(int R, int W) { return (SNAP_P + snap_head(R) + W + 7
 // compare values of different rows of one block: the difference of their frames is a constant folded into D.  The
 // frame grows by GE 2^k per row, so the host picks k from the longest read as well (plan_locate) and falls back to MODE 5
 // where no k >= LOC_FRAME_KMIN fits.
+// ROWF 4: MODE 6 for 25 to 32 columns runs in a shape of its own, eight columns per lane, four lanes per alignment, sixteen
+// alignments per wavefront (four interleaved per DPP row, hand-over by row_shr:4), blocks still two rows tall: the work a lane
+// does per block beside its cells is shared by sixteen cells instead of eight.  The same cells, and column R's [lo, hi] as the
+// eight-lane shape reports them, to the row (see LOC_ODD in k_align); the window kernel keeps its shape, the hand-over is per read.
 constexpr int LOC_NEG = -(1 << 29);   // -inf of the integer DP (and of its table entries); cells stay above -2^27
 // -inf of a framed table entry.  Framed cells and intermediates lie in (-2^27, 2^30] (plan_locate), so diag' + LOC_NEG_FRAMED
 // neither leaves int32 nor passes a real cell: cell (i, c) is at least the horizontal path from column 0,
@@ -245,7 +254,8 @@ constexpr int LOC_NEG = -(1 << 29);   // -inf of the integer DP (and of its tabl
 constexpr int LOC_NEG_FRAMED = -(1 << 30);
 constexpr int LOC_FRAME_KMIN = 8;
 // resident wavefronts per SIMD of the locator kernel: at 4 it takes 114 VGPRs (115 in the frame) and spills nothing (at 6
-// and 8 its steady state reloads spilled registers from scratch)
+// and 8 its steady state reloads spilled registers from scratch).  At eight columns per lane (ROWF 4) it takes all 128 and
+// keeps about thirty dwords in scratch, touched at the refills and around the item loop, never inside a steady block
 constexpr int LOC_WAVES = 4;
 constexpr int LOC_STATS = 8;   // ints of AlignArgs::loc_stats
 // The codes of a MODE 4 window in LDS (WLDS).  A walk reads one code word per cell it visits, each load depending on the one
@@ -307,7 +317,8 @@ __global__ void __launch_bounds__(256) k_loc_order(const uint8_t* cls, long long
 // MODE 5 / 6: the locator fill of MODE 4 as a kernel of its own, plain / in the extension-free frame.
 // LOCAL: free leading read bases + free vertical gaps in the last column (adaptor mode).
 // ROWF: 0 alignments of any width, wave-wide shifts; 1 alignments are 16 lanes wide and start on DPP row
-// boundaries; 2 alignments are 8 lanes wide, two interleaved per DPP row (see lane_shr1).
+// boundaries; 2 alignments are 8 lanes wide, two interleaved per DPP row (see lane_shr1); 4 alignments are 4 lanes wide,
+// four interleaved per DPP row (the framed locator at K = 8 only).
 // KLAST: index (inside its lane) of reference column R when known at compile time, else -1.
 // PENSEL: select the gap penalty of every step explicitly (only needed when gapopen < 0).
 //
@@ -327,11 +338,12 @@ template <int K, int MODE, bool LOCAL, int ROWF, int KLAST, bool PENSEL, bool WL
 // (WLDS: the MODE 4 window with its codes in an LDS ring and the walk by whole lane groups, three wavefronts per SIMD, see WIN_LDS_WAVES)
 __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 ? LOC_WAVES : (MODE == 3 && ROWF != 2) ? 6 : 5) k_align(const AlignArgs A) {
     constexpr bool ROW16 = ROWF != 0;                      // leaders keep their column-0 inputs through the DPP fill operand
-    constexpr int NG = ROWF == 2 ? NGMAX2 : NGMAX;         // alignments per wavefront at most
+    constexpr int NG = ROWF == 4 ? NGMAX4 : ROWF == 2 ? NGMAX2 : NGMAX;   // alignments per wavefront at most
     // uint16 entries per alignment's ring slot: 512 B slots let a ring address be base | offset; with eight
     // alignments per wave the slots are packed (ring + mirror) and the address is an add
-    constexpr int SLOT = ROWF == 2 ? RING + RING_MIRROR : RING_SLOT;
-    constexpr int UNR = TbSteps<K>::value;
+    constexpr int SLOT = (ROWF == 2 || ROWF == 4) ? RING + RING_MIRROR : RING_SLOT;
+    // (ROWF 4 is the locator alone, which writes no codes: its blocks stay two rows tall, the granularity of [lo, hi])
+    constexpr int UNR = ROWF == 4 ? 2 : TbSteps<K>::value;
     constexpr int CELLS = UNR * K;
     using Word = typename TbStore<K>::type;
     constexpr bool ADDC = sizeof(Word) == 4;
@@ -347,19 +359,24 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // tell the compiler it is wave-uniform
-    const int W = A.W, R = A.R;
+    // ROWF 4: the locator's own shape, four lanes per alignment and sixteen alignments, whatever the window kernel's (A.W,
+    // A.ngroups: window_plan sizes the windows by them)
+    const int W = ROWF == 4 ? 4 : A.W, R = A.R, NGR = ROWF == 4 ? NGMAX4 : A.ngroups;
     // lane <-> (alignment g of the wave, lane j inside it)
-    auto lane_of = [&](int gg, int jj) -> int { return ROWF == 2 ? ((gg >> 1) << 4) + (jj << 1) + (gg & 1) : gg * W + jj; };
-    const int g = ROWF == 2 ? (((lane >> 4) << 1) | (lane & 1)) : lane / W;
-    const int j = ROWF == 2 ? ((lane & 15) >> 1) : lane - g * W;
-    const bool lane_on = g < A.ngroups;
+    auto lane_of = [&](int gg, int jj) -> int {
+        return ROWF == 4 ? ((gg >> 2) << 4) + (jj << 2) + (gg & 3) : ROWF == 2 ? ((gg >> 1) << 4) + (jj << 1) + (gg & 1) : gg * W + jj;
+    };
+    const int g = ROWF == 4 ? (((lane >> 4) << 2) | (lane & 3)) : ROWF == 2 ? (((lane >> 4) << 1) | (lane & 1)) : lane / W;
+    const int j = ROWF == 4 ? ((lane & 15) >> 2) : ROWF == 2 ? ((lane & 15) >> 1) : lane - g * W;
+    const bool lane_on = g < NGR;
     const bool leader = (j == 0);
     const int c0 = j * K + 1;
     const double NEG_INF = -__builtin_huge_val();
     const double GO = A.GO, GE = A.GE;
     const int GOhi = hi32(GO), GOlo = lo32(GO), GEhi = hi32(GE), GElo = lo32(GE);
 
-    static_assert(MODE < 4 || (ROWF == 2 && LOCAL && !PENSEL), "the locator runs the interleaved local shape only");
+    static_assert(MODE < 4 || ((ROWF == 2 || ROWF == 4) && LOCAL && !PENSEL), "the locator runs the interleaved local shapes only");
+    static_assert(ROWF != 4 || (MODE == 6 && K == 8 && KLAST >= 0), "four alignments per DPP row: the framed locator at eight columns per lane");
     static_assert(!WLDS || MODE == 4, "the LDS code ring belongs to the MODE 4 window");
     // the redo launch after a locator pass with an empty list: nothing to stage
     if (A.read_list && A.read_list[0] == 0) return;
@@ -416,10 +433,10 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
     __syncthreads();
 
     const long long nreads = A.read_list ? static_cast<long long>(A.read_list[0]) : A.n;   // redo launch: the list's length
-    const long long nitems = (nreads + A.ngroups - 1) / A.ngroups;
+    const long long nitems = (nreads + NGR - 1) / NGR;
     int wsteps = 0;   // MODE 4: window steps of this wave's items (wave-uniform; a wave owns a few items of 120 steps at most)
     for (long long item = gwave; item < nitems; item += nwaves) {
-        const long long slot_r = item * A.ngroups + g;
+        const long long slot_r = item * NGR + g;
         const bool valid = lane_on && slot_r < nreads;
         const long long read = A.read_list ? (valid ? static_cast<long long>(A.read_list[2 + slot_r]) : 0) : slot_r;
         long long start = 0;
@@ -432,21 +449,25 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
         long long gstart[NG];
         int glen[NG];
         int Lmax = 0, Lmin = 0x7fffffff;
+        int Lmin8[2] = {0x7fffffff, 0x7fffffff};   // ROWF 4: of the item's first and second eight reads (an item each in the eight-lane shape)
 #pragma unroll
         for (int gg = 0; gg < NG; ++gg) {
-            const int src = gg < A.ngroups ? lane_of(gg, 0) : 0;
+            const int src = gg < NGR ? lane_of(gg, 0) : 0;
             const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(start), src));
             const int hi = __builtin_amdgcn_readlane(static_cast<int>(start >> 32), src);
             const int len = __builtin_amdgcn_readlane(L, src);
             gstart[gg] = (static_cast<long long>(hi) << 32) | lo;
-            glen[gg] = gg < A.ngroups ? len : 0;
+            glen[gg] = gg < NGR ? len : 0;
             Lmax = max(Lmax, glen[gg]);
             // reads past the end of the batch (last work item) compute garbage nobody stores
-            if (gg < A.ngroups && item * A.ngroups + gg < nreads) Lmin = min(Lmin, glen[gg]);
+            if (gg < NGR && item * NGR + gg < nreads) {
+                Lmin = min(Lmin, glen[gg]);
+                if (ROWF == 4) Lmin8[gg >> 3] = min(Lmin8[gg >> 3], glen[gg]);
+            }
         }
 
         // Read staging, one refill (64 positions per alignment) ahead of use: lane -> (alignment sg = lane / 16, four
-        // consecutive positions), so one pass of the wave stages four alignments (two passes for eight).  A staged entry
+        // consecutive positions), so one pass of the wave stages four alignments (two passes for eight, four for sixteen).  A staged entry
         // is the byte offset of (base code, quality) inside a block of table rows; base codes 0-3 = ACGT, 4 = anything else.
         constexpr int NPASS = NG / 4;
         const int sq = (lane & 15) * 4;
@@ -455,9 +476,9 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
             sgs[ps] = (lane >> 4) + 4 * ps;
-            const int sgl = sgs[ps] < A.ngroups ? lane_of(sgs[ps], 0) : 0;
+            const int sgl = sgs[ps] < NGR ? lane_of(sgs[ps], 0) : 0;
             const int slen_any = __shfl(L, sgl);   // every lane takes part: a source lane switched off would read as 0
-            slens[ps] = sgs[ps] < A.ngroups ? slen_any : 0;
+            slens[ps] = sgs[ps] < NGR ? slen_any : 0;
             sstarts[ps] = (static_cast<long long>(__shfl(static_cast<int>(start >> 32), sgl)) << 32) |
                           static_cast<unsigned>(__shfl(static_cast<int>(start), sgl));
             stoffs[ps] = 0;
@@ -564,7 +585,7 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                                             : code * static_cast<uint32_t>(A.row_bytes) + static_cast<uint32_t>(qi << 3);
                 ent[e] = (r + e < slen) ? at : 0u;
             }
-            if (bad && !A.bad_done) atomicMin(A.badqual, A.read_base + static_cast<int>(item * A.ngroups + sg));
+            if (bad && !A.bad_done) atomicMin(A.badqual, A.read_base + static_cast<int>(item * NGR + sg));
             const uint2 w = make_uint2(ent[0] | (ent[1] << 16), ent[2] | (ent[3] << 16));
             uint16_t* const slot = s_ring + sg * SLOT + (r & (RING - 1));   // r is a multiple of 4: 8-byte aligned
             *reinterpret_cast<uint2*>(slot) = w;
@@ -639,7 +660,7 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                 Word pk = 0;
                 double v_first = 0.0;   // TR 2: vertical candidate of column R at the block's first step
                 // ring address of the block's first row; the following rows sit behind it (mirror: no wrap inside a block)
-                const uint32_t ring_blk = static_cast<uint32_t>(ROWF == 2 ? ring_g + (x2 & 0xff) : (ring_g | (x2 & 0xff)));
+                const uint32_t ring_blk = static_cast<uint32_t>(ROWF == 2 || ROWF == 4 ? ring_g + (x2 & 0xff) : (ring_g | (x2 & 0xff)));
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
                     if (ROWF == 0) {
@@ -777,6 +798,10 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
         int t_b = Lmin == 0x7fffffff ? 0 : ((Lmin + 1) / UNR) * UNR;  // first block leaving the shortest read
         t_a = min(t_a, nsteps);
         t_b = min(max(t_b, t_a), nsteps);
+        // (The framed locator's ROWF 4 shape restates these three for the ROWF 2 shape at K = 4 -- t_a = 8, t_b even and from the
+        // shortest of eight reads, two-row blocks -- to report the same [lo, hi]: see LOC_SHIFT below and change both together.
+        // Where they part, results stay right and only class bytes and the oversize list differ;
+        // tests/test_gpu_align_locate_k8.py compares the records of the two shapes read for read.)
         // MODE 5, pass 1 (see LOC_NEG): the lane of column R ends with I_max and the candidate rows [lo, hi] (x2 units),
         // which MODE 4 reads back
         int loc_max = 0, loc_lo = -2, loc_hi = -2;
@@ -798,19 +823,45 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
             // LTRIM & 1 (framed steady state): the horizontal jump score stays in the lane that formed it and its hand-over
             // rides on the consumer's max (see lane_shr1_max); lj_src is that score before the move
             constexpr bool FOLD = FRAMED && (LTRIM & 1) != 0;
+            // ROWF 4 with 25 to 28 columns (KLAST < 4): the steady state's blocks start on odd steps, see below
+            constexpr bool LOC_ODD = ROWF == 4 && KLAST < 4;
+            constexpr int LOC_SHIFT = LOC_ODD ? 3 : 4;
+            // ROWF 4 reports what the eight-lane shape reports, to the row.  [lo, hi] are exact rows in the guarded phases and
+            // block rows in the steady state, so column R must take the same rows by the same rule in the same blocks.  In
+            // that shape its lane, (R - 1) / 4, is 6 or 7 and its steady state covers the steps 8 to t_b of the read's own
+            // eight reads; here its lane is 3, LOC_SHIFT steps earlier on every row -- on odd steps where that lane was 6.  The
+            // steady state ends with the shorter of the item's two halves; the rows the other half would still have run in its
+            // steady state (steps below blk_end) take the block rule in the guarded phase.
+            int ta = t_a, tb = t_b, tn = nsteps, blk_end = 0;
+            if (ROWF == 4) {
+                // the partner: {K = 4, W = 8, ngroups = 8, rowf = 2} with two-row blocks (plan_align picks ROWF 4 beside no other)
+                static_assert(TbSteps<4>::value == 2 && NGMAX4 == 2 * NGMAX2, "ROWF 4 mirrors the schedule of the eight-lane shape at K = 4");
+                auto tb8 = [](int lmin) { return max(lmin == 0x7fffffff ? 0 : ((lmin + 1) / 2) * 2, 8); };   // (t_a = 8 <= nsteps there)
+                tn = Lmax + 4;
+                ta = min(8 - LOC_SHIFT, tn);
+                tb = min(max(tb8(Lmin) - LOC_SHIFT, ta), tn);
+                blk_end = tb8(g < 8 ? Lmin8[0] : Lmin8[1]) - LOC_SHIFT;
+            }
             auto run_loc = [&](auto guard_tag, int t_begin, int t_end) {
                 constexpr bool GUARD = decltype(guard_tag)::value;
                 constexpr int NO_ROW = -0x7fffffff - 1;
                 int hi_blk = NO_ROW;   // steady state: first row of the last block that sets loc_hi (the row loc_lo takes too)
+                int g_before = 0, g_xacc = LOC_NEG;   // ROWF 4, guarded: s_before and xacc of a block taken row by row
                 int lj_src = 0;
-                // what row_shr:2 will bring back: lji_in of the lane two to the right (the leaders' LOC_NEG is implied)
-                if (FOLD && !GUARD) lj_src = __builtin_amdgcn_update_dpp(lji_in, lji_in, 0x102 /* row_shl:2 */, 0xf, 0xf, false);
+                // what row_shr:2 (ROWF 4: row_shr:4) will bring back: lji_in of the lane two (four) to the right (the leaders'
+                // LOC_NEG is implied)
+                if (FOLD && !GUARD)
+                    lj_src = ROWF == 4 ? __builtin_amdgcn_update_dpp(lji_in, lji_in, 0x104 /* row_shl:4 */, 0xf, 0xf, false)
+                                       : __builtin_amdgcn_update_dpp(lji_in, lji_in, 0x102 /* row_shl:2 */, 0xf, 0xf, false);
                 // RAWPF: nothing the item's first loads returned is still in flight when the steady state begins, so its blocks
                 // hold no wait for global memory (the refills' own loads are waited for at the next refill)
                 if (RAWPF && !GUARD) __builtin_amdgcn_s_waitcnt(0x0f70 /* vmcnt(0) */);
                 for (int t0 = t_begin; t0 < t_end; t0 += UNR) {
-                    if ((t0 & 63) == 0) {
-                        int t0s = t0;
+                    // (blocks on odd steps, see LOC_ODD, refill one step early: the ring holds 128 positions, a lane reads
+                    // at most four behind the wave's first)
+                    const int t0r = LOC_ODD ? t0 + (t0 & 1) : t0;
+                    if ((t0r & 63) == 0) {
+                        int t0s = t0r;
                         asm volatile("" : "+s"(t0s));
 #pragma unroll
                         for (int ps = 0; ps < NPASS; ++ps) {
@@ -828,6 +879,7 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                     }
 #pragma unroll
                     for (int u = 0; u < UNR; ++u) {
+                        if (GUARD && ROWF == 4 && t0 + u >= t_end) break;   // (its phases end on any step)
                         int left = si_in, lj = lji_in;
                         const int s_two_back = di_prev;
                         bool act = true;
@@ -855,7 +907,17 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                                 const bool is_last = KLAST >= 0 ? (k == KLAST) : (k == klast);
                                 if (is_last) {
                                     // V is column R's running maximum before this row (free vertical gaps)
-                                    if (GUARD) {
+                                    if (GUARD && ROWF == 4 && t0 + u >= ta && t0 + u < blk_end) {
+                                        if (((t0 + u - ta) & 1) == 0) {
+                                            g_before = V;
+                                            g_xacc = X;
+                                        } else {
+                                            g_xacc = max(g_xacc, X - GEi);
+                                            const int bd = best - D_lo;
+                                            if (bd > g_before) loc_lo = x2 - 2;
+                                            if (g_xacc >= bd) loc_hi = x2;
+                                        }
+                                    } else if (GUARD) {
                                         if (best - D > V) loc_lo = x2;
                                         if (X + D >= best) loc_hi = x2;
                                     } else {
@@ -881,9 +943,9 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                 if (FOLD && !GUARD) lji_in = lane_shr1<ROWF>(lj_src, lji_in);   // the leaders keep their LOC_NEG
                 if (!GUARD && hi_blk != NO_ROW) loc_hi = hi_blk + 2 * (UNR - 1);
             };
-            run_loc(Flag<true>{}, 0, t_a);
-            run_loc(Flag<false>{}, t_a, t_b);
-            run_loc(Flag<true>{}, t_b, nsteps);
+            run_loc(Flag<true>{}, 0, ta);
+            run_loc(Flag<false>{}, ta, tb);
+            run_loc(Flag<true>{}, tb, tn);
             loc_max = Si[0];
 #pragma unroll
             for (int k = 1; k < K; ++k) loc_max = (k == klast) ? Si[k] : loc_max;
@@ -964,11 +1026,11 @@ __global__ void __launch_bounds__(64 * NWAVES, WLDS ? WIN_LDS_WAVES : MODE >= 5 
                 int nwin = 0, t_wa = 0, t_wb = 0x7fffffff;
 #pragma unroll
                 for (int gg = 0; gg < NG; ++gg) {
-                    const int src = gg < A.ngroups ? lane_of(gg, 0) : 0;
+                    const int src = gg < NGR ? lane_of(gg, 0) : 0;
                     toff[gg] = __builtin_amdgcn_readlane(ts, src);
                     const int pend = __builtin_amdgcn_readlane(pending, src);
                     const int need = __builtin_amdgcn_readlane(want + W + 1 - ts, src);
-                    if (gg < A.ngroups && pend) {
+                    if (gg < NGR && pend) {
                         nwin = max(nwin, need);
                         if (toff[gg] < W) t_wa = W;                 // lanes still entering the read
                         t_wb = min(t_wb, glen[gg] + 1 - toff[gg]);  // first step leaving it
@@ -2100,6 +2162,10 @@ struct AlignPlan {
     bool pensel = false, wide = false, classes = false, wide_queue = false;   // wide_queue: k_align_wide by k_align_wide_q
     size_t per_wave = 0, word_bytes = 4, lds = 0, redo_per_wave = 0;   // traceback tile of one wavefront (wide: of one workgroup), in words; LDS bytes
     long long grid = 0;
+    // MODE 4: the locator's own launch shape, KLAST and grid (the window and snapshot launches run in `sh`)
+    Shape loc_sh{1, 64, 1, 0};
+    int loc_klast = -1;
+    long long loc_grid = 0;
     int win_nb = 0, redo_grid = 0;   // window classes: the tiles (redo_per_wave) and the grid of the two small snapshot launches
     int wide_T = 0, wide_strips = 0, wide_band = 0;   // k_align_wide: threads, strips, see AlignArgs::wide_band
 };
@@ -2154,6 +2220,14 @@ static int plan_wide(const AlignJob& job, int num_cu, AlignPlan& p) {
     // stays on the device: no wait in between; none for reads of the reference's molecule).  align_wide_band = -1: no band.
     p.wide_band = kernel_mode == 0 || option(OPT_ALIGN_WIDE_BAND) < 0 ? 0 : (option(OPT_ALIGN_WIDE_BAND) > 0 ? option(OPT_ALIGN_WIDE_BAND) : WIDE_BAND);
     return 0;
+}
+
+// The framed locator's LTRIM (k_align): 1 the jump score's hand-over folded into its max (lane_shr1_max), 2 the staging
+// prefetch kept as raw load results until the next refill (RAWPF); both by default.  align_locate_trim = -1: neither (the
+// loop as it was: A/B, tests), 1 / 2: that one alone.
+static int locate_trim() {
+    const int o = option(OPT_ALIGN_LOCATE_TRIM);
+    return o < 0 ? 0 : o == 0 ? 3 : (o & 3);
 }
 
 // No HIP call and no allocation: the small per-call tables, the shape, the mode and the sizes of tiles, grid and LDS (and,
@@ -2248,6 +2322,16 @@ static int plan_align(const AlignJob& job, int num_cu, AlignPlan& p, LocPlan& lp
     }
     p.sh = sh; p.klast = sh.rowf == 2 || sh.K <= 2 ? (R - 1) % sh.K : -1; p.mode = kernel_mode; p.pensel = pensel;
     p.per_wave = per_wave_elems; p.word_bytes = word_bytes; p.grid = grid; p.lds = lds;
+    // The locator hands its results over per read, so it need not share the windows' shape: in the frame, with both trims
+    // and 25 to 32 columns it runs eight columns per lane, sixteen alignments per wavefront (ROWF 4), which halves the
+    // per-lane work around the recurrence per cell.  align_locate_shape = -1: the windows' shape (A/B, tests).
+    p.loc_sh = sh; p.loc_klast = p.klast; p.loc_grid = grid;
+    if (kernel_mode == 4 && lp.framed && sh.rowf == 2 && sh.K == 4 && R >= 25 && R <= 32 && locate_trim() == 3 &&
+        option(OPT_ALIGN_LOCATE_SHAPE) >= 0) {
+        p.loc_sh = {8, 4, NGMAX4, 4};
+        p.loc_klast = (R - 1) % 8;
+        p.loc_grid = align_grid((job.batch.n + NGMAX4 - 1) / NGMAX4, NWAVES, num_cu);   // (the locator writes no tile)
+    }
     return wide ? plan_wide(job, num_cu, p) : 0;
 }
 
@@ -2349,10 +2433,13 @@ static int raise_dynamic_lds(const void* kernel, size_t bytes) {
 // The instantiations of k_align the library is built with (each costs compile time and code-object size).
 // KLAST is known for one or two columns per lane and for interleaved alignments.
 constexpr bool shape_exists(int K, int rowf, int klast) {
+    if (rowf == 4) return K == 8 && klast >= 0 && klast < K;   // the framed locator of 25 to 32 columns
     if (rowf == 2) return (K == 2 || K == 4) && klast >= 0 && klast < K;
     return K <= 2 ? klast >= 0 && klast < K : klast == -1;
 }
-constexpr bool mode_exists(int rowf, int mode, bool local, bool pensel, bool wlds) {
+constexpr bool mode_exists(int rowf, int mode, bool local, bool pensel, bool wlds, int ltrim) {
+    if (ltrim != 0 && mode != 6) return false;
+    if (rowf == 4) return local && !pensel && !wlds && mode == 6 && ltrim == 3;   // plan_align asks for nothing else
     // interleaved alignments: local mode without penalty selects only (adaptor_align by snapshots or by the locator 5 / 6 and
     // its window 4, score-only)
     if (rowf == 2) return local && !pensel && (wlds ? mode == 4 : (mode == 0 || (mode >= 3 && mode <= 6)));
@@ -2360,10 +2447,11 @@ constexpr bool mode_exists(int rowf, int mode, bool local, bool pensel, bool wld
     return !wlds && (mode == 0 || (mode == 1 && local) || (mode == 3 && local && !pensel) || (mode == 2 && !local));
 }
 
-// One launch of k_align in the plan's shape; `mode` and `wlds` are the launch's (MODE 4 is a sequence of several).
+// One launch of k_align in shape `sh`; `mode` and `wlds` are the launch's (MODE 4 is a sequence of several).
 // (ltrim: the framed locator's LTRIM, see locate_trim)
-static int launch_k(const AlignPlan& p, int mode, bool wlds, const AlignArgs& a, int grid, size_t lds, hipStream_t s, int ltrim = 0) {
-    const bool il = p.sh.rowf == 2;
+static int launch_shape(const Shape& sh, int klast, bool pensel, int mode, bool wlds, const AlignArgs& a, int grid, size_t lds, hipStream_t s,
+                        int ltrim) {
+    const bool il = sh.rowf == 2 || sh.rowf == 4;
     if (ltrim && mode != 6) return fail("sarlacc_amd: internal error: a trimmed locator outside the frame");
     const int rc = pick([&](auto k_, auto r_, auto l_) {
         constexpr int K = decltype(k_)::value, ROWF = decltype(r_)::value, KLAST = decltype(l_)::value;
@@ -2372,26 +2460,22 @@ static int launch_k(const AlignPlan& p, int mode, bool wlds, const AlignArgs& a,
             const int rcm = pick([&](auto m_, auto g_, auto p_, auto w_, auto t_) {
                 constexpr int MODE = decltype(m_)::value, LTRIM = decltype(t_)::value;
                 constexpr bool LOCAL = decltype(g_)::value != 0, PENSEL = decltype(p_)::value != 0, WLDS = decltype(w_)::value != 0;
-                if constexpr (!mode_exists(ROWF, MODE, LOCAL, PENSEL, WLDS) || (LTRIM != 0 && MODE != 6)) return NO_KERNEL;
+                if constexpr (!mode_exists(ROWF, MODE, LOCAL, PENSEL, WLDS, LTRIM)) return NO_KERNEL;
                 else {
                     if constexpr (WLDS) SL_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(&k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS, LTRIM>), lds));
                     hipLaunchKernelGGL((k_align<K, MODE, LOCAL, ROWF, KLAST, PENSEL, WLDS, LTRIM>), dim3(grid), dim3(64 * NWAVES), lds, s, a);
                     return 0;
                 }
-            }, Ints<0, 1, 2, 3, 4, 5, 6>{}, mode, Ints<0, 1>{}, a.local, Ints<0, 1>{}, p.pensel, Ints<0, 1>{}, wlds, Ints<0, 1, 2, 3>{}, ltrim);
+            }, Ints<0, 1, 2, 3, 4, 5, 6>{}, mode, Ints<0, 1>{}, a.local, Ints<0, 1>{}, pensel, Ints<0, 1>{}, wlds, Ints<0, 1, 2, 3>{}, ltrim);
             return rcm != NO_KERNEL ? rcm : fail(il ? "sarlacc_amd: interleaved alignments serve local modes 0 and 3 only" : "sarlacc_amd: unsupported alignment mode");
         }
-    }, Ints<1, 2, 4, 8, 16>{}, p.sh.K, Ints<0, 1, 2>{}, p.sh.rowf, Ints<-1, 0, 1, 2, 3>{}, p.klast);
+    }, Ints<1, 2, 4, 8, 16>{}, sh.K, Ints<0, 1, 2, 4>{}, sh.rowf, Ints<-1, 0, 1, 2, 3, 4, 5, 6, 7>{}, klast);
     // (an interleaved shape with K and mode both unknown raised the mode's message before: plan_align produces neither)
-    return rc != NO_KERNEL ? rc : fail(il ? "sarlacc_amd: unsupported columns-per-lane %d for interleaved alignments" : "sarlacc_amd: unsupported columns-per-lane %d", p.sh.K);
+    return rc != NO_KERNEL ? rc : fail(il ? "sarlacc_amd: unsupported columns-per-lane %d for interleaved alignments" : "sarlacc_amd: unsupported columns-per-lane %d", sh.K);
 }
-
-// The framed locator's LTRIM (k_align): 1 the jump score's hand-over folded into its max (lane_shr1_max), 2 the staging
-// prefetch kept as raw load results until the next refill (RAWPF); both by default.  align_locate_trim = -1: neither (the
-// loop as it was: A/B, tests), 1 / 2: that one alone.
-static int locate_trim() {
-    const int o = option(OPT_ALIGN_LOCATE_TRIM);
-    return o < 0 ? 0 : o == 0 ? 3 : (o & 3);
+// ... in the plan's shape
+static int launch_k(const AlignPlan& p, int mode, bool wlds, const AlignArgs& a, int grid, size_t lds, hipStream_t s, int ltrim = 0) {
+    return launch_shape(p.sh, p.klast, p.pensel, mode, wlds, a, grid, lds, s, ltrim);
 }
 
 // MODE 4: the locator, the windows, the snapshot kernel on what they could not certify.
@@ -2399,8 +2483,9 @@ static int launch_locate(const AlignPlan& p, const AlignArgs& a, const LocLaunch
     const int grid = static_cast<int>(p.grid);
     // the locator (its LDS: rings + the integer table), the windows, then the snapshot kernel on the reads the windows
     // put on their list (count read on the device)
-    const size_t lds5 = sizeof(uint16_t) * NWAVES * NGMAX2 * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
-    SL_TRY(launch_k(p, a.loc_framed ? 6 : 5, false, a, grid, lds5, s, a.loc_framed ? locate_trim() : 0));
+    const size_t lds5 = sizeof(uint16_t) * NWAVES * p.loc_sh.ngroups * (RING + RING_MIRROR) + sizeof(int) * a.tab_doubles + 16;
+    SL_TRY(launch_shape(p.loc_sh, p.loc_klast, p.pensel, a.loc_framed ? 6 : 5, false, a, static_cast<int>(p.loc_grid), lds5, s,
+                        a.loc_framed ? locate_trim() : 0));
     AlignArgs r = a;
     r.bad_done = 1;
     // the windows: with the code ring in LDS behind the maps (three wavefronts per SIMD), or the tile alone
@@ -2496,6 +2581,8 @@ static int report_align(const AlignPlan& p, const LocPlan& lp, const AlignArgs& 
         for (int x = 1; x < LOC_NCLS; ++x) c.counts["align_window_class_" + std::to_string(x)] = d_ccount ? ccount[x] : -1.0;
         // the locator's scale 2^k, negative where it ran un-framed (0: no locator)
         c.counts["align_locate_k"] = d_stats ? (lp.framed ? lp.k : -lp.k) : 0.0;
+        // the columns a lane of the locator owns (0: no locator)
+        c.counts["align_locate_cols"] = d_stats ? p.loc_sh.K : 0.0;
     }
     if (flags[1]) return fail("sarlacc_amd: internal error: an alignment traceback exceeded its bound");
     return 0;

@@ -26,7 +26,7 @@ int fail(const char* fmt, ...) {
 }
 
 static const char* const kOptNames[OPT_N] = {"msa_spec", "msa2_general_rows", "msa2_chain_hbm", "msa2_waves_per_cu", "msa2_single_wave", "msa2_batches", "align_pensel", "align_chunks",
-                                             "align_k", "align_waves_per_cu", "consensus_chars", "consensus_generic", "msa_int32", "msa_affine", "umi_full_rounds", "umi_tile_search", "msa_bitvector", "msa_bitvector_core", "msa_bitvector_tile_gb", "align_interleave", "umi_split_min", "msa2_tight_profiles", "umi_scan_single", "align_wide_barrier", "msa2_budget_gb", "msa2_max_columns", "align_wide_band", "msa2_simple_extend", "msa2_wide_extend", "align_locate", "align_panel", "profile_chunk_reads", "align_window_classes", "align_window_lds", "align_locate_trim", "names_hash_bits"};
+                                             "align_k", "align_waves_per_cu", "consensus_chars", "consensus_generic", "msa_int32", "msa_affine", "umi_full_rounds", "umi_tile_search", "msa_bitvector", "msa_bitvector_core", "msa_bitvector_tile_gb", "align_interleave", "umi_split_min", "msa2_tight_profiles", "umi_scan_single", "align_wide_barrier", "msa2_budget_gb", "msa2_max_columns", "align_wide_band", "msa2_simple_extend", "msa2_wide_extend", "align_locate", "align_panel", "profile_chunk_reads", "align_window_classes", "align_window_lds", "align_locate_trim", "align_locate_shape", "names_hash_bits"};
 static int* option_values() {
     static int values[OPT_N];
     static const bool parsed = [] {
@@ -253,6 +253,16 @@ double sarlacc_stage_count(const char* name) {
     if (!name) return -1.0;
     auto it = c.counts.find(name);
     return it == c.counts.end() ? -1.0 : it->second;
+}
+
+int sarlacc_align_locate_records(int32_t* out, int64_t n) {
+    sarlacc::Context& c = sarlacc::ctx();
+    auto it = c.ws.find("align.lout");   // (run_align's scratch of that name; the call that filled it has waited for its stream)
+    const size_t bytes = n > 0 ? static_cast<size_t>(n) * 3 * sizeof(int32_t) : 0;
+    if (!out || n <= 0 || it == c.ws.end() || !it->second.ptr || it->second.cap < bytes || c.counts["align_locate_cols"] <= 0)
+        return sarlacc::fail("sarlacc_amd: no locator records of %lld reads", static_cast<long long>(n));
+    SL_HIP(hipMemcpy(out, it->second.ptr, bytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 double sarlacc_last_kernel_ms(void) {

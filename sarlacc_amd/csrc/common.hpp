@@ -73,6 +73,7 @@ enum Opt {
     OPT_ALIGN_WINDOW_CLASSES, // adaptor_align by the locator: -1 the windows in index order, one redo list filled by the window kernel and its launch on the caller's stream (A/B, tests)
     OPT_ALIGN_WINDOW_LDS,     // adaptor_align by the locator: -1 the window's codes in the global tile alone, five wavefronts per SIMD (A/B, tests); >= 2 that many blocks in the LDS code ring (tests)
     OPT_ALIGN_LOCATE_TRIM,    // adaptor_align's framed locator: -1 the fill loop without its trims (A/B, tests); 1 the folded hand-over of the jump score alone, 2 the raw staging prefetch alone, 3 both (the default)
+    OPT_ALIGN_LOCATE_SHAPE,   // adaptor_align's framed locator: 0 eight columns per lane, sixteen alignments per wavefront, where built (25 to 32 columns, both trims); -1 the window kernel's shape, four columns per lane (A/B, tests)
     OPT_NAMES_HASH_BITS,      // name match of readGroups: bits of the name hash kept for slot and tag (0 = all 64; tests keep 1 to 8 so that every probe walks chains of unequal keys)
     OPT_N
 };
