@@ -517,6 +517,43 @@ int sarlacc_dev_links_verify(const uint8_t* d_seq, const int64_t* d_off, int64_t
 int sarlacc_dev_components(const uint64_t* d_links, int64_t n_links, int64_t n, const int32_t* d_nkmers, int32_t* d_label,
                            int64_t* n_groups, void* stream);
 
+/* Resident reads assigned to references (generics.referenceGroups; csrc/ref_map.hip; the rules are DESIGN.md §4.20, M1 to
+ * M6).  Both sides are sketched by sarlacc_dev_sketch_reads with the same k and buckets; two calls on data already in
+ * device memory follow, each usable alone; the chosen references go to CSR groups by sarlacc_dev_labels_csr.  Every
+ * result is exact and the same from run to run: no value depends on the order in which atomics arrive.  Both calls
+ * return when the device has finished.
+ * sarlacc_dev_sketch_candidates (rules M2 and M3): d_ref_sketch (n_refs * buckets words) and d_read_sketch (n_reads *
+ * buckets words), both below 2^31 words, are sketches as sarlacc_dev_sketch_reads writes them: entry j of a sketch is
+ * 2^64 - 1 or a hash h with h >> (64 - log2 buckets) == j ("reference sketch K, bucket J: ..." / "read sketch K, bucket J:
+ * the entry is neither empty nor a hash of that bucket", K 1-based).  A hit is (read r, reference f, bucket j) with
+ * d_read_sketch[r * buckets + j] == d_ref_sketch[f * buckets + j] != 2^64 - 1; every reference that holds the hash
+ * counts, however many there are.  shared(r, f) is the number of such j; *n_hits (host; may be NULL) the number of all hits,
+ * which must stay below 2^31.  The candidates of a read are the references with shared >= min_shared (1 .. buckets),
+ * ranked by shared descending, then by reference ascending; the first max_candidates (1 .. 16) are kept.  d_cand_ref and
+ * d_cand_shared (int32, n_reads * max_candidates each) get row r = the kept candidates of read r in rank order, unused
+ * slots -1 / 0; d_ncand[r] their number.  n_refs == 0 leaves every row unused; n_reads == 0 launches nothing.
+ * sarlacc_dev_candidates_assign (rules M4 and M5): d_cand_ref / d_cand_shared are such a table (a slot of -1 is unused,
+ * wherever it stands; rank = slot).  max_diff_ppm in 0 .. 999999: every used slot is checked as
+ * sarlacc_dev_links_verify checks a link, with a = the reference (d_ref_seq, the n_refs + 1 offsets d_ref_off) and b =
+ * the read (d_read_seq, d_read_off): same equality, D_w with w = bandwidth (0 .. 127), t = max_diff_ppm * max(la, lb) div
+ * 10^6, forward first (strand 0), then, only with both_strands != 0, the read reverse-complemented (strand 1: the read is
+ * the reference's reverse strand).  Among the slots that pass, the one of smallest dist is chosen, the lowest slot among
+ * equals.  max_diff_ppm < 0: no check; slot 0 is chosen if used, with dist -1 and strand 0, and neither sequence buffer
+ * is read.  Per read (n_reads entries): d_reference (-1: none), d_strand, d_dist (-1: none, or unchecked), d_shared (the
+ * chosen slot's d_cand_shared, 0: none).  d_cand_dist / d_cand_strand (may be NULL; n_reads * max_candidates) get every
+ * slot's result: the distance, -1 where the slot is unused, fails or was not checked, and the strand.  *n_checked (host;
+ * may be NULL) counts the used slots handed to the check.  No byte outside a pair's two sequences is read.  "read K:
+ * candidate outside 0 .. n_refs - 1", "reference K: ..." / "read K: its offsets do not ascend inside the sequence buffer,
+ * or it has 2^31 bases or more" (K 1-based): nothing that rests on such an entry is launched. */
+int sarlacc_dev_sketch_candidates(const uint64_t* d_ref_sketch, int64_t n_refs, const uint64_t* d_read_sketch, int64_t n_reads,
+                                  int buckets, int min_shared, int max_candidates, int32_t* d_cand_ref, int32_t* d_cand_shared,
+                                  int32_t* d_ncand, int64_t* n_hits, void* stream);
+int sarlacc_dev_candidates_assign(const uint8_t* d_ref_seq, const int64_t* d_ref_off, int64_t n_refs, const uint8_t* d_read_seq,
+                                  const int64_t* d_read_off, int64_t n_reads, const int32_t* d_cand_ref, const int32_t* d_cand_shared,
+                                  int max_candidates, int bandwidth, int64_t max_diff_ppm, int both_strands, int32_t* d_reference,
+                                  uint8_t* d_strand, int32_t* d_dist, int32_t* d_shared, int32_t* d_cand_dist, uint8_t* d_cand_strand,
+                                  int64_t* n_checked, void* stream);
+
 /* SAM alignment records already in device memory -> ranges (sam2ranges, R/sam2ranges.R:8-95).  d_text holds
  * body lines of a SAM file (no header), LF or CRLF, blank lines skipped; first_line is the 1-based file line
  * number of its first line, used in error messages.  The caller reads the header: ref_names / ref_off (n_ref + 1

@@ -165,6 +165,8 @@ def _prototypes():
         "sarlacc_dev_sketch_links": (i, [p, i64, i, i, i, p, i64, p, p, p]),
         "sarlacc_dev_links_verify": (i, [p, p, i64, p, i64, i, i64, i, p, p, p, p, p]),
         "sarlacc_dev_components": (i, [p, i64, i64, p, p, p, p]),
+        "sarlacc_dev_sketch_candidates": (i, [p, i64, p, i64, i, i, i, p, p, p, p, p]),
+        "sarlacc_dev_candidates_assign": (i, [p, p, i64, p, p, i64, p, p, i, i, i64, i, p, p, p, p, p, p, p, p]),
         "sarlacc_dev_sam_index": (i, [p, i64, i64, p, p, i64, p, p, p, i64, i, i64, p, p, p, p]),
         "sarlacc_dev_sam_extract": (i, [p, p, p, p, p, p, p, p, p, p]),
         "sarlacc_dev_bam_index": (i, [p, i64, i64, i, i64, p, i, i64, p, p, p, p, p]),

@@ -9,6 +9,32 @@ namespace sarlacc {
 constexpr uint64_t SK_EMPTY = ~0ull;      // an empty bucket of a sketch; a k-mer whose hash is this value counts as absent
 constexpr int SK_MAX_BUCKETS = 256;       // 2 KB of LDS per wavefront
 
+// ---- what the host sides of the sketch calls share (sketch_host.cpp, ref_map_host.cpp) ----
+constexpr long long SK_LIMIT = 1LL << 31;
+
+inline int count_ok(int64_t n, const char* what) {
+    if (n < 0) return fail("sarlacc_amd: negative number of %s", what);
+    if (n >= SK_LIMIT) return fail("sarlacc_amd: %lld %s: at most 2^31 - 1", static_cast<long long>(n), what);
+    return 0;
+}
+
+// log2 of a power of two in 16 .. 256, -1 otherwise
+inline int buckets_log2(int buckets) {
+    for (int b = 4; b <= 8; ++b)
+        if (buckets == 1 << b) return b;
+    return -1;
+}
+
+// `body` as one segment of the stage timer `name`, which starts a new call
+template <typename F>
+int staged(const char* name, hipStream_t s, F&& body) {
+    Context& c = ctx();
+    c.stage_reset(name);
+    SL_TRY(c.stage_begin(name, s));
+    SL_TRY(body());
+    return c.stage_end(name, s);
+}
+
 // The words a call's kernels report through (one scratch block, set up by sk_state_reset): every `bad_*` is an atomicMin
 // over ~0, the counters are sums.
 struct SkState {

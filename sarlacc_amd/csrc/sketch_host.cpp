@@ -15,21 +15,6 @@
 namespace sarlacc {
 namespace {
 
-constexpr long long SK_LIMIT = 1LL << 31;
-
-int count_ok(int64_t n, const char* what) {
-    if (n < 0) return fail("sarlacc_amd: negative number of %s", what);
-    if (n >= SK_LIMIT) return fail("sarlacc_amd: %lld %s: at most 2^31 - 1", static_cast<long long>(n), what);
-    return 0;
-}
-
-// log2 of a power of two in 16 .. 256, -1 otherwise
-int buckets_log2(int buckets) {
-    for (int b = 4; b <= 8; ++b)
-        if (buckets == 1 << b) return b;
-    return -1;
-}
-
 int state_begin(SkState** d_state, hipStream_t s) {
     SL_TRY(scratch("sk.state", 1, d_state));
     return sk_state_reset(*d_state, s);
@@ -39,15 +24,6 @@ int state_fetch(const SkState* d_state, SkState* host, hipStream_t s) {
     SL_HIP(hipMemcpyAsync(host, d_state, sizeof(SkState), hipMemcpyDeviceToHost, s));
     SL_HIP(hipStreamSynchronize(s));
     return 0;
-}
-
-template <typename F>
-int staged(const char* name, hipStream_t s, F&& body) {
-    Context& c = ctx();
-    c.stage_reset(name);
-    SL_TRY(c.stage_begin(name, s));
-    SL_TRY(body());
-    return c.stage_end(name, s);
 }
 
 }  // namespace

@@ -76,12 +76,13 @@ def to_host_strings(seq, qual, off, count):
 
 
 def make_molecule_reads(molecules, copies, read_len, seed, device, umi_len=12, sub_rate=0.05, indel_rate=0.01,
-                        max_insert=5, chunk=8192):
+                        max_insert=5, chunk=8192, keep_truth=False):
     """BASELINE configs C3 + C4 generated in HBM: `molecules` random bodies of `read_len` bases and
     random `umi_len`-base UMIs, each observed `copies` times through the mockReads error process
     (5 % substitutions by a uniform base, 1 % indel events with k in {0,2..5} copies, qualities from
     error probabilities ~ U(0, 0.06)); reads are in molecule order (read r comes from molecule r // copies).
-    Returns dict(seq, qual, off, umi, umi_off, max_len) of device tensors (uint8 / int64)."""
+    Returns dict(seq, qual, off, umi, umi_off, max_len) of device tensors (uint8 / int64); with keep_truth also
+    "truth", the molecules x read_len bodies the reads were made from."""
     g = torch.Generator(device=device)
     g.manual_seed(int(seed))
     nuc = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device=device)
@@ -98,10 +99,12 @@ def make_molecule_reads(molecules, copies, read_len, seed, device, umi_len=12, s
         flat = torch.repeat_interleave(r.reshape(-1), counts.reshape(-1))
         return flat, counts.sum(dim=1)
 
-    seqs, quals, lens, umis, ulens = [], [], [], [], []
+    seqs, quals, lens, umis, ulens, bodies = [], [], [], [], [], []
     for lo in range(0, molecules, chunk):
         m = min(chunk, molecules - lo)
         body = nuc[torch.randint(0, 4, (m, read_len), generator=g, device=device)]
+        if keep_truth:
+            bodies.append(body)
         flat, ln = noisy(body)
         seqs.append(flat)
         quals.append(_phred_from_uniform(torch.rand(flat.numel(), generator=g, device=device), sub_rate + indel_rate))
@@ -118,4 +121,4 @@ def make_molecule_reads(molecules, copies, read_len, seed, device, umi_len=12, s
     uoff = torch.zeros(n + 1, dtype=torch.int64, device=device)
     uoff[1:] = torch.cumsum(ulens, 0)
     return {"seq": torch.cat(seqs), "qual": torch.cat(quals), "off": off, "umi": torch.cat(umis), "umi_off": uoff,
-            "max_len": int(lens.max().item())}
+            "max_len": int(lens.max().item()), **({"truth": torch.cat(bodies)} if keep_truth else {})}

@@ -67,6 +67,26 @@ def read_fastq(path):
     return Reads(seqs, quals, names)
 
 
+def read_fasta(path):
+    """FASTA -> Reads without qualities (qual None), with names: the references of referenceGroups and profileReads.
+    Host reader.  A record is a '>' line and the lines up to the next one, joined; its name is the header up to, and not
+    including, its first whitespace; sequences are upper-cased; blank lines are skipped.  A gzip or BGZF file is read
+    through Python's gzip module.  Sequence before the first header is refused."""
+    from .bgzf import open_text
+    names, seqs = [], []
+    with open_text(path) as fh:
+        for number, line in enumerate(fh, 1):
+            line = line.strip()
+            if line.startswith(b">"):
+                names.append((line[1:].split(None, 1) or [b""])[0].decode())
+                seqs.append([])
+            elif line:
+                if not seqs:
+                    raise ValueError("%s, line %d: sequence before the first '>' line" % (path, number))
+                seqs[-1].append(line.upper())
+    return Reads([b"".join(parts) for parts in seqs], None, names)
+
+
 def read_bam(path, exclude_flags=0x900, missing_qual=1, tags=None):
     """The reads of a BAM file -> Reads: resident.DeviceReads.from_bam (unpacked on the device), downloaded, with their
     names.  The qualities are Phred+33.  With `tags`, a tuple of tag names, the result is (Reads, {name: (values,
@@ -883,3 +903,51 @@ def sequenceGroups(reads, k=13, buckets=64, window=8, min_shared=3, canonical=Tr
     from .sketch import sequence_groups
     return sequence_groups(reads, k=k, buckets=buckets, window=window, min_shared=min_shared, canonical=canonical,
                            identity=identity, bandwidth=bandwidth)
+
+
+# ---------------------------------------------------------------------------
+# referenceGroups: reads assigned to the expected sequences without leaving the device (both vignettes' mapping step)
+
+def referenceGroups(reads, references, k=13, buckets=64, min_shared=2, max_candidates=4, identity=0.8, bandwidth=100,
+                    both_strands=True):
+    """The mapping step of the reference's two vignettes for a user who has the expected sequences -- spike-ins, a
+    transcript panel, a transcriptome: the `pre.groups` of umiGroup(groups=) by the correction vignette's first route
+    ("each set of reads mapping to the same transcript would then be defined as a single group") and the reference of
+    every read that profileReads(assignment=) needs, without writing the reads out, an outside mapper and a SAM file.
+    It is not minimap2 and claims no parity; the stage follows a specification of its own (rules M1
+    to M6).  `reads` is a resident.DeviceReads (used where it lies) or a Reads (uploaded); `references` a list of
+    strings (upper-cased here, as profileReads does), a Reads (read_fasta returns one) or a DeviceReads; names are not
+    needed.
+    M1: both sides get sequenceGroups' one-permutation MinHash sketch (its rules 1 to 4) with the same `k` and `buckets`;
+    with `both_strands` a k-mer and its reverse complement are one.  M2: a hit is a bucket in which a read's sketch and
+    a reference's hold the same hash; shared(read, reference) counts them; there is no window, every reference that
+    holds the hash counts.  M3: the candidates of a read are the references with shared >= `min_shared` (1 .. buckets),
+    ranked by shared descending, then reference index ascending; the first `max_candidates` (1 .. 16) are kept.  M4, only
+    with `identity` (a number in (0, 1], or None): every kept candidate is checked by the alignment of sequenceGroups'
+    rule 6a with the reference as its first and the read as its second sequence -- unit-cost edit distance inside the
+    band |j - i| <= `bandwidth` (0 .. 127), at most (max_diff_ppm * max(la, lb)) // 10^6 with max_diff_ppm =
+    int(round((1 - identity) * 10^6)); forward first (strand 0), then, with `both_strands`, the read reverse-
+    complemented (strand 1: the read is the reference's reverse strand).  M5: among the candidates that pass, the one
+    of smallest distance wins, the better-ranked among equals; with identity=None the best-ranked candidate wins
+    unchecked (dist -1, strand 0).  A read with no candidate, or none that passes, gets reference -1.  M6: the group of
+    a read is its reference.
+    The distance is global: filterReads keeps reads with both adaptors and realizeReads trims them, so the reads that
+    come here are whole molecules and "this read is that transcript" is a global question; a truncated read, or a
+    reference longer than its read by more than the bound, is left unassigned rather than guessed.  One noisy read
+    against its clean reference differs by the per-read error rate, so 0.8 leaves room at the mock rates (5 %
+    substitutions, 1 % indels: every one of 10^6 2-kb reads reached its own one of 10^5 transcripts); at twice them it
+    left 4 % of such reads unassigned and put none on a wrong transcript, where identity=None put 693 on a wrong one
+    (profiles/reference_groups.txt).  The sketch only proposes: `min_shared` 1 or 2 with a check is the
+    sensitive setting, and `max_candidates` bounds what a read can cost where references share sequence.
+    Returns a dict in the reads' order, shaped as readGroups returns it: "reference" (int32, -1 none: what
+    profileReads(assignment=) takes), "strand" (uint8), "dist" (int32, -1 none or unchecked), "shared" (int32, of the
+    chosen candidate, 0 none), "n.candidates" (int32, candidates kept), "n.kmers" (int32 per read), "ref.n.kmers" (int32
+    per reference), "group" (equal to "reference"), "groups" (the CSR pair (off int64[G + 1], members int32, 1-based,
+    ascending) of the distinct assigned references ascending; strset.lists_from_csr(*out["groups"]) is the list
+    umiGroup(groups=) takes), "n.hits" (int64) and, with `identity`, "n.checked" (int64: candidates handed to the check).
+    Every result is exact and the same from run to run.  Bad arguments raise ValueError before a device is touched; no
+    reads, or no references, return the result in which no read has a reference without one: nothing is sketched then,
+    and the k-mer counts are -1."""
+    from .refmap import reference_groups
+    return reference_groups(reads, references, k=k, buckets=buckets, min_shared=min_shared, max_candidates=max_candidates,
+                            identity=identity, bandwidth=bandwidth, both_strands=both_strands)
